@@ -17,7 +17,8 @@ collective) to rank 0 is inside the timed region.
 Inputs are synthetic and resident in HBM before the timed region: developed-flow initial state from
 tests/golden/rayleigh_128x64_init.npz (float64 oracle warm-up), actions from
 numpy.random.default_rng(1234).uniform(-1, 1, (steps, global batch, 10)), distinct per replica and step.
-Prints ONE JSON line on rank 0."""
+Prints ONE JSON line on rank 0.  --dump-outputs DIR also writes what the last timed step returned (obs, rwd, done, trunc)
+as DIR/<name>.npy, so that two builds can be compared output for output."""
 import argparse
 import json
 import os
@@ -70,7 +71,39 @@ def parse_args(argv=None):
     ap.add_argument("--stub", action="store_true",
                     help="CPU stand-in env (no GPU, no kernels): exercises launcher, sharding and gather only; "
                          "its line is marked data=stub and is not a measurement")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller (obs, rwd, done, trunc; "
+                         "rank 0: the gathered global batch) as DIR/<name>.npy, obs / rwd in the run's float type, done / trunc "
+                         "as float32: two builds run with the same arguments can be compared output for output (bench_outputs/ is "
+                         "ignored by git)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, result):
+    """result: (obs, rwd, done, trunc) of the last timed step -> outdir/<name>.npy (float32 / float64); returns the file names.
+    Above DUMP_MAX_BYTES in all, a fixed seeded sample of the replicas (rows) is written, their indices as replica_index.npy."""
+    import numpy as np
+    arrs = {}
+    for name, t in zip(("obs", "rwd", "done", "trunc"), result):
+        a = t.detach().cpu().numpy()
+        arrs[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float32)
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_MAX_BYTES:
+        n = arrs["rwd"].shape[0]
+        keep = max(1, DUMP_MAX_BYTES // (total // n + 8))        # + 8 bytes per row for its index
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrs = {k: v[idx] for k, v in arrs.items()}
+        arrs["replica_index"] = idx.astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrs.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return [name + ".npy" for name in arrs]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -605,7 +638,7 @@ def main():
         use_ev = not args.stub
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(K)] if use_ev else []
         sweeps_all = []
-        pend = None
+        pend = res = None
         # rank 0 takes delivery on its own stream, as a trainer's copy stream would: the step stream never waits for a gather
         # younger than three steps (ShardedVecEnv.NBUF output buffers)
         consumer = torch.cuda.Stream(device=dev) if (use_ev and collective and senv.overlap) else None
@@ -627,20 +660,24 @@ def main():
             if collective and senv.overlap:
                 p = senv.step_async(acts[W + k], scattered=True)   # the one HIP launch of this step + its gather (side stream)
             else:
-                env.step(acts[W + k])                              # the one HIP launch of this step (torch's current stream)
+                res = env.step(acts[W + k])                        # the one HIP launch of this step (torch's current stream)
             if use_ev:
                 ev[k][1].record()
             sweeps_all.append(env.sweeps.clone())       # tiny device copy, for the roofline accounting
             if collective and not senv.overlap:
-                senv._gather()                          # --no-overlap: blocking collective between two steps
+                g = senv._gather()                      # --no-overlap: blocking collective between two steps
+                res = None if g is None else (g[0], g[1], g[3], g[4])
             if pend is not None:
                 deliver(pend)                           # rank 0 takes delivery of step k - 1 while step k runs
             pend = p
         if pend is not None:
             deliver(pend)
+            res = pend.result
         sync()
         elapsed = time.perf_counter() - t0
         gc.enable()
+        # what the caller of the timed path received from its last step (rank 0 of a collective: the gathered batch)
+        timed_steps.last_outputs = None if res is None or res[0] is None else tuple(res[:4])
         env.check_status()
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         if dist.is_initialized():
@@ -666,6 +703,9 @@ def main():
 
     elapsed, kern_ms, sweeps_all = timed_steps(env, senv, acts, W, K, distc, keep_state)
     own_elapsed = timed_steps.own_elapsed
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, timed_steps.last_outputs)
     state_after_warmup = saved.get("state")
     cyc = env.get_counters().astype(np.float64)     # of the last step
 
@@ -865,6 +905,8 @@ def main():
                          "solves_last_step": int(B * env.ndt_act)}
         if strong is not None:
             out["strong"] = strong
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped, "of_step": W + K - 1}
         # (the N > 1 rehearsal BEFORE the CPU legs: the C oracle's OpenMP workers keep spinning on every host core after
         #  their parallel regions, and the blocking gather's host side then measured 2 ms per step late)
         # Nothing below may cost the headline that is already measured: a failure of a secondary leg (RCCL rendezvous of the

@@ -186,7 +186,7 @@ def test_rayleigh_batch_vs_oracle_f64(variant):
     env.close()
 
 
-def test_rayleigh_fast_schedulers_match_single_launch():
+def test_rayleigh_fast_schedulers_match_single_launch(tmp_path):
     """The fast path splits a step into [0,Q) + LPT-ordered [Q,ndt) when replicas outnumber
     the CUs; forced here on a small batch: obs, rewards, sweep counts and interior fields must
     equal the unsplit run bit for bit (only the p ghost cells, rebuilt once per launch from the
@@ -211,7 +211,7 @@ def test_rayleigh_fast_schedulers_match_single_launch():
     outs = []
     # bcn_set_sched(mode, grid, q, lpt_min_batch) per handle (no environment variable changes the scheduling)
     for tag, sched in (("split", "1,0,0,2"), ("single", "0,0,0,0"), ("ticket", "2,5,0,0")):
-        path = "/tmp/bcn_lpt_%s.npy" % tag
+        path = str(tmp_path / ("bcn_lpt_%s.npy" % tag))
         r = subprocess.run([sys.executable, "-c", code, path, sched], capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]
         outs.append(np.load(path))
@@ -1308,7 +1308,7 @@ def test_mixing_fast2_vs_generic_and_identical_replicas():
     env.close()
 
 
-def test_mixing_fast2_ticket_scheduler_matches_single_launch():
+def test_mixing_fast2_ticket_scheduler_matches_single_launch(tmp_path):
     """ns2d_fast2_sched (persistent workgroups drawing 10-timestep chunks, here 5 workgroups for 24
     replicas) against the plain one-workgroup-per-replica launch: obs, rewards, sweep counts and
     interior fields bit for bit (p ghost cells: one float32 rounding, see the rayleigh test above)."""
@@ -1330,7 +1330,7 @@ def test_mixing_fast2_ticket_scheduler_matches_single_launch():
     ) % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     outs = []
     for tag, kname, sched in (("single", "ns2d_fast2_step", "0,0,0,0"), ("ticket", "ns2d_fast2_sched", "2,5,0,0")):
-        path = "/tmp/bcn_mix_%s.npy" % tag
+        path = str(tmp_path / ("bcn_mix_%s.npy" % tag))
         r = subprocess.run([sys.executable, "-c", code, path, kname, sched], capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]
         outs.append(np.load(path))

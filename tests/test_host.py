@@ -418,6 +418,36 @@ def test_bench_force_dist_runs_the_collectives_with_one_rank_on_cpu_stub():
     assert d["strong"]["global_batch"] == 16 and d["strong"]["replicas_per_gpu"] == 16
 
 
+def test_bench_dump_outputs_writes_the_last_timed_step_on_cpu_stub(tmp_path):
+    """`--dump-outputs DIR`: what the caller of the timed path received from its LAST timed step (rank 0: the gathered global
+    batch) as DIR/{obs,rwd,done,trunc}.npy in float32 / float64, the same from run to run.  The stand-in env's obs are
+    2 x the first 8 action components, so the step the arrays belong to can be read off them."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    W, K = 1, 3
+    runs = {}
+    for tag, extra in (("one", ["--gpus", "1"]), ("again", ["--gpus", "1"]), ("two", ["--gpus", "2"]),
+                       ("two_blocking", ["--gpus", "2", "--no-overlap"])):
+        out = tmp_path / tag
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(K), "--warmup", str(W), "--batch", "16",
+                            "--stub", "--backend", "gloo", "--dump-outputs", str(out)] + extra,
+                           env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stdout + r.stderr
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        d = json.loads(lines[0])
+        assert d["steps"] == K and sorted(d["dumped_outputs"]["files"]) == ["done.npy", "obs.npy", "rwd.npy", "trunc.npy"]
+        a = {n: np.load(out / (n + ".npy")) for n in ("obs", "rwd", "done", "trunc")}
+        assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+        bg = d["config"]["global_batch"]
+        acts = np.random.default_rng(1234).uniform(-1.0, 1.0, (W + K, bg, 10)).astype(np.float32)
+        assert a["obs"].shape == (bg, 8) and a["rwd"].shape == a["done"].shape == a["trunc"].shape == (bg,)
+        assert np.array_equal(a["obs"], acts[W + K - 1, :, :8] * 2)
+        runs[tag] = a
+    for n in runs["one"]:
+        assert np.array_equal(runs["one"][n], runs["again"][n])
+        assert np.array_equal(runs["two"][n], runs["two_blocking"][n])
+
+
 def test_bench_launcher_stops_every_rank_when_one_dies():
     """A rank that dies before the rendezvous (BENCH_FAULT_RANK: os._exit(3) in front of init_process_group) must not
     leave its peer waiting there: the self-launching parent polls all children, terminates the survivors and exits
