@@ -25,8 +25,17 @@ extern "C" {
 
 __attribute__((visibility("default"))) int bcn_jit_launch(const void* args, int batch, void* stream) {
 #ifdef BCN_JIT_BREAK   // TEST HOOK (tests/test_gpu_parity.py): a deliberately wrong kernel -- the first-use self-check of beacon_amd/jit.py must refuse it
+  // 1: dt x 1.5 (grossly wrong); 2: dt x (1 + BCN_JIT_BREAK_EPS), subtly wrong -- below the self-check's old float32 bound (2e-4)
+  // but above its per-field bounds
+#ifndef BCN_JIT_BREAK_EPS
+#define BCN_JIT_BREAK_EPS 3e-4
+#endif
   NS2DArgs<BCN_JIT_REAL> a = *static_cast<const NS2DArgs<BCN_JIT_REAL>*>(args);
+#if BCN_JIT_BREAK == 2
+  a.dt *= BCN_JIT_REAL(1.0 + BCN_JIT_BREAK_EPS);
+#else
   a.dt *= BCN_JIT_REAL(1.5);
+#endif
 #else
   const NS2DArgs<BCN_JIT_REAL>& a = *static_cast<const NS2DArgs<BCN_JIT_REAL>*>(args);
 #endif

@@ -327,6 +327,7 @@ __device__ __forceinline__ void fast_body(const NS2DArgs<real>& A, const int w, 
   // residual leaves them out.  LIVE(k): column k of THIS wave exists (compile time for k < RL and for every other grid).
   constexpr int RL = G::RL;
   constexpr bool DEADC = GF == 2 && RW == R0 && RL != R0;
+  static_assert(!(DEADC && G::XC == 4), "dead columns exist only in the single-sweep exchange paths (XC == 2, GF == 2)");
   const bool lastw = DEADC && w == NW - 1;
 #define LIVE(k) (!DEADC || (k) < RL || !lastw)
   const int i0 = w * R0 + 1;

@@ -106,6 +106,12 @@ def choose(nx, ny, f64, kind):
             # is compared with the generic kernel before its first use (verify()).
             if f64 and r > 16:
                 continue
+            # float64 on fewer than 8 waves: refused.  The 6-wave one-body kernels with strips of 9 columns (50x64: 5 x 9 + 5
+            # live; 51x60: 5 x 9 + 6) disagree with the generic kernel and the oracle by O(1) in T, the ticket scheduler worse
+            # than the plain launch (tests/test_gpu_parity.py::test_jit_kernels_vs_oracle, its 50x64 case); the cause is not
+            # found, so these grids take the hybrid (rows 4) instead.  6-wave strips of 10 and 11 columns measured exact.
+            if f64 and nw != 8:
+                continue
             for gf in ((0,) if not f64 else ((2, 1) if rl == r else (2,))):
                 if _lds_rows1(nx, ny, nw, esz, gf, r) <= LDS_BYTES:
                     return {"rows": 1, "R": r, "gf": gf, "nw": nw}
@@ -143,10 +149,19 @@ def _seeded_rayleigh_state(env):
     return np.tile(np.ascontiguousarray(st0.transpose(0, 2, 1))[None], (env.batch, 1, 1, 1))
 
 
-def compare_with_generic(make_env, kind, f64, ndt=6, batch=3):
+SELF_CHECK_F64 = dict(u=1e-9, v=1e-9, p=5e-8, S=1e-9)
+# float32: 10 x the largest plugin-vs-generic difference over every float32 case of test_jit_kernels_vs_oracle (12 timesteps,
+# 4 replicas; m: u 4.8e-7, v 5.4e-7, p 5.8e-5, T/C 7.7e-7).  Before: 2e-4 for u, v, T/C and 1e-2 for p.
+SELF_CHECK_F32 = dict(u=4.8e-6, v=5.4e-6, p=5.8e-4, S=7.7e-6)
+
+
+def compare_with_generic(make_env, kind, f64, ndt=6, batch=3, stats=None):
     """(ok, report): `ndt` timesteps of a seeded state through the attached register-resident kernel -- plain launch and
     ticket scheduler (chunks of two timesteps on two persistent workgroups: hand-offs through HBM) -- against the generic
-    kernel.  float64: fields within 1e-9 (p 5e-8), sweep counts within 1; float32: 2e-4 (p 1e-2), counts within max(3, 2 %)."""
+    kernel.  float64: fields within 1e-9 (p 5e-8), sweep counts within 1; float32: per field,
+    SELF_CHECK_F32 (u 4.8e-6, v 5.4e-6, T/C 7.7e-6, p 5.8e-4: 10 x the largest plugin-vs-generic differences measured over every
+    float32 case of tests/test_gpu_parity.py::test_jit_kernels_vs_oracle), counts within max(3, 2 %).  `stats`: a dict, filled
+    with the per-field differences and the sweep counts of each run."""
     import numpy as np
     import torch
     runs = {}
@@ -170,19 +185,22 @@ def compare_with_generic(make_env, kind, f64, ndt=6, batch=3):
         finally:
             env.close()
     ref = runs["generic"]
-    tol = 1e-9 if f64 else 2e-4
+    tol = SELF_CHECK_F64 if f64 else SELF_CHECK_F32
     rep, ok = [], True
     for tag in ("plain", "ticket"):
         st, sw, status, kname, got = runs[tag]
         d = np.abs(st - ref[0])
         d = np.where(np.isfinite(d), d, np.inf)
-        dp, dr = float(d[:, 2].max()), float(np.delete(d, 2, axis=1).max())
+        dm = {F: float(d[:, i].max()) for i, F in enumerate("uvpS")}
         ds = int(np.abs(sw - ref[1]).max())
-        good = (got == 1 and not status.any() and not ref[2].any() and dr <= tol and dp <= 50 * tol and
+        if stats is not None:
+            stats[tag] = dict(dm, sweeps=ds, sweeps_max=int(ref[1].max()))
+        good = (got == 1 and not status.any() and not ref[2].any() and all(dm[F] <= tol[F] for F in "uvpS") and
                 ds <= (1 if f64 else max(3, int(0.02 * ref[1].max()))))
         ok = ok and good
-        rep.append("%s (%s): fields %.2e p %.2e sweeps %d of %d status %s%s" % (tag, kname, dr, dp, ds, int(ref[1].max()),
-                                                                                 np.unique(status).tolist(), "" if good else "  <-- MISMATCH"))
+        rep.append("%s (%s): u %.2e v %.2e p %.2e T/C %.2e sweeps %d of %d status %s%s"
+                   % (tag, kname, dm["u"], dm["v"], dm["p"], dm["S"], ds, int(ref[1].max()), np.unique(status).tolist(),
+                      "" if good else "  <-- MISMATCH"))
     return ok, "; ".join(rep)
 
 
@@ -195,9 +213,10 @@ def _read(path):
 
 
 def _verdict_on_disk(p, tag):
-    """True / False from the marker files beside the shared object, None where there is none for this device + runtime."""
+    """True / False from the marker files beside the shared object, None where there is none for this device + runtime.  Both
+    markers start with the runtime tag; one written on another device or HIP runtime is ignored (the plugin is checked again)."""
     bad = _read(p.path + ".bad")
-    if bad is not None:
+    if bad is not None and bad.split("\n")[0].strip() == tag:
         return False, bad.strip()[:300]
     ok = _read(p.path + ".ok")
     if ok is not None and ok.split("\n")[0].strip() == tag:
@@ -244,6 +263,12 @@ def verify(p, make_env, kind, f64):
         try:
             with open(p.path + (".ok" if ok else ".bad"), "w") as fh:
                 fh.write("%s\n%s\n" % (tag, rep))
+            try:
+                os.remove(p.path + (".bad" if ok else ".ok"))     # the other verdict, from another device or runtime
+            except FileNotFoundError:
+                pass
+            if lock is not None:
+                os.remove(p.path + ".vlock")      # the verdict is on disk: a rank still queued on the lock finds it there
         except OSError:
             pass                    # read-only package directory: the verdict holds for this process
     finally:
@@ -445,12 +470,78 @@ def fuzz_cases(seed=6):
     return out
 
 
+# grids of libbeacon_hip.so's own register-resident kernels (nx, ny, kind): no plugin is built for them
+BUILTIN_GRIDS = {(128, 64, 0), (50, 50, 0), (100, 50, 0), (150, 50, 0), (200, 50, 0), (100, 100, 1)}
+
+# the grids where choose() switches family, and the narrowest last strips, as (nx, ny, f64, kind, with other constructor
+# arguments).  The family a grid maps to is in the comment (rows per lane: 1 / 2 / 4 = hybrid; "3 live": last strip of 3 columns)
+BOUNDARY_GRIDS = [
+    # rayleigh: ny = 64 / 65, one row per lane <-> two rows (51x65: strips of 8, the last one 3 live)
+    # (50x64 float64 took the 6-wave one-row kernel, which was wrong: choose() now maps it to the hybrid; 120x64: 8 x 15)
+    (50, 64, False, 0, False), (50, 64, True, 0, True), (120, 64, True, 0, False), (51, 65, False, 0, True),
+    (51, 65, True, 0, False),
+    # ny = 128 / 129, two rows <-> hybrid (52x129 float64: hybrid, 3 live)
+    (50, 128, False, 0, False), (50, 128, True, 0, True), (50, 129, False, 0, True), (52, 129, True, 0, False),
+    # ny = 255 / 256: the hybrid with 4 rows per lane, the tallest grid admitted
+    (50, 255, False, 0, False), (50, 256, False, 0, True),
+    # the width limit of the one-row family: float32 nx 152 -> 153 at ny = 64 and 206 -> 207 at ny = 50 (153x64: hybrid, 3 live)
+    (152, 64, False, 0, True), (153, 64, False, 0, False), (206, 50, False, 0, False), (207, 50, False, 0, True),
+    # float64: nx 128 -> 129 (one row, 8 strips of 16 <-> hybrid)
+    (128, 50, True, 0, False), (129, 50, True, 0, True), (129, 64, True, 0, False),
+    # last strips of 3 live columns: one row per lane (52x50: 7 x 7 + 3) and the hybrid (213x50: 15 x 14 + 3)
+    (52, 50, False, 0, True), (213, 50, False, 0, False),
+    # mixing 100x128: hybrid in float32, two rows in float64; ny = 129 / 255 / 256 on the hybrid
+    (100, 128, False, 1, True), (100, 128, True, 1, False), (100, 129, False, 1, False), (100, 255, False, 1, True),
+    (100, 256, False, 1, False),
+    # mixing float32 hybrid, 16 strips of 8 columns, the last one 3 live
+    (123, 100, False, 1, True),
+    # mixing float64 even ny: two rows only for nx 100..104 (104x110, 104x100), the hybrid for nx 105..120 (105x100, 120x128); odd ny:
+    # two rows 102x101, hybrid 110x101 (each class at least twice with fuzz_cases())
+    (104, 110, True, 1, True), (104, 100, True, 1, False), (105, 100, True, 1, False), (120, 128, True, 1, True),
+    (102, 101, True, 1, False),
+    (110, 101, True, 1, True),
+]
+
+
+def _extent(c, n):
+    """A domain length whose grid is exactly c cells of 1 / n (int(n L) == c)."""
+    return c / n if int(n * (c / n)) == c else (c + 0.5) / n
+
+
+def oracle_cases(seed=7):
+    """fuzz_cases() followed by BOUNDARY_GRIDS, as (L, H, f64, kind, kwargs): the list tests/test_gpu_parity.py::
+    test_jit_kernels_vs_oracle runs through the plugin and the generic kernel against the float64 oracle.  The boundary grids
+    marked for it draw the reference's other constructor arguments from the ranges of fuzz_cases() (seeded)."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    out = list(fuzz_cases())
+    for nx, ny, f64, kind, args in BOUNDARY_GRIDS:
+        if (nx, ny, kind) in BUILTIN_GRIDS:
+            continue
+        n = 50.0 if kind == 0 else 100.0
+        kw = {}
+        if args and kind == 0:
+            kw = dict(n_sgts=int(rng.integers(1, 13)), ra=float(round(10.0 ** rng.uniform(np.log10(8e3), np.log10(2e5)), -2)))
+        elif args:
+            kw = dict(re=float(round(rng.uniform(50, 400), 0)), pe=float(round(10.0 ** rng.uniform(3, 5), -1)),
+                      side=round(float(rng.uniform(0.3, 0.7)), 2), C0=round(float(rng.uniform(0.5, 2.0)), 2))
+        out.append((_extent(nx, n), _extent(ny, n), f64, kind, kw))
+    return out
+
+
+def oracle_grid_keys():
+    return [_grid(L, H, kind) + (f64, kind) for L, H, f64, kind, _ in oracle_cases()]
+
+
 def fuzz_grid_keys():
     return [_grid(L, H, kind) + (f64, kind) for L, H, f64, kind, _ in fuzz_cases()]
 
 
-# plugins built with extra -D flags: the deliberately wrong kernel of the self-check's own test
-EXTRA_BUILDS = [((75, 50, True, 0), {"BCN_JIT_BREAK": 1})]
+# plugins built with extra -D flags: the deliberately wrong kernels of the self-check's own tests (dt x 1.5; float32 two rows
+# per lane with dt x (1 + eps): a subtle error, under the old float32 bound of the self-check but over the per-field one)
+BREAK2_GRID = (60, 80, False, 0)
+BREAK2_DEFS = {"BCN_JIT_BREAK": 2, "BCN_JIT_BREAK_EPS": "3e-4"}
+EXTRA_BUILDS = [((75, 50, True, 0), {"BCN_JIT_BREAK": 1}), (BREAK2_GRID, BREAK2_DEFS)]
 
 
 def _bounds_job(cell):
@@ -467,7 +558,7 @@ def prebuild(grids=None, verbose=False):
     """Compile the plugins of a list of (nx, ny, f64, kind) grids (used by __graft_entry__.build() for the grids the
     tests touch, so that they ship with the tree)."""
     from concurrent.futures import ThreadPoolExecutor
-    todo = [(g, None) for g in (grids or (TEST_GRIDS + [k for k in fuzz_grid_keys() if k not in TEST_GRIDS]))]
+    todo = [(g, None) for g in (grids or (TEST_GRIDS + [k for k in oracle_grid_keys() if k not in TEST_GRIDS]))]
     if grids is None:
         todo += EXTRA_BUILDS
     with ThreadPoolExecutor(max_workers=int(os.environ.get("BEACON_JIT_JOBS", "4"))) as ex:
@@ -477,7 +568,7 @@ def prebuild(grids=None, verbose=False):
     from . import stoprule
     cells = [(nx, ny, kind, 0.25) for (nx, ny, f64, kind), _ in todo]
     if grids is None:
-        for L, H, f64, kind, _ in fuzz_cases():
+        for L, H, f64, kind, _ in oracle_cases():
             nx, ny = _grid(L, H, kind)
             dx, dy = float(L / nx), float(H / ny)
             cells.append((nx, ny, kind, dy * dy / (2.0 * (dx * dx + dy * dy))))

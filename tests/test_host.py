@@ -579,3 +579,100 @@ def test_torch_extension_builds_loads_and_registers_every_op():
     assert len(vec._OPS) == 10
     with pytest.raises((NotImplementedError, RuntimeError)):                # CUDA key only: CPU tensors find no kernel
         ops.mixing_reset(0, torch.zeros(4))
+
+
+# the family switches of jit.choose() that jit.oracle_cases() must hold on both sides: (grid, grid), each (nx, ny, f64, kind)
+JIT_SWITCHES = [((50, 64, False, 0), (51, 65, False, 0)), ((120, 64, True, 0), (51, 65, True, 0)),       # one row <-> two rows
+                ((50, 128, False, 0), (50, 129, False, 0)), ((50, 128, True, 0), (52, 129, True, 0)),   # two rows <-> hybrid
+                ((152, 64, False, 0), (153, 64, False, 0)), ((206, 50, False, 0), (207, 50, False, 0)),  # one-row width limit
+                ((128, 50, True, 0), (129, 50, True, 0)),
+                ((104, 100, True, 1), (105, 100, True, 1)),                                           # float64 mixing
+                ((100, 128, False, 1), (100, 128, True, 1))]                                          # hybrid f32 / two rows f64
+
+
+def test_jit_oracle_cases_cover_every_kernel_class_and_family_switch():
+    """jit.oracle_cases() (the list of tests/test_gpu_parity.py::test_jit_kernels_vs_oracle): every (rows per lane, float64,
+    env, ny parity) class that jit.choose() produces over the domain sizes the kernels admit holds at least two cases, both sides
+    of every family switch are in it, the tallest grids (ny = 255 / 256) and last strips of 3 live columns too, and no case is
+    a grid libbeacon_hip.so carries itself."""
+    from beacon_amd import jit
+    classes = set()
+    for kind, nxs, nys in ((0, range(50, 321), range(50, 257)), (1, range(100, 221), range(100, 257))):
+        for f64 in (False, True):
+            for nx in nxs:
+                for ny in nys:
+                    m = jit.choose(nx, ny, f64, kind)
+                    if m is not None:
+                        classes.add((m["rows"], f64, kind, ny % 2))
+    assert len(classes) == 20, sorted(classes)
+    keys = jit.oracle_grid_keys()
+    assert len(keys) == len(set(keys)) and len(keys) == len(jit.oracle_cases())
+    have = {}
+    for nx, ny, f64, kind in keys:
+        assert (nx, ny, kind) not in jit.BUILTIN_GRIDS
+        m = jit.choose(nx, ny, f64, kind)
+        assert m is not None, (nx, ny, f64, kind)
+        have.setdefault((m["rows"], f64, kind, ny % 2), []).append((nx, ny))
+    for c in sorted(classes):
+        assert len(have.get(c, [])) >= 2, (c, have.get(c))
+    fam = lambda g: jit.choose(*g)["rows"]
+    for a, b in JIT_SWITCHES:
+        assert a in keys and b in keys, (a, b)
+        assert fam(a) != fam(b), (a, b)
+    assert (50, 255, False, 0) in keys and (50, 256, False, 0) in keys and (100, 256, False, 1) in keys
+    assert jit.choose(50, 256, False, 0)["rpl"] == 4 and jit.choose(50, 257, False, 0) is None
+    live3 = {(m["rows"], f64) for nx, ny, f64, kind in keys
+             for m in [jit.choose(nx, ny, f64, kind)] if nx - (m["nw"] - 1) * m["R"] == 3}
+    assert {(1, False), (2, False), (2, True), (4, False), (4, True)} <= live3, live3
+    # every case builds at the size it names, and about half carry other constructor arguments
+    n_args = 0
+    for L, H, f64, kind, kw in jit.oracle_cases()[len(jit.fuzz_cases()):]:
+        nx, ny = jit._grid(L, H, kind)
+        assert (nx, ny, f64, kind) in [g[:4] for g in jit.BOUNDARY_GRIDS]
+        n_args += bool(kw)
+    assert 0.4 <= n_args / len(jit.BOUNDARY_GRIDS) <= 0.6
+
+
+class _FakePlugin(object):
+    def __init__(self, path):
+        self.path, self.verified, self.report = path, None, ""
+
+
+def test_jit_verdict_markers_carry_the_runtime_tag(tmp_path, monkeypatch):
+    """jit.verify() / _verdict_on_disk(): `.ok` and `.bad` both start with the runtime tag (device + HIP runtime); a marker of
+    another tag is ignored and the plugin is checked again, the new verdict replaces the other marker, and `<plugin>.vlock`
+    is gone once the verdict is written.  (Fake marker files; the comparison itself is monkeypatched.)"""
+    import warnings
+    from beacon_amd import jit
+    monkeypatch.setattr(jit, "_runtime_tag", lambda: "gfx950 hip 7.0")
+    p = _FakePlugin(str(tmp_path / "ns2d_60x80_f32_k0_r10_0123456789ab.so"))
+    assert jit._verdict_on_disk(p, "gfx950 hip 7.0") == (None, "")
+    (tmp_path / (os.path.basename(p.path) + ".bad")).write_text("gfx942 hip 6.4\nplain: MISMATCH\n")
+    assert jit._verdict_on_disk(p, "gfx950 hip 7.0")[0] is None
+    (tmp_path / (os.path.basename(p.path) + ".ok")).write_text("gfx942 hip 6.4\nplain: fine\n")
+    assert jit._verdict_on_disk(p, "gfx950 hip 7.0")[0] is None
+    calls = []
+    monkeypatch.setattr(jit, "compare_with_generic", lambda *a, **k: (calls.append(a) or True, "plain: fine here"))
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        jit.verify(p, None, 0, False)
+    assert p.verified is True and len(calls) == 1
+    assert open(p.path + ".ok").read().split("\n")[0] == "gfx950 hip 7.0"
+    assert not os.path.exists(p.path + ".bad") and not os.path.exists(p.path + ".vlock")
+    p2 = _FakePlugin(p.path)
+    jit.verify(p2, None, 0, False)          # from the marker: no second comparison
+    assert p2.verified is True and len(calls) == 1
+    # a refusal on this runtime: `.bad` with the tag, the `.ok` of the same plugin gone, the lock file gone
+    monkeypatch.setattr(jit, "compare_with_generic", lambda *a, **k: (False, "plain: u 1e-3  <-- MISMATCH"))
+    os.remove(p.path + ".ok")
+    (tmp_path / (os.path.basename(p.path) + ".ok")).write_text("gfx942 hip 6.4\nplain: fine\n")
+    p3 = _FakePlugin(p.path)
+    with pytest.warns(jit.JitWarning, match="DISAGREES"):
+        jit.verify(p3, None, 0, False)
+    assert p3.verified is False
+    assert open(p.path + ".bad").read().split("\n")[0] == "gfx950 hip 7.0"
+    assert not os.path.exists(p.path + ".ok") and not os.path.exists(p.path + ".vlock")
+    with pytest.warns(jit.JitWarning, match="failed its self-check earlier"):
+        jit.verify(_FakePlugin(p.path), None, 0, False)
+    # the same markers seen from another runtime: neither counts
+    assert jit._verdict_on_disk(p, "gfx950 hip 7.1")[0] is None
