@@ -57,6 +57,20 @@ class SloshingCfg(C.Structure):
                 ("alpha", C.c_double)]
 
 
+class LorenzCfg(C.Structure):
+    _fields_ = [("ndt_act", C.c_int32), ("n_act", C.c_int32),
+                ("dt", C.c_double), ("sigma", C.c_double), ("rho", C.c_double), ("beta", C.c_double)]
+
+
+class VortexCfg(C.Structure):
+    _fields_ = [("ndt_act", C.c_int32), ("n_act", C.c_int32), ("dt", C.c_double),
+                ("lmbda_re", C.c_double), ("lmbda_cx", C.c_double), ("mu_re", C.c_double), ("mu_cx", C.c_double),
+                ("alpha_re", C.c_double), ("alpha_cx", C.c_double), ("beta", C.c_double), ("re", C.c_double),
+                ("re_crit", C.c_double), ("omega_s", C.c_double), ("omega_f", C.c_double), ("gamma", C.c_double),
+                ("mass", C.c_double), ("weight", C.c_double), ("mod_min", C.c_double), ("mod_max", C.c_double),
+                ("phase_min", C.c_double), ("phase_max", C.c_double)]
+
+
 # every symbol include/beacon_hip.h declares: (restype, argtypes)
 SIGNATURES = {
     "bcn_rayleigh_create": (C.c_int, [C.POINTER(RayleighCfg), C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
@@ -74,6 +88,12 @@ SIGNATURES = {
     "bcn_sloshing_create": (C.c_int, [C.POINTER(SloshingCfg), C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
     "bcn_sloshing_reset": (C.c_int, [vp, vp, vp, vp]),
     "bcn_sloshing_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    "bcn_lorenz_create": (C.c_int, [C.POINTER(LorenzCfg), C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
+    "bcn_lorenz_reset": (C.c_int, [vp, vp, vp]),
+    "bcn_lorenz_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    "bcn_vortex_create": (C.c_int, [C.POINTER(VortexCfg), C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
+    "bcn_vortex_reset": (C.c_int, [vp, vp, vp]),
+    "bcn_vortex_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
     "bcn_env_kind": (C.c_int, [vp]),
     "bcn_batch": (C.c_int, [vp]),
     "bcn_dtype": (C.c_int, [vp]),

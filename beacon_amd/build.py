@@ -40,7 +40,9 @@ FILE_FLAGS = {"ns2d_fast.hip": ["-fno-slp-vectorize", "-ffp-contract=on", "-O2"]
               "ns2d_fast2.hip": ["-fno-slp-vectorize", "-ffp-contract=on", "-mllvm", "-amdgpu-disable-unclustered-high-rp-reschedule",
                                  "-mllvm", "-amdgpu-sdwa-peephole=0"],
               # float64 1D kernels: the reference's operation order without FMA contraction -> bit-identical fields
-              "env1d_f64.hip": ["-ffp-contract=off"]}
+              "env1d_f64.hip": ["-ffp-contract=off"],
+              # float64 ODE envs (lorenz, vortex): the host ports' operation order without FMA contraction -> bit-identical episodes
+              "ode_f64.hip": ["-ffp-contract=off"]}
 
 
 # the on-demand kernels (beacon_amd/jit.py: csrc/jit/ns2d_jit.hip, any family, any precision): the flags their verification and

@@ -9,6 +9,7 @@
 
 #include "env1d.h"
 #include "ns2d.h"
+#include "ode_env.h"
 
 thread_local const char* bcn_env1d_launched = nullptr;   // env1d.h: set by the 1D launchers
 
@@ -412,6 +413,125 @@ int make_sloshing(const bcn_sloshing_cfg* c, int batch, int dtype, int device, b
   return BCN_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// lorenz / vortex: one lane per replica (ode_env.h)
+// ------------------------------------------------------------------------------------------
+template <typename real>
+struct OdeEnv : bcn_env_s {
+  OdeArgs<real> a{};
+  DevBuf st, iubuf, stpbuf, stage;   // stage: [B][n_state] rows of a host-side state copy
+  int nreal = 0, nstate = 0;
+
+  int init() {
+    int rc;
+    if ((rc = st.alloc((size_t)batch * nreal * sizeof(real)))) return rc;
+    BCN_HIP(hipMemset(st.p, 0, st.bytes));
+    a.st = static_cast<real*>(st.p);
+    if ((rc = iubuf.alloc((size_t)batch * sizeof(int32_t)))) return rc;
+    BCN_HIP(hipMemset(iubuf.p, 0, iubuf.bytes));
+    a.iu = static_cast<int32_t*>(iubuf.p);
+    if ((rc = stpbuf.alloc((size_t)batch * sizeof(int32_t)))) return rc;
+    BCN_HIP(hipMemset(stpbuf.p, 0, stpbuf.bytes));
+    stp = a.stp = static_cast<int32_t*>(stpbuf.p);
+    a.batch = batch; a.n_obs = n_obs;
+    // observation rows through LDS for float64 (48 / 64 B rows), direct per-lane stores for float32: measured A/B/A/B at B = 2^20
+    // (DESIGN.md §10): lorenz float64 30.8 / 34.5 us per step staged / direct, float32 19.8 / 19.0; vortex float32 42.4 / 40.9,
+    // float64 81.1 / 81.7
+    a.obs_stage = sizeof(real) == 8 ? 1 : 0;
+    return BCN_OK;
+  }
+  ~OdeEnv() override {
+    DeviceGuard g(device);
+    st.release(); iubuf.release(); stpbuf.release(); stage.release();
+  }
+  size_t state_elems() const override { return (size_t)nstate; }
+  // caller layout [B][nstate]; device layout [field][B] (+ lorenz's int32 action index): one pack / unpack kernel, host copies
+  // through a staging buffer
+  int copy_state(void* buf, int is_device, hipStream_t s, bool out) {
+    real* ext = static_cast<real*>(buf);
+    const size_t bytes = (size_t)batch * nstate * sizeof(real);
+    if (!is_device) {
+      if (!stage.p) { int rc = stage.alloc(bytes); if (rc) return rc; }
+      ext = static_cast<real*>(stage.p);
+      if (!out) BCN_HIP(hipMemcpyAsync(ext, buf, bytes, hipMemcpyHostToDevice, s));
+    }
+    const int rc = out ? ode_launch_pack<real>(a, ext, s) : ode_launch_unpack<real>(a, ext, s);
+    if (rc) return rc;
+    if (!is_device) {
+      if (out) BCN_HIP(hipMemcpyAsync(buf, ext, bytes, hipMemcpyDeviceToHost, s));
+      BCN_HIP(hipStreamSynchronize(s));
+    }
+    return BCN_OK;
+  }
+  int get_state(void* buf, int is_device, hipStream_t s) override { return copy_state(buf, is_device, s, true); }
+  int set_state(const void* buf, int is_device, hipStream_t s) override { return copy_state(const_cast<void*>(buf), is_device, s, false); }
+  int set_variant(int) override { bcn_set_error("lorenz / vortex have one kernel and no variants"); return BCN_ERR_ARG; }
+  int set_sched(int, int, int, int) override { bcn_set_error("lorenz / vortex step one replica per lane: nothing to schedule"); return BCN_ERR_ARG; }
+  int set_option(const char* name, int value) override {
+    if (!strcmp(name, "obs_stage") && (value == 0 || value == 1)) { a.obs_stage = value; return BCN_OK; }
+    return bcn_env_s::set_option(name, value);
+  }
+  void set_mask(const uint8_t* m) override { a.mask = m; }
+  const char* kernel_name() const override { return kind == BCN_LORENZ ? "lorenz_step_k" : "vortex_step_k"; }
+};
+
+template <typename real>
+int make_lorenz(const bcn_lorenz_cfg* c, int batch, int dtype, int device, bcn_env_t* out) {
+  auto* e = new (std::nothrow) OdeEnv<real>();
+  if (!e) { bcn_set_error("out of host memory"); return BCN_ERR_ARG; }
+  e->kind = BCN_LORENZ; e->batch = batch; e->dtype = dtype; e->device = device; e->esz = sizeof(real);
+  e->nreal = LZ_NREAL; e->nstate = LZ_NSTATE;
+  OdeArgs<real>& a = e->a;
+  a.kind = BCN_LORENZ; a.ndt_act = c->ndt_act; a.n_act = c->n_act;
+  a.dt = (real)c->dt; a.sigma = (real)c->sigma; a.rho = (real)c->rho; a.beta = (real)c->beta;
+  e->n_obs = 6; e->n_act = 1; e->ndt_act = c->ndt_act;
+  int rc = e->init();
+  if (rc) { delete e; return rc; }
+  *out = e;
+  return BCN_OK;
+}
+
+template <typename real>
+int make_vortex(const bcn_vortex_cfg* c, int batch, int dtype, int device, bcn_env_t* out) {
+  auto* e = new (std::nothrow) OdeEnv<real>();
+  if (!e) { bcn_set_error("out of host memory"); return BCN_ERR_ARG; }
+  e->kind = BCN_VORTEX; e->batch = batch; e->dtype = dtype; e->device = device; e->esz = sizeof(real);
+  e->nreal = VX_NREAL; e->nstate = VX_NSTATE;
+  OdeArgs<real>& a = e->a;
+  a.kind = BCN_VORTEX; a.ndt_act = c->ndt_act; a.n_act = c->n_act;
+  a.dt = (real)c->dt;
+  a.lmbda_re = (real)c->lmbda_re; a.lmbda_cx = (real)c->lmbda_cx; a.mu_re = (real)c->mu_re; a.mu_cx = (real)c->mu_cx;
+  a.alpha_re = (real)c->alpha_re; a.alpha_cx = (real)c->alpha_cx;
+  // the derived constants of vortex.py:26-42, in double and in the reference's order
+  a.ire = (real)(1.0 / c->re_crit - 1.0 / c->re);
+  a.omega_f = (real)c->omega_f;
+  a.m_omega_f_gamma = (real)(-c->omega_f * c->gamma);
+  a.domega = (real)(c->omega_s - c->omega_f);
+  a.beta_m = (real)(c->beta / (c->omega_f * c->mass));
+  a.mod_min = (real)c->mod_min; a.dmod = (real)(c->mod_max - c->mod_min);
+  a.phase_min = (real)c->phase_min; a.dphase = (real)(c->phase_max - c->phase_min);
+  a.rwd_k = (real)(2.0 * c->omega_s * c->gamma);
+  a.weight = (real)c->weight;
+  e->n_obs = 8; e->n_act = 2; e->ndt_act = c->ndt_act;
+  int rc = e->init();
+  if (rc) { delete e; return rc; }
+  *out = e;
+  return BCN_OK;
+}
+
+template <typename real>
+static int ode_call(bcn_env_t h, bool reset, const void* actions, void* obs, void* rwd, uint8_t* done, uint8_t* trunc,
+                    int32_t* status, void* stream) {
+  auto* e = static_cast<OdeEnv<real>*>(h);
+  DeviceGuard g(e->device);
+  OdeArgs<real> a = e->a;
+  a.actions = actions;
+  a.obs_out = static_cast<real*>(obs);
+  a.rwd_out = static_cast<real*>(rwd);
+  a.done = done; a.trunc = trunc; a.status = status;
+  return reset ? ode_launch_reset<real>(a, static_cast<hipStream_t>(stream)) : ode_launch_step<real>(a, static_cast<hipStream_t>(stream));
+}
+
 int check_create(const void* cfg, int batch, int dtype, int device, bcn_env_t* out) {
   if (!cfg || !out) { bcn_set_error("null cfg/out"); return BCN_ERR_ARG; }
   if (batch <= 0) { bcn_set_error("batch must be > 0"); return BCN_ERR_ARG; }
@@ -608,6 +728,47 @@ int bcn_sloshing_step(bcn_env_t h, const void* actions_dev, void* obs_dev, void*
                      status_dev);
   h->note_kernel(bcn_env1d_launched ? bcn_env1d_launched : "sloshing_step_k");
   return rc_;
+}
+
+// ---- lorenz / vortex --------------------------------------------------------------------------
+#define BCN_ODE_CALL(h, ...) \
+  (h->dtype == BCN_F32 ? ode_call<float>(h, __VA_ARGS__) : ode_call<double>(h, __VA_ARGS__))
+
+int bcn_lorenz_create(const bcn_lorenz_cfg* c, int batch, int dtype, int device, bcn_env_t* out) {
+  int rc = check_create(c, batch, dtype, device, out);
+  if (rc) return rc;
+  if (c->ndt_act < 1 || c->n_act < 1 || !(c->dt > 0)) { bcn_set_error("lorenz cfg out of range (ndt_act, n_act >= 1, dt > 0)"); return BCN_ERR_ARG; }
+  DeviceGuard g(device);
+  return dtype == BCN_F32 ? make_lorenz<float>(c, batch, dtype, device, out) : make_lorenz<double>(c, batch, dtype, device, out);
+}
+int bcn_lorenz_reset(bcn_env_t h, void* obs_dev, void* stream) {
+  BCN_CHECK_KIND(h, BCN_LORENZ);
+  return BCN_ODE_CALL(h, true, nullptr, obs_dev, nullptr, nullptr, nullptr, nullptr, stream);
+}
+int bcn_lorenz_step(bcn_env_t h, const int32_t* actions_dev, void* obs_dev, void* rwd_dev, uint8_t* done_dev, uint8_t* trunc_dev,
+                    int32_t* status_dev, void* stream) {
+  BCN_CHECK_KIND(h, BCN_LORENZ);
+  return BCN_ODE_CALL(h, false, actions_dev, obs_dev, rwd_dev, done_dev, trunc_dev, status_dev, stream);
+}
+
+int bcn_vortex_create(const bcn_vortex_cfg* c, int batch, int dtype, int device, bcn_env_t* out) {
+  int rc = check_create(c, batch, dtype, device, out);
+  if (rc) return rc;
+  if (c->ndt_act < 1 || c->n_act < 1 || !(c->dt > 0) || !(c->omega_f != 0) || !(c->mass != 0) || !(c->re != 0) || !(c->re_crit != 0)) {
+    bcn_set_error("vortex cfg out of range (ndt_act, n_act >= 1, dt > 0, omega_f, mass, re, re_crit nonzero)");
+    return BCN_ERR_ARG;
+  }
+  DeviceGuard g(device);
+  return dtype == BCN_F32 ? make_vortex<float>(c, batch, dtype, device, out) : make_vortex<double>(c, batch, dtype, device, out);
+}
+int bcn_vortex_reset(bcn_env_t h, void* obs_dev, void* stream) {
+  BCN_CHECK_KIND(h, BCN_VORTEX);
+  return BCN_ODE_CALL(h, true, nullptr, obs_dev, nullptr, nullptr, nullptr, nullptr, stream);
+}
+int bcn_vortex_step(bcn_env_t h, const void* actions_dev, void* obs_dev, void* rwd_dev, uint8_t* done_dev, uint8_t* trunc_dev,
+                    int32_t* status_dev, void* stream) {
+  BCN_CHECK_KIND(h, BCN_VORTEX);
+  return BCN_ODE_CALL(h, false, actions_dev, obs_dev, rwd_dev, done_dev, trunc_dev, status_dev, stream);
 }
 
 // ---- common ----------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 // beacon_torch.cpp -- the thin PyTorch-ROCm extension over the C ABI (include/beacon_hip.h): torch.library ops
-//   beacon::{rayleigh,mixing,burgers,shkadov,sloshing}_{step,reset}(int handle, Tensor ...) -> ()
+//   beacon::{rayleigh,mixing,burgers,shkadov,sloshing,lorenz,vortex}_{step,reset}(int handle, Tensor ...) -> ()
 // Each op is ONE dispatcher call that takes device tensors, reads torch's current HIP stream in C++ and forwards to the
 // bcn_* entry point of libbeacon_hip.so -- no ctypes marshalling, no Python-side stream query (what the per-call host cost of
 // the ctypes binding was made of: scripts/host_cost.py), and an op CUDA-graph capture and fake-tensor tracing can see (Meta kernels below).  The ops
@@ -150,13 +150,44 @@ void sloshing_step(int64_t h_, OptT actions, const Tensor& obs, const Tensor& rw
         "bcn_sloshing_step");
 }
 
+// ---- lorenz (lorenz.py:60-117), vortex (vortex.py:82-146) --------------------------------------------------------------
+void lorenz_reset(int64_t h_, const Tensor& obs) {
+  bcn_env_t h = H(h_);
+  rows(obs, h, bcn_n_obs(h), "obs");
+  check(bcn_lorenz_reset(h, dp(obs, h, true, "obs"), stream_of(obs)), "bcn_lorenz_reset");
+}
+void lorenz_step(int64_t h_, OptT actions, const Tensor& obs, const Tensor& rwd, const Tensor& done, const Tensor& trunc,
+                 const Tensor& status) {
+  bcn_env_t h = H(h_);
+  rows(obs, h, bcn_n_obs(h), "obs");
+  rows(rwd, h, 1, "rwd");
+  const int32_t* a = actions.has_value() ? i32(*actions, h, 1, "actions") : nullptr;
+  check(bcn_lorenz_step(h, a, dp(obs, h, true, "obs"), dp(rwd, h, true, "rwd"), u8(done, h, 1, "done"), u8(trunc, h, 1, "trunc"),
+                        i32(status, h, 1, "status"), stream_of(obs)),
+        "bcn_lorenz_step");
+}
+void vortex_reset(int64_t h_, const Tensor& obs) {
+  bcn_env_t h = H(h_);
+  rows(obs, h, bcn_n_obs(h), "obs");
+  check(bcn_vortex_reset(h, dp(obs, h, true, "obs"), stream_of(obs)), "bcn_vortex_reset");
+}
+void vortex_step(int64_t h_, OptT actions, const Tensor& obs, const Tensor& rwd, const Tensor& done, const Tensor& trunc,
+                 const Tensor& status) {
+  bcn_env_t h = H(h_);
+  rows(obs, h, bcn_n_obs(h), "obs");
+  rows(rwd, h, 1, "rwd");
+  check(bcn_vortex_step(h, dpr(actions, h, bcn_n_act(h), "actions"), dp(obs, h, true, "obs"), dp(rwd, h, true, "rwd"),
+                        u8(done, h, 1, "done"), u8(trunc, h, 1, "trunc"), i32(status, h, 1, "status"), stream_of(obs)),
+        "bcn_vortex_step");
+}
+
 // Meta (fake-tensor) kernels: the ops return nothing and their outputs keep their shapes, so tracing needs no more than this.
 void reset2_meta(int64_t, const Tensor&) {}
 void reset3_meta(int64_t, OptT, const Tensor&) {}
 void rayleigh_step_meta(int64_t, OptT, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&) {}
 void mixing_step_meta(int64_t, OptT, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&) {}
 void noisy_step_meta(int64_t, OptT, OptT, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&) {}
-void sloshing_step_meta(int64_t, OptT, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&) {}
+void sloshing_step_meta(int64_t, OptT, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&) {}   // also lorenz, vortex
 
 }  // namespace
 
@@ -178,6 +209,12 @@ TORCH_LIBRARY(beacon, m) {
   m.def("sloshing_reset(int handle, Tensor? init_fields, Tensor(a!) obs) -> ()");
   m.def("sloshing_step(int handle, Tensor? actions, Tensor(a!) obs, Tensor(b!) rwd, Tensor(c!) done, Tensor(d!) trunc, "
         "Tensor(e!) status) -> ()");
+  m.def("lorenz_reset(int handle, Tensor(a!) obs) -> ()");
+  m.def("lorenz_step(int handle, Tensor? actions, Tensor(a!) obs, Tensor(b!) rwd, Tensor(c!) done, Tensor(d!) trunc, "
+        "Tensor(e!) status) -> ()");
+  m.def("vortex_reset(int handle, Tensor(a!) obs) -> ()");
+  m.def("vortex_step(int handle, Tensor? actions, Tensor(a!) obs, Tensor(b!) rwd, Tensor(c!) done, Tensor(d!) trunc, "
+        "Tensor(e!) status) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(beacon, CUDA, m) {
@@ -191,6 +228,10 @@ TORCH_LIBRARY_IMPL(beacon, CUDA, m) {
   m.impl("shkadov_step", &shkadov_step);
   m.impl("sloshing_reset", &sloshing_reset);
   m.impl("sloshing_step", &sloshing_step);
+  m.impl("lorenz_reset", &lorenz_reset);
+  m.impl("lorenz_step", &lorenz_step);
+  m.impl("vortex_reset", &vortex_reset);
+  m.impl("vortex_step", &vortex_step);
 }
 
 TORCH_LIBRARY_IMPL(beacon, Meta, m) {
@@ -204,4 +245,8 @@ TORCH_LIBRARY_IMPL(beacon, Meta, m) {
   m.impl("shkadov_step", &noisy_step_meta);
   m.impl("sloshing_reset", &reset3_meta);
   m.impl("sloshing_step", &sloshing_step_meta);
+  m.impl("lorenz_reset", &reset2_meta);
+  m.impl("lorenz_step", &sloshing_step_meta);
+  m.impl("vortex_reset", &reset2_meta);
+  m.impl("vortex_step", &sloshing_step_meta);
 }

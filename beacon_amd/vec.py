@@ -52,13 +52,14 @@ def _ptr(t):
 
 _OPS = ("rayleigh_reset", "rayleigh_step", "mixing_reset", "mixing_step", "burgers_reset", "burgers_step", "shkadov_reset",
         "shkadov_step", "sloshing_reset", "sloshing_step")
+_ODE_OPS = ("lorenz_reset", "lorenz_step", "vortex_reset", "vortex_step")     # the ODE envs (csrc/ode_env.h)
 
 
 def _op_table():
     """{name: torch.ops.beacon.<name>.default} of the torch extension (beacon_amd/torch_ext.py), or None without it."""
     from . import torch_ext
     ops = torch_ext.load()
-    return None if ops is None else {n: getattr(ops, n).default for n in _OPS}
+    return None if ops is None else {n: getattr(ops, n).default for n in _OPS + _ODE_OPS}
 
 
 class VecEnv(object):
@@ -801,3 +802,110 @@ class VecSloshing(VecEnv):
             return self._ops["sloshing_step"](self.h.value, a, self.obs, self.rwd, self.done, self.trunc, self.status)
         _lib.check(self.lib.bcn_sloshing_step(self.h, _ptr(a), _ptr(self.obs), _ptr(self.rwd), _ptr(self.done),
                                               _ptr(self.trunc), _ptr(self.status), self._stream()))
+
+
+class VecLorenz(VecEnv):
+    """lorenz/lorenz.py:18-264 (the host port: beacon_amd/lorenz.py).  One lane per replica (csrc/ode_env.h); Discrete(3)
+    actions as int32 [B] (force -1, 0, 1), obs = (x, f(x) of the last RK stage), reward 1 while x0 < 0.
+    State rows (get_state / set_state): [B, 8] = x0, x1, x2, fx0, fx1, fx2, t, u."""
+
+    action_is_int = True
+
+    def __init__(self, batch, device="cuda:0", dtype="f32", sigma=10.0, rho=28.0, beta=8.0 / 3.0):
+        self._derive(sigma, rho, beta)
+        super().__init__(batch, device, dtype)
+        self._make_spaces()
+
+    def _derive(self, sigma=10.0, rho=28.0, beta=8.0 / 3.0):
+        self.sigma, self.rho, self.beta = sigma, rho, beta
+        self.dt, self.dt_act, self.t_max = 0.05, 0.05, 25.0               # lorenz.py:26-36
+        self.n_obs = 6
+        self.ndt_act = int(self.dt_act / self.dt)
+        self.n_act = int(self.t_max / self.dt_act)
+        return self
+
+    def _make_spaces(self):
+        self.action_space = spaces.discrete(3)                                  # lorenz.py:49
+        self.observation_space = spaces.sym_box(1.0, self.n_obs)               # :51-55
+        return self
+
+    def _create(self):
+        c = _lib.LorenzCfg(ndt_act=self.ndt_act, n_act=self.n_act, dt=self.dt, sigma=self.sigma, rho=self.rho, beta=self.beta)
+        self.cfg = c
+        _lib.check(self.lib.bcn_lorenz_create(C.byref(c), self.batch, self.cdtype, self.dev_index, C.byref(self.h)))
+
+    def state_shape(self):
+        return (8,)
+
+    def _reset(self):
+        if self._ops is not None:
+            return self._ops["lorenz_reset"](self.h.value, self.obs)
+        _lib.check(self.lib.bcn_lorenz_reset(self.h, _ptr(self.obs), self._stream()))
+
+    def _step(self, actions, noise=None):
+        a = None
+        if actions is not None:
+            if not torch.is_tensor(actions):
+                actions = torch.as_tensor(np.asarray(actions, dtype=np.int64))
+            a = actions.to(device=self.device, dtype=torch.int32).reshape(self.batch).contiguous()
+        self._keep = a
+        if self._ops is not None:
+            return self._ops["lorenz_step"](self.h.value, a, self.obs, self.rwd, self.done, self.trunc, self.status)
+        _lib.check(self.lib.bcn_lorenz_step(self.h, _ptr(a), _ptr(self.obs), _ptr(self.rwd), _ptr(self.done),
+                                            _ptr(self.trunc), _ptr(self.status), self._stream()))
+
+
+class VecVortex(VecEnv):
+    """vortex/vortex.py:17-283 (the host port: beacon_amd/vortex.py).  One lane per replica (csrc/ode_env.h); Box(-1, 1, (2,))
+    actions [B, 2] = (modulus, phase) of the feedback.  State rows (get_state / set_state): [B, 14] = ar, ai, yr, yi,
+    fx0..fx3, t, y, kmod, kphase, u0, u1."""
+
+    def __init__(self, batch, device="cuda:0", dtype="f32", re=50.0, weight=50.0):
+        self._derive(re, weight)
+        super().__init__(batch, device, dtype)
+        self._make_spaces()
+
+    def _derive(self, re=50.0, weight=50.0):
+        self.lmbda_re, self.lmbda_cx = 9.153, 3.239                       # vortex.py:26-48
+        self.mu_re, self.mu_cx = 308.9, -1025.0
+        self.alpha_re, self.alpha_cx = 0.03492, 0.01472
+        self.beta, self.re, self.re_crit = 1.0, re, 46.6
+        self.omega_s, self.omega_f = 1.1, 0.74
+        self.gamma, self.mass, self.weight = 0.023, 10.0, weight
+        self.dt, self.dt_act, self.t_max = 0.1, 0.5, 400.0
+        self.n_obs = 8
+        self.ndt_act = int(self.dt_act / self.dt)
+        self.n_act = int(self.t_max / self.dt_act)
+        self.mod_min, self.mod_max = 0.0, 0.3
+        self.phase_min, self.phase_max = -math.pi, math.pi
+        return self
+
+    def _make_spaces(self):
+        self.action_space = spaces.box(-1.0, 1.0, (2,))                         # vortex.py:69-72
+        self.observation_space = spaces.sym_box(1.0e-4, self.n_obs)             # :74-79
+        return self
+
+    def _create(self):
+        c = _lib.VortexCfg(ndt_act=self.ndt_act, n_act=self.n_act, dt=self.dt, lmbda_re=self.lmbda_re, lmbda_cx=self.lmbda_cx,
+                           mu_re=self.mu_re, mu_cx=self.mu_cx, alpha_re=self.alpha_re, alpha_cx=self.alpha_cx, beta=self.beta,
+                           re=self.re, re_crit=self.re_crit, omega_s=self.omega_s, omega_f=self.omega_f, gamma=self.gamma,
+                           mass=self.mass, weight=self.weight, mod_min=self.mod_min, mod_max=self.mod_max,
+                           phase_min=self.phase_min, phase_max=self.phase_max)
+        self.cfg = c
+        _lib.check(self.lib.bcn_vortex_create(C.byref(c), self.batch, self.cdtype, self.dev_index, C.byref(self.h)))
+
+    def state_shape(self):
+        return (14,)
+
+    def _reset(self):
+        if self._ops is not None:
+            return self._ops["vortex_reset"](self.h.value, self.obs)
+        _lib.check(self.lib.bcn_vortex_reset(self.h, _ptr(self.obs), self._stream()))
+
+    def _step(self, actions, noise=None):
+        a = self._real(actions, (self.batch, 2))
+        self._keep = a
+        if self._ops is not None:
+            return self._ops["vortex_step"](self.h.value, a, self.obs, self.rwd, self.done, self.trunc, self.status)
+        _lib.check(self.lib.bcn_vortex_step(self.h, _ptr(a), _ptr(self.obs), _ptr(self.rwd), _ptr(self.done),
+                                            _ptr(self.trunc), _ptr(self.status), self._stream()))

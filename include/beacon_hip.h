@@ -56,7 +56,7 @@ enum { BCN_OK = 0, BCN_ERR_ARG = 1, BCN_ERR_HIP = 2, BCN_ERR_UNSUPPORTED = 3 };
 enum { BCN_ST_OK = 0, BCN_ST_ITMAX = 1, BCN_ST_BLOWUP = 2,
        BCN_ST_PLAN = 4 /* diagnostic (bcn_set_option "verify_conv"): a Jacobi sweep the residual-evaluation plan skips passed the test */ };
 /* env kinds (bcn_env_kind) */
-enum { BCN_RAYLEIGH = 0, BCN_MIXING = 1, BCN_BURGERS = 2, BCN_SHKADOV = 3, BCN_SLOSHING = 4 };
+enum { BCN_RAYLEIGH = 0, BCN_MIXING = 1, BCN_BURGERS = 2, BCN_SHKADOV = 3, BCN_SLOSHING = 4, BCN_LORENZ = 5, BCN_VORTEX = 6 };
 
 /* ---- rayleigh: rayleigh/rayleigh.py -------------------------------------------------- */
 /* ctor kwargs + the derived quantities of rayleigh.__init__ (rayleigh.py:20-56) */
@@ -164,6 +164,48 @@ BCN_API int bcn_sloshing_reset(bcn_env_t h, const void* init_fields_dev, void* o
 BCN_API int bcn_sloshing_step(bcn_env_t h, const void* actions_dev, void* obs_dev, void* rwd_dev,
                       uint8_t* done_dev, uint8_t* trunc_dev, int32_t* status_dev, void* stream);
 
+/* ---- lorenz: lorenz/lorenz.py ------------------------------------------------------- */
+/* The two ODE envs run one lane per replica with the whole state in registers (beacon_amd/csrc/ode_env.h).  Precision: BCN_F64
+ * follows the reference's episodes bit for bit (lorenz) / to the last bits of the device cos / sin (vortex); BCN_F32 one action
+ * step from the same state: tests/test_gpu_ode.py. */
+typedef struct {
+  int32_t ndt_act, n_act;         /* int(dt_act / dt) = 1, int(t_max / dt_act) = 500 */
+  double dt;                      /* 0.05 */
+  double sigma, rho, beta;        /* 10, 28, 8/3 (lorenz.py:22-25) */
+} bcn_lorenz_cfg;
+
+/* replaces lorenz.__init__ (lorenz.py:22-57) */
+BCN_API int bcn_lorenz_create(const bcn_lorenz_cfg* cfg, int batch, int dtype, int device, bcn_env_t* out);
+/* replaces lorenz.reset / reset_fields (lorenz.py:60-95): x = 10, fx = 0, t = 0, u = 1 (no force).  obs_dev[B][6] may be NULL. */
+BCN_API int bcn_lorenz_reset(bcn_env_t h, void* obs_dev, void* stream);
+/* replaces lorenz.step (lorenz.py:98-117) incl. solve/get_obs/get_rwd (:120-172).  actions_dev int32[B] in {0,1,2}
+ * (force -1, 0, 1; anything else = no force), NULL = repeat last.  obs_dev[B][6] = (x, f(x) of the last RK stage). */
+BCN_API int bcn_lorenz_step(bcn_env_t h, const int32_t* actions_dev, void* obs_dev, void* rwd_dev, uint8_t* done_dev,
+                    uint8_t* trunc_dev, int32_t* status_dev, void* stream);
+
+/* ---- vortex: vortex/vortex.py ------------------------------------------------------- */
+typedef struct {
+  int32_t ndt_act, n_act;         /* int(dt_act / dt) = 5, int(t_max / dt_act) = 800 */
+  double dt;                      /* 0.1 */
+  double lmbda_re, lmbda_cx;      /* 9.153, 3.239 (vortex.py:26-48) */
+  double mu_re, mu_cx;            /* 308.9, -1025 */
+  double alpha_re, alpha_cx;      /* 0.03492, 0.01472 */
+  double beta, re, re_crit;       /* 1, 50, 46.6 */
+  double omega_s, omega_f;        /* 1.1, 0.74 */
+  double gamma, mass, weight;     /* 0.023, 10, 50 */
+  double mod_min, mod_max;        /* 0, 0.3 */
+  double phase_min, phase_max;    /* -pi, pi */
+} bcn_vortex_cfg;
+
+/* replaces vortex.__init__ (vortex.py:21-79) */
+BCN_API int bcn_vortex_create(const bcn_vortex_cfg* cfg, int batch, int dtype, int device, bcn_env_t* out);
+/* replaces vortex.reset / reset_fields (vortex.py:82-125): the fixed start point, u = (0, 0), kmod = kphase = 0.  obs_dev[B][8] or NULL. */
+BCN_API int bcn_vortex_reset(bcn_env_t h, void* obs_dev, void* stream);
+/* replaces vortex.step (vortex.py:127-146) incl. solve/get_obs/get_rwd (:149-208).  actions_dev[B][2] = (modulus, phase) in
+ * [-1, 1], NULL = repeat last.  obs_dev[B][8] = (x, f(x) of the last RK stage). */
+BCN_API int bcn_vortex_step(bcn_env_t h, const void* actions_dev, void* obs_dev, void* rwd_dev, uint8_t* done_dev,
+                    uint8_t* trunc_dev, int32_t* status_dev, void* stream);
+
 /* ---- common -------------------------------------------------------------------------- */
 BCN_API int bcn_env_kind(bcn_env_t h);
 BCN_API int bcn_batch(bcn_env_t h);
@@ -175,8 +217,10 @@ BCN_API int bcn_device(bcn_env_t h);      /* HIP device index the handle was cre
 /* Solver state of all replicas, the equivalent of the env's field attributes (and of
  * dump()/load(), rayleigh.py:344-362): elements per replica, then copy out / in.  Layout per
  * replica: rayleigh/mixing [4][ny+2][nx+2] = u,v,p,S; burgers [3][nx] = u,up,upp;
- * shkadov [4][nx] = h,q,rhsh,rhsq; sloshing [4][nx+2] = h,q,rhsh,rhsq.  `buf` may be a host or a
- * device pointer (is_device); host copies synchronise the stream. */
+ * shkadov [4][nx] = h,q,rhsh,rhsq; sloshing [4][nx+2] = h,q,rhsh,rhsq;
+ * lorenz [8] = x0,x1,x2, fx0,fx1,fx2, t, u (the action index, as a value of the handle's dtype);
+ * vortex [14] = ar,ai,yr,yi, fx0..fx3, t, y, kmod, kphase, u0,u1 (t accumulated as t += dt, y of the last get_rwd).
+ * `buf` may be a host or a device pointer (is_device); host copies synchronise the stream. */
 BCN_API size_t bcn_state_elems(bcn_env_t h);
 BCN_API int bcn_get_state(bcn_env_t h, void* buf, int is_device, void* stream);
 BCN_API int bcn_set_state(bcn_env_t h, const void* buf, int is_device, void* stream);
@@ -196,7 +240,8 @@ BCN_API int bcn_set_stp(bcn_env_t h, const int32_t* buf_host, void* stream);
  * bcn_set_fast_plugin (beacon_amd/jit.py compiles it on demand): one row per lane for rayleigh with ny <= 64, two rows per
  * lane for 64 < ny <= 128, and for everything else up to ny = 256 (tall grids, grids wider than the strips, mixing below
  * ny = 64) the hybrid of ns2d_fast4_impl.h (Poisson solve in registers, fields in HBM/L2).  Beyond that: variant 0 only.
- * Results of the two variants agree to rounding (float64: 1e-9).  Returns the variant actually selected. */
+ * Results of the two variants agree to rounding (float64: 1e-9).  Returns the variant actually selected; lorenz and vortex have
+ * one kernel and no variants: BCN_ERR_ARG (as for bcn_set_noise, bcn_set_fast_plugin, bcn_set_sched, bcn_set_slow_mode_bound). */
 BCN_API int bcn_set_variant(bcn_env_t h, int variant);
 /* Measurement aid (no reference counterpart), uint64[B][4] on the host, per replica, of the last *_step (all chunks):
  *   [0] shader-clock cycles inside the Jacobi loop (rayleigh.py:419-454 / mixing.py:428-463), [1] in the whole replica,
@@ -275,6 +320,8 @@ BCN_API int bcn_set_noise(bcn_env_t h, double sigma, uint64_t seed, int64_t repl
  *   "generic_threads" 256 / 1024: workgroup size of the generic 2D kernel (0 = chosen by grid size)
  *   "cells_per_thread" (1D envs) 1, 2, 4, 8 cells per thread (0 = chosen from grid and batch); "one_wave" (1D envs) 0 / 1:
  *                 grids up to 512 cells as one wave per replica with DPP halos (default 1)
+ *   "obs_stage"   (lorenz, vortex) 1 = the observation rows [B][n_obs] go through LDS so that every store of a workgroup writes
+ *                 contiguous bytes (default of BCN_F64), 0 = each lane stores its own row (default of BCN_F32)
  * No environment variable changes any of these (round 5: the library reads none).
  * Returns BCN_ERR_ARG for unknown names. */
 BCN_API int bcn_set_option(bcn_env_t h, const char* name, int value);
@@ -295,7 +342,8 @@ BCN_API int bcn_get_slow_mode_bound(bcn_env_t h, double* cutoff, double* bound);
  * (2), 0 = one workgroup per replica in one launch, 1 = two launches with the
  * replicas re-ordered longest-first, 2 = persistent workgroups drawing (chunk of q timesteps, replica)
  * tickets; grid = persistent workgroups (0 = one per CU); q = timesteps per chunk (0 = kernel default);
- * lpt_min_batch = smallest batch that mode 1 splits (0 = CUs + 1).  Results do not depend on the mode. */
+ * lpt_min_batch = smallest batch that mode 1 splits (0 = CUs + 1).  Results do not depend on the mode.  BCN_ERR_ARG for lorenz
+ * and vortex (one lane per replica, nothing to schedule). */
 BCN_API int bcn_set_sched(bcn_env_t h, int mode, int grid, int q, int lpt_min_batch);
 /* name of the kernel the last *_step dispatched, e.g. "ns2d_fast_sched" (before the first step: the
  * variant's plain kernel); for profiles */

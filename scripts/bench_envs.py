@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Secondary benchmark lines (BASELINE.json configs 2, 3, 5 + sloshing): env steps/s and effective GB/s
+"""Secondary benchmark lines (BASELINE.json configs 2, 3, 5 + sloshing, lorenz, vortex): env steps/s and effective GB/s
 (SURVEY 8d algorithmic bytes / launch time) of the other solver kernels on one GPU, with the float64 C
 oracle timed on a bounded sample next to each.  Not the headline metric (that is bench.py).
 usage: python scripts/bench_envs.py [--steps K] [--no-cpu]"""
@@ -15,6 +15,7 @@ ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--no-cpu", action="store_true")
 ap.add_argument("--only", default="")
+ap.add_argument("--ode-batch", type=int, action="append", default=[], help="lorenz / vortex batch sizes (default 1024, 65536, 2^20)")
 ap.add_argument("--opt", action="append", default=[], help="name=value for bcn_set_option on every env (e.g. cells_per_thread=4)")
 args = ap.parse_args()
 dev = "cuda:0"
@@ -127,6 +128,52 @@ if "tall" in args.only:      # a grid above ny = 128 (ns2d_fast4_impl.h): mixing
          "env_steps_per_s": B * Km / wall, "launch_ms": ms, "effective_GBps": bytes_ / (ms * 1e-3) / 1e9,
          "mean_sweeps_per_timestep": float(sw.mean()), "dtype": "f32"}
     out.append(r); env.close()
+
+# the ODE envs (csrc/ode_env.h): one lane per replica, B from a trainer's 1 024 to 2^20; eager steps and a 100-step StepGraph.
+# Bytes per replica-step that the kernel must move (esz = 4 / 8), with actions given:
+#   lorenz: read x[3], t (4 reals), the int32 action and stp; write x[3], fx[3], t (7 reals), the action, stp, obs[6] and rwd
+#           (7 reals), done, trunc (2 B) and status (4 B)              -> 18 esz + 22 B  (f64 166 B, f32 94 B)
+#   vortex: read x[4], t, y (6 reals), the action[2] (2 reals) and stp; write x[4], fx[4], t, y, kmod, kphase, u[2] (14 reals),
+#           stp, obs[8] and rwd (9 reals), done, trunc and status        -> 31 esz + 14 B  (f64 262 B, f32 138 B)
+ODE_BYTES = {"lorenz": (18, 22), "vortex": (31, 14)}
+for name in ("lorenz", "vortex"):
+    if args.only and name not in args.only:
+        continue
+    cls = V.VecLorenz if name == "lorenz" else V.VecVortex
+    for B in (args.ode_batch or (1024, 65536, 1 << 20)):
+        for dt in ("f32", "f64"):
+            env = cls(B, dev, dt)
+            for o in args.opt:
+                env.set_option(o.split("=")[0], int(o.split("=")[1]))
+            env.reset()
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(7)
+            if name == "lorenz":
+                a = torch.randint(0, 3, (100, B), generator=gen, device=dev, dtype=torch.int32)
+            else:
+                a = (2 * torch.rand((100, B, 2), generator=gen, device=dev, dtype=torch.float64) - 1).to(env.tdtype)
+            nr, ni = ODE_BYTES[name]
+            bytes_ = (nr * (4 if dt == "f32" else 8) + ni) * B
+            wall, ms = timed(env, lambda k: env.step(a[k % 100]), K, W)
+            g = env.capture(a, n_steps=100, keep_steps=False)
+            g.replay()
+            torch.cuda.synchronize()
+            reps = max(1, K // 20)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                g.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            gms = e0.elapsed_time(e1) / (100 * reps)
+            r = {"env": "%s-v0 B=%d" % (name, B), "dtype": dt, "kernel": env.kernel_name, "bytes_per_replica_step": bytes_ / B,
+                 "eager_env_steps_per_s": B * K / wall, "eager_us_per_step": ms * 1e3,
+                 "eager_effective_GBps": bytes_ / (ms * 1e-3) / 1e9,
+                 "graph_env_steps_per_s": B / (gms * 1e-3), "graph_us_per_step": gms * 1e3,
+                 "graph_effective_GBps": bytes_ / (gms * 1e-3) / 1e9, "opts": args.opt}
+            out.append(r)
+            del g
+            env.close()
 
 for r in out:
     print(json.dumps(r))
