@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: aggregate env steps/s of rayleigh-v0 (BASELINE configs[3]: 128x64 grid, batch 512).
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--full]
 
 N > 1 without a launcher: this process touches no GPU and starts N children (one per GPU, env RANK /
 LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT); under `python -m torch.distributed.run
@@ -18,7 +18,14 @@ Inputs are synthetic and resident in HBM before the timed region: developed-flow
 tests/golden/rayleigh_128x64_init.npz (float64 oracle warm-up), actions from
 numpy.random.default_rng(1234).uniform(-1, 1, (steps, global batch, 10)), distinct per replica and step.
 Prints ONE JSON line on rank 0.  --dump-outputs DIR also writes what the last timed step returned (obs, rwd, done, trunc)
-as DIR/<name>.npy, so that two builds can be compared output for output."""
+as DIR/<name>.npy, so that two builds can be compared output for output.
+
+A plain run does only what the headline figure needs: set-up, the W warm-up and K timed steps, --dump-outputs, and the line
+(with what those steps yield besides: roofline, solver counters, ranks, topology).  --full adds the runs of their own that the
+headline does not need -- on one GPU: the CPU baselines, the secondary configurations, the headline once more through the
+N > 1 path (one rank over the backend; not with --force-dist) and the scaling prediction made from them; on the N > 1 path
+(N > 1 or --force-dist) with weak scaling: the strong-scaling loop.  --no-cpu / --no-secondary / --no-strong leave parts of
+--full out."""
 import argparse
 import json
 import os
@@ -46,8 +53,13 @@ def parse_args(argv=None):
     ap.add_argument("--dtype", default="f32")
     ap.add_argument("--variant", type=int, default=-1, help="-1 = best available, 0 = generic kernel")
     ap.add_argument("--sched", type=int, default=-1, help="scheduler mode of the fast kernels (bcn_set_sched)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline legs")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary configurations")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: on one GPU the CPU baselines, the secondary "
+                         "configurations, the N > 1 path rehearsal and the scaling prediction; on the N > 1 path with weak scaling "
+                         "the strong-scaling loop")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline legs")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="with --full: skip the N > 1 path rehearsal, the secondary configurations and the scaling prediction")
     ap.add_argument("--zero-actions", action="store_true",
                     help="diagnostic: uncontrolled steady flow (1 Jacobi sweep per timestep) -> non-Poisson cost")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (gloo with --stub)")
@@ -67,7 +79,8 @@ def parse_args(argv=None):
     ap.add_argument("--dist-timeout", type=float, default=300.0,
                     help="seconds a rank waits in the rendezvous / a collective before it gives up (init_process_group timeout)")
     ap.add_argument("--no-strong", action="store_true",
-                    help="N > 1, --scaling weak: skip the extra strong-scaling loop (global batch sharded) reported under `strong`")
+                    help="with --full, N > 1, --scaling weak: skip the extra strong-scaling loop (global batch sharded) reported under "
+                         "`strong`")
     ap.add_argument("--stub", action="store_true",
                     help="CPU stand-in env (no GPU, no kernels): exercises launcher, sharding and gather only; "
                          "its line is marked data=stub and is not a measurement")
@@ -79,6 +92,8 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:          # a plain run: the headline alone (module docstring)
+        args.no_cpu = args.no_secondary = args.no_strong = True
     return args
 
 

@@ -38,13 +38,13 @@ for what in "$@"; do
     stamp64) BEACON_NO_BUILD=0 BCN_STAMP_DTYPE=f64 step stamp64 1100 python3 scripts/stamp2.py ;;
     stampmix) BEACON_NO_BUILD=0 step stampmix 1100 python3 scripts/stamp_mixing.py ;;
     dist)    step tests_dist 600 python3 -m pytest tests -m gpu -q -k "rccl or gloo or masked" ;;
-    bench)   step bench 600 python3 bench.py --steps 20 --warmup 5 ;;
+    bench)   step bench 600 python3 bench.py --steps 20 --warmup 5 --full ;;
     benchq)  step benchq 600 python3 bench.py --steps 20 --warmup 5 --no-cpu --no-secondary ;;
-    fdist)   step fdist 600 python3 bench.py --gpus 1 --force-dist --steps 20 --warmup 5 --no-cpu --no-secondary
-             step fdist_noov 600 python3 bench.py --gpus 1 --force-dist --no-overlap --steps 20 --warmup 5 --no-cpu --no-secondary ;;
+    fdist)   step fdist 600 python3 bench.py --gpus 1 --force-dist --steps 20 --warmup 5 --full --no-cpu --no-secondary
+             step fdist_noov 600 python3 bench.py --gpus 1 --force-dist --no-overlap --steps 20 --warmup 5 --full --no-cpu --no-secondary ;;
     trace_fdist)
       cd /tmp && export TMPDIR=/tmp
-      step trace_fdist 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_fdist -o run -- python3 $ROOT/bench.py --gpus 1 --force-dist --steps 10 --warmup 2 --no-cpu --no-secondary
+      step trace_fdist 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_fdist -o run -- python3 $ROOT/bench.py --gpus 1 --force-dist --steps 10 --warmup 2 --full --no-cpu --no-secondary
       find $OUT/trace_fdist -name '*kernel_stats.csv' -exec cp {} $OUT/trace_fdist_kernel_stats.csv \;
       find $OUT/trace_fdist -name '*kernel_trace.csv' -exec cp {} $OUT/trace_fdist_kernel_trace.csv \;
       rm -rf $OUT/trace_fdist

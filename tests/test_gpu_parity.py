@@ -2662,13 +2662,14 @@ def test_one_rank_through_rccl(tmp_path):
 
 def test_bench_multi_gpu_path_over_rccl_with_one_rank():
     """`bench.py --force-dist`: the N > 1 code path of the bench (process group on the "nccl" backend with the device id,
-    barriers and the max-reduction around the timed region, the packed gather inside it, the strong-scaling loop) with a
-    world of ONE rank on the box's one GPU, self-launched and under torch.distributed.run as the driver starts it."""
+    barriers and the max-reduction around the timed region, the packed gather inside it, the strong-scaling loop of --full) with
+    a world of ONE rank on the box's one GPU, self-launched and under torch.distributed.run as the driver starts it."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = [os.path.join(root, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-secondary"]
+    common = [os.path.join(root, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "2", "--warmup", "1", "--full", "--no-cpu",
+              "--no-secondary"]
     for cmd in ([sys.executable] + common,
                 [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                  "--master-port", "29757"] + common):
@@ -2680,6 +2681,25 @@ def test_bench_multi_gpu_path_over_rccl_with_one_rank():
         d = json.loads(lines[0])
         assert d["n_gpus"] == 1 and d["steps"] == 2 and d["value"] > 1000 and d["config"]["kernel"] == "ns2d_fast_sched"
         assert d["strong"]["global_batch"] == 512 and d["strong"]["value"] > 1000
+
+
+def test_bench_plain_run_is_the_headline_alone():
+    """`bench.py --gpus 1` without --full: set-up, warm-up, the timed steps and the line, whose figure is those steps' own --
+    none of what --full adds (the N > 1 path rehearsal, the CPU baselines, the secondary configurations, the scaling prediction)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1"], env=env,
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["config"]["kernel"] == "ns2d_fast_sched"
+    assert abs(d["value"] - 512 * 2 / (d["ms_per_step"] * 2e-3)) < 1e-6 * d["value"]
+    assert not {"secondary", "cpu_baseline", "scaling_prediction", "strong"} & set(d) and "unverified_stop_rule" not in d["config"]
 
 
 def test_two_ranks_share_the_gpu_over_gloo(tmp_path):

@@ -357,11 +357,12 @@ dist.destroy_process_group()
 def test_bench_self_launch_and_scalings_on_cpu_stub():
     """`python bench.py --gpus 2` with no launcher: the parent starts one process per rank, rank 0 prints ONE JSON
     line; weak scaling doubles the global batch, strong scaling shards the batch of 512.  Run with the CPU stand-in
-    env over gloo (the line is marked data=stub: launcher / sharding / gather plumbing only)."""
+    env over gloo (the line is marked data=stub: launcher / sharding / gather plumbing only), with --full for the weak
+    line's strong-scaling loop."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     for scaling, per_gpu, glob in (("weak", 16, 32), ("strong", 8, 16)):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                            "--batch", "16", "--scaling", scaling, "--stub", "--backend", "gloo"],
+                            "--batch", "16", "--scaling", scaling, "--stub", "--backend", "gloo", "--full"],
                            env=env, capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stdout + r.stderr
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -385,7 +386,7 @@ def test_bench_world8_rehearsal_on_cpu_stub_carries_eight_rank_records():
     env["OMP_NUM_THREADS"] = "1"
     for scaling, per_gpu, glob in (("weak", 16, 128), ("strong", 2, 16)):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1",
-                            "--batch", "16", "--scaling", scaling, "--stub", "--backend", "gloo"],
+                            "--batch", "16", "--scaling", scaling, "--stub", "--backend", "gloo", "--full"],
                            env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stdout + r.stderr
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -406,7 +407,21 @@ def test_bench_world8_rehearsal_on_cpu_stub_carries_eight_rank_records():
 def test_bench_force_dist_runs_the_collectives_with_one_rank_on_cpu_stub():
     """`--gpus 1 --force-dist` (the one-GPU rehearsal of the N > 1 path: tests/test_gpu_parity.py runs it over RCCL): a
     world of one rank still builds the process group and sends its barriers, reductions and the packed gather through the
-    backend; here with the CPU stand-in env over gloo."""
+    backend; here with the CPU stand-in env over gloo, with --full for the strong-scaling loop."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "3", "--warmup", "1",
+                        "--batch", "16", "--stub", "--backend", "gloo", "--full"], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 1 and d["data"] == "stub" and d["config"]["global_batch"] == 16
+    assert d["strong"]["global_batch"] == 16 and d["strong"]["replicas_per_gpu"] == 16
+
+
+def test_bench_plain_run_leaves_the_strong_scaling_loop_to_full_on_cpu_stub():
+    """Without --full a run does only what its headline figure needs: the same command as the test above, without --full,
+    times its steps over the backend and prints the line, but runs no strong-scaling loop."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "3", "--warmup", "1",
                         "--batch", "16", "--stub", "--backend", "gloo"], env=env, capture_output=True, text=True, timeout=300)
@@ -414,8 +429,8 @@ def test_bench_force_dist_runs_the_collectives_with_one_rank_on_cpu_stub():
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
     d = json.loads(lines[0])
-    assert d["n_gpus"] == 1 and d["data"] == "stub" and d["config"]["global_batch"] == 16
-    assert d["strong"]["global_batch"] == 16 and d["strong"]["replicas_per_gpu"] == 16
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["config"]["global_batch"] == 16 and d["value"] > 0
+    assert "strong" not in d
 
 
 def test_bench_dump_outputs_writes_the_last_timed_step_on_cpu_stub(tmp_path):
