@@ -4,10 +4,11 @@ Batched envs (tensors on the GPU, one HIP launch per step):
     VecRayleigh, VecMixing, VecBurgers, VecShkadov, VecSloshing, VecLorenz, VecVortex
 Drop-in single-env mirrors of the reference classes:  beacon_amd.envs.{rayleigh, mixing, ...}
 Multi-GPU replica sharding:  beacon_amd.dist.ShardedVecEnv
+Full on-device state of a batch:  VecEnv.snapshot() -> Snapshot, VecEnv.restore(snap, src, mask), VecEnv.fork(src)
 
 Importing the package does not touch the GPU; constructing an env does, and raises if the HIP
 library or a ROCm device is missing (there is no CPU fallback for the solver path)."""
-from .vec import Box, Discrete, VecBurgers, VecEnv, VecLorenz, VecMixing, VecRayleigh, VecShkadov, VecSloshing, VecVortex  # noqa: F401
+from .vec import Box, Discrete, Snapshot, VecBurgers, VecEnv, VecLorenz, VecMixing, VecRayleigh, VecShkadov, VecSloshing, VecVortex  # noqa: F401
 from .lorenz import lorenz  # noqa: F401
 from .vortex import vortex  # noqa: F401
 

@@ -71,6 +71,14 @@ class VortexCfg(C.Structure):
                 ("phase_min", C.c_double), ("phase_max", C.c_double)]
 
 
+class SnapshotSeg(C.Structure):
+    """bcn_snapshot_seg: one named segment of a snapshot, [planes][n][row_elems] elements at `offset` bytes."""
+    _fields_ = [("name", C.c_char * 16), ("offset", C.c_uint64), ("elem", C.c_int32), ("planes", C.c_int32),
+                ("row_elems", C.c_int64)]
+
+
+SNAP_REAL, SNAP_I32, SNAP_U32, SNAP_U8 = 0, 1, 2, 3      # include/beacon_hip.h: BCN_SNAP_*
+
 # every symbol include/beacon_hip.h declares: (restype, argtypes)
 SIGNATURES = {
     "bcn_rayleigh_create": (C.c_int, [C.POINTER(RayleighCfg), C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
@@ -117,6 +125,12 @@ SIGNATURES = {
     "bcn_set_sched": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "bcn_set_slow_mode_bound": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "bcn_get_slow_mode_bound": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "bcn_snapshot_bytes": (C.c_size_t, [vp]),
+    "bcn_snapshot_bytes_n": (C.c_size_t, [vp, C.c_int]),
+    "bcn_snapshot_layout": (C.c_int, [vp, C.c_int, C.POINTER(SnapshotSeg), C.c_int]),
+    "bcn_snapshot_signature": (C.c_uint64, [vp]),
+    "bcn_snapshot_save": (C.c_int, [vp, vp, vp, vp]),
+    "bcn_snapshot_load": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp]),
     "bcn_kernel_name": (C.c_char_p, [vp]),
     "bcn_destroy": (C.c_int, [vp]),
     "bcn_last_error": (C.c_char_p, []),

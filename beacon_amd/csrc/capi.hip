@@ -3,6 +3,7 @@
 // narrowed once), state copies.  All device work is enqueued on the caller's stream.
 #include <math.h>
 #include <stdarg.h>
+#include <stddef.h>
 
 #include <new>
 #include <vector>
@@ -10,6 +11,7 @@
 #include "env1d.h"
 #include "ns2d.h"
 #include "ode_env.h"
+#include "snapshot.h"
 
 thread_local const char* bcn_env1d_launched = nullptr;   // env1d.h: set by the 1D launchers
 
@@ -31,6 +33,22 @@ struct DeviceGuard {
   ~DeviceGuard() { (void)hipSetDevice(prev); }
 };
 
+// FNV-1a over the values of a cfg struct (its int32 members, then its doubles: the layout of every bcn_*_cfg), without the padding
+// between the two groups: the part of bcn_snapshot_signature that says "same constructor arguments"
+uint64_t snap_fnv(uint64_t h, const void* p, size_t n) {
+  const unsigned char* c = static_cast<const unsigned char*>(p);
+  for (size_t i = 0; i < n; i++) { h ^= c[i]; h *= 1099511628211ull; }
+  return h;
+}
+template <typename Cfg, int NI, int ND>
+uint64_t snap_cfg_hash(const Cfg* c) {
+  constexpr size_t doubles_at = (NI * sizeof(int32_t) + 7) / 8 * 8;
+  static_assert(sizeof(Cfg) == doubles_at + ND * sizeof(double), "cfg struct: NI int32 members followed by ND doubles");
+  static_assert(offsetof(Cfg, ndt_act) < NI * sizeof(int32_t) && offsetof(Cfg, dt) >= doubles_at, "cfg struct: the int32 members come first");
+  uint64_t h = snap_fnv(14695981039346656037ull, c, NI * sizeof(int32_t));
+  return snap_fnv(h, reinterpret_cast<const char*>(c) + doubles_at, ND * sizeof(double));
+}
+
 // ------------------------------------------------------------------------------------------
 // rayleigh / mixing
 // ------------------------------------------------------------------------------------------
@@ -42,6 +60,7 @@ struct NS2DEnv : bcn_env_s {
   DevBuf obs_hist, a_last, ia_last, stpbuf, sweepbuf, orderbuf, schedbuf, fscrbuf, statusbuf;
   int32_t* status_int = nullptr;   // per-replica status words when the caller passes no status_dev
   bool fast_ok = false;
+  uint64_t cfg_hash = 0;           // of the constructor's cfg (bcn_snapshot_signature)
   bool guard_holds() const { return a.nx >= 48 && a.ny >= 48; }
 
   int init() {
@@ -254,6 +273,7 @@ int make_rayleigh(const bcn_rayleigh_cfg* c, int batch, int dtype, int device, b
   a.Tc = (real)c->Tc; a.Th = (real)c->Th; a.C = (real)c->C;
   a.rwd_scale = (real)(1.0 / (0.5 * c->dy * c->nx));
   e->n_obs = a.n_obs; e->n_act = c->n_sgts; e->ndt_act = a.ndt_act;
+  e->cfg_hash = snap_cfg_hash<bcn_rayleigh_cfg, 12, 9>(c);
   int rc = e->init();
   if (rc) { delete e; return rc; }
   *out = e;
@@ -276,6 +296,7 @@ int make_mixing(const bcn_mixing_cfg* c, int batch, int dtype, int device, bcn_e
   a.ksc = (real)(1.0 / c->pe);
   a.u_max = (real)c->u_max; a.ref_c = (real)c->ref_c; a.C0 = (real)c->C0;
   e->n_obs = a.n_obs; e->n_act = 1; e->ndt_act = a.ndt_act;
+  e->cfg_hash = snap_cfg_hash<bcn_mixing_cfg, 14, 9>(c);
   int rc = e->init();
   if (rc) { delete e; return rc; }
   *out = e;
@@ -289,11 +310,14 @@ template <typename real>
 struct Env1D : bcn_env_s {
   Env1DArgs<real> a{};
   int nfields = 4;
+  int nact = 1;                    // columns of a_last / a_prev
+  uint64_t cfg_hash = 0;           // of the constructor's cfg (bcn_snapshot_signature)
   DevBuf fields, a_last, a_prev, stpbuf, nctrbuf;
   const char* kname = "";
 
   int init(int n_actions) {
     int rc;
+    nact = n_actions;
     const size_t per = (size_t)batch * a.n * sizeof(real);
     if ((rc = fields.alloc(4 * per))) return rc;
     BCN_HIP(hipMemset(fields.p, 0, 4 * per));
@@ -366,6 +390,7 @@ int make_burgers(const bcn_burgers_cfg* c, int batch, int dtype, int device, bcn
   a.u_target = (real)c->u_target; a.amp = (real)c->amp;
   a.dx = (real)c->dx; a.rdx = (real)(1.0 / c->dx); a.dt = (real)c->dt;
   e->n_obs = c->n_obs_pts; e->n_act = 1; e->ndt_act = a.ndt_act;
+  e->cfg_hash = snap_cfg_hash<bcn_burgers_cfg, 5, 4>(c);
   int rc = e->init(1);
   if (rc) { delete e; return rc; }
   *out = e;
@@ -388,6 +413,7 @@ int make_shkadov(const bcn_shkadov_cfg* c, int batch, int dtype, int device, bcn
   a.blowup_rwd = (real)c->blowup_rwd;
   a.dx = (real)c->dx; a.rdx = (real)(1.0 / c->dx); a.dt = (real)c->dt;
   e->n_obs = a.n_obs; e->n_act = c->n_jets; e->ndt_act = a.ndt_act;
+  e->cfg_hash = snap_cfg_hash<bcn_shkadov_cfg, 12, 7>(c);
   int rc = e->init(c->n_jets);
   if (rc) { delete e; return rc; }
   *out = e;
@@ -407,6 +433,7 @@ int make_sloshing(const bcn_sloshing_cfg* c, int batch, int dtype, int device, b
   a.g = (real)c->g; a.amp = (real)c->amp; a.alpha = (real)c->alpha;
   a.dx = (real)c->dx; a.rdx = (real)(1.0 / c->dx); a.dt = (real)c->dt;
   e->n_obs = a.n_obs; e->n_act = 1; e->ndt_act = a.ndt_act;
+  e->cfg_hash = snap_cfg_hash<bcn_sloshing_cfg, 4, 5>(c);
   int rc = e->init(1);
   if (rc) { delete e; return rc; }
   *out = e;
@@ -421,6 +448,7 @@ struct OdeEnv : bcn_env_s {
   OdeArgs<real> a{};
   DevBuf st, iubuf, stpbuf, stage;   // stage: [B][n_state] rows of a host-side state copy
   int nreal = 0, nstate = 0;
+  uint64_t cfg_hash = 0;           // of the constructor's cfg (bcn_snapshot_signature)
 
   int init() {
     int rc;
@@ -485,6 +513,7 @@ int make_lorenz(const bcn_lorenz_cfg* c, int batch, int dtype, int device, bcn_e
   a.kind = BCN_LORENZ; a.ndt_act = c->ndt_act; a.n_act = c->n_act;
   a.dt = (real)c->dt; a.sigma = (real)c->sigma; a.rho = (real)c->rho; a.beta = (real)c->beta;
   e->n_obs = 6; e->n_act = 1; e->ndt_act = c->ndt_act;
+  e->cfg_hash = snap_cfg_hash<bcn_lorenz_cfg, 2, 4>(c);
   int rc = e->init();
   if (rc) { delete e; return rc; }
   *out = e;
@@ -513,6 +542,7 @@ int make_vortex(const bcn_vortex_cfg* c, int batch, int dtype, int device, bcn_e
   a.rwd_k = (real)(2.0 * c->omega_s * c->gamma);
   a.weight = (real)c->weight;
   e->n_obs = 8; e->n_act = 2; e->ndt_act = c->ndt_act;
+  e->cfg_hash = snap_cfg_hash<bcn_vortex_cfg, 2, 19>(c);
   int rc = e->init();
   if (rc) { delete e; return rc; }
   *out = e;
@@ -583,6 +613,102 @@ static Env1DArgs<real>& env1d_io(bcn_env_t h, const void* actions, const void* n
   a.rwd_out = static_cast<real*>(rwd);
   a.done = done; a.trunc = trunc; a.status = status;
   return a;
+}
+
+// ------------------------------------------------------------------------------------------
+// snapshots (snapshot.h): which arrays of a handle are state, and where they sit in a snapshot of n replicas
+// ------------------------------------------------------------------------------------------
+// One named segment: `planes` arrays of [replicas][row_elems] one behind the other -- in the handle (plane stride = batch rows) and
+// in the snapshot (plane stride = n rows).
+struct SnapDesc { const char* name; int elem; int planes; size_t row_elems; void* dev; };
+
+// What the next *_step reads of what an earlier call wrote ("Snapshots", has the reasoning for what is left out: us / vs,
+// the work arrays, fscr, the sweep counts, the scheduler block and the cycle counters are rewritten or zeroed inside every step).
+template <typename real>
+int snap_desc(bcn_env_t h, SnapDesc* d) {
+  int n = 0;
+  if (h->kind == BCN_RAYLEIGH || h->kind == BCN_MIXING) {
+    auto* e = static_cast<NS2DEnv<real>*>(h);
+    d[n++] = {"fields", BCN_SNAP_REAL, 4, (size_t)e->a.ncell, e->fields.p};
+    d[n++] = {"obs_hist", BCN_SNAP_REAL, 1, (size_t)e->a.n_obs, e->obs_hist.p};
+    if (h->kind == BCN_RAYLEIGH) d[n++] = {"a_last", BCN_SNAP_REAL, 1, (size_t)e->a.n_sgts, e->a_last.p};
+    else d[n++] = {"ia_last", BCN_SNAP_I32, 1, 1, e->ia_last.p};
+    d[n++] = {"stp", BCN_SNAP_I32, 1, 1, e->stpbuf.p};
+  } else if (h->kind == BCN_LORENZ || h->kind == BCN_VORTEX) {
+    auto* e = static_cast<OdeEnv<real>*>(h);
+    d[n++] = {"fields", BCN_SNAP_REAL, e->nreal, 1, e->st.p};
+    if (h->kind == BCN_LORENZ) d[n++] = {"iu", BCN_SNAP_I32, 1, 1, e->iubuf.p};
+    d[n++] = {"stp", BCN_SNAP_I32, 1, 1, e->stpbuf.p};
+  } else {
+    auto* e = static_cast<Env1D<real>*>(h);
+    d[n++] = {"fields", BCN_SNAP_REAL, e->nfields, (size_t)e->a.n, e->fields.p};
+    d[n++] = {"a_last", BCN_SNAP_REAL, 1, (size_t)e->nact, e->a_last.p};
+    d[n++] = {"a_prev", BCN_SNAP_REAL, 1, (size_t)e->nact, e->a_prev.p};
+    d[n++] = {"stp", BCN_SNAP_I32, 1, 1, e->stpbuf.p};
+    d[n++] = {"nctr", BCN_SNAP_U32, 1, 1, e->nctrbuf.p};
+  }
+  return n;
+}
+
+uint64_t snap_cfg_of(bcn_env_t h) {
+  if (h->kind == BCN_RAYLEIGH || h->kind == BCN_MIXING)
+    return h->dtype == BCN_F32 ? static_cast<NS2DEnv<float>*>(h)->cfg_hash : static_cast<NS2DEnv<double>*>(h)->cfg_hash;
+  if (h->kind == BCN_LORENZ || h->kind == BCN_VORTEX)
+    return h->dtype == BCN_F32 ? static_cast<OdeEnv<float>*>(h)->cfg_hash : static_cast<OdeEnv<double>*>(h)->cfg_hash;
+  return h->dtype == BCN_F32 ? static_cast<Env1D<float>*>(h)->cfg_hash : static_cast<Env1D<double>*>(h)->cfg_hash;
+}
+
+inline size_t snap_up16(size_t x) { return (x + 15) / 16 * 16; }
+
+// Lays out a snapshot of n replicas of this handle's configuration: the bytes it takes, optionally the named segments (`lay`, up to
+// max_lay; the count is returned) and the kernels' table `t` (handle side: this handle's arrays and the packed output buffer
+// `out_buf` of its `batch` replicas; NULL out_buf leaves the five output segments out of the copy).
+int snap_build(bcn_env_t h, int n, char* out_buf, SnapTable* t, bcn_snapshot_seg* lay, int max_lay, size_t* bytes) {
+  SnapDesc d[16];
+  int nd = h->dtype == BCN_F32 ? snap_desc<float>(h, d) : snap_desc<double>(h, d);
+  const size_t B = (size_t)h->batch, esz = h->esz;
+  // the packed per-step outputs [obs | rwd | status | done | trunc], every part 16-byte aligned (bcn_snapshot_save)
+  const size_t o_rwd = snap_up16(B * h->n_obs * esz), o_status = snap_up16(o_rwd + B * esz), o_done = snap_up16(o_status + B * 4),
+               o_trunc = snap_up16(o_done + B);
+  d[nd++] = {"obs", BCN_SNAP_REAL, 1, (size_t)h->n_obs, out_buf};
+  d[nd++] = {"rwd", BCN_SNAP_REAL, 1, 1, out_buf ? out_buf + o_rwd : nullptr};
+  d[nd++] = {"status", BCN_SNAP_I32, 1, 1, out_buf ? out_buf + o_status : nullptr};
+  d[nd++] = {"done", BCN_SNAP_U8, 1, 1, out_buf ? out_buf + o_done : nullptr};
+  d[nd++] = {"trunc", BCN_SNAP_U8, 1, 1, out_buf ? out_buf + o_trunc : nullptr};
+  size_t off = 0, blk = 0;
+  int ns = 0;
+  for (int k = 0; k < nd; k++) {
+    off = snap_up16(off);
+    const size_t el = d[k].elem == BCN_SNAP_REAL ? esz : d[k].elem == BCN_SNAP_U8 ? 1 : 4;
+    const size_t row = d[k].row_elems * el;
+    if (lay && k < max_lay) {
+      memset(&lay[k], 0, sizeof(lay[k]));
+      strncpy(lay[k].name, d[k].name, sizeof(lay[k].name) - 1);
+      lay[k].offset = off; lay[k].elem = d[k].elem; lay[k].planes = d[k].planes; lay[k].row_elems = (int64_t)d[k].row_elems;
+    }
+    for (int pl = 0; t && d[k].dev && pl < d[k].planes; pl++) {
+      if (ns >= BCN_SNAP_MAX_SEG || row == 0 || row > 0xffffffffull) { bcn_set_error("snapshot: segment table overflow"); return -1; }
+      SnapSeg& g = t->seg[ns++];
+      g.dev = static_cast<char*>(d[k].dev) + (size_t)pl * B * row;
+      g.snap_off = off + (size_t)pl * (size_t)n * row;
+      g.row_bytes = (unsigned)row;
+      g.blk0 = (unsigned)blk;
+      if (row >= BCN_SNAP_LONG_ROW) {
+        g.bpr = (unsigned)((row + BCN_SNAP_TILE - 1) / BCN_SNAP_TILE);
+        g.unit = 16;
+        blk += B * g.bpr;
+      } else {
+        g.bpr = 0;
+        g.unit = row % 16 == 0 ? 16 : row % 8 == 0 ? 8 : row % 4 == 0 ? 4 : 1;
+        blk += (B * (row / g.unit) + BCN_SNAP_NT * 4 - 1) / (BCN_SNAP_NT * 4);
+      }
+      if (blk > 0x7fffffffull) { bcn_set_error("snapshot: batch too large for one launch"); return -1; }
+    }
+    off += (size_t)d[k].planes * (size_t)n * row;
+  }
+  if (bytes) *bytes = snap_up16(off);
+  if (t) { t->nseg = ns; t->batch = h->batch; t->n_src = n; t->nblk = (unsigned)blk; }
+  return nd;
 }
 
 }  // namespace
@@ -854,6 +980,56 @@ int bcn_set_sched(bcn_env_t h, int mode, int grid, int q, int lpt_min_batch) {
   if (!h) { bcn_set_error("null handle"); return BCN_ERR_ARG; }
   if (mode < -1 || mode > 2 || grid < 0 || q < 0 || lpt_min_batch < 0) { bcn_set_error("bcn_set_sched: argument out of range"); return BCN_ERR_ARG; }
   return h->set_sched(mode, grid, q, lpt_min_batch);
+}
+// ---- snapshots -------------------------------------------------------------------------------
+size_t bcn_snapshot_bytes_n(bcn_env_t h, int n) {
+  size_t bytes = 0;
+  if (!h || n < 1 || snap_build(h, n, nullptr, nullptr, nullptr, 0, &bytes) < 0) return 0;
+  return bytes;
+}
+size_t bcn_snapshot_bytes(bcn_env_t h) { return h ? bcn_snapshot_bytes_n(h, h->batch) : 0; }
+int bcn_snapshot_layout(bcn_env_t h, int n, bcn_snapshot_seg* segs, int max_segs) {
+  if (!h || n < 1 || (max_segs > 0 && !segs)) { bcn_set_error("bcn_snapshot_layout: null handle/array or n < 1"); return 0; }
+  const int nd = snap_build(h, n, nullptr, nullptr, segs, max_segs, nullptr);
+  return nd < 0 ? 0 : nd;
+}
+uint64_t bcn_snapshot_signature(bcn_env_t h) {
+  if (!h) return 0;
+  bcn_snapshot_seg lay[16];
+  const int nd = snap_build(h, 1, nullptr, nullptr, lay, 16, nullptr);
+  const int32_t head[2] = {h->kind, h->dtype};
+  uint64_t sig = snap_fnv(14695981039346656037ull, head, sizeof(head));
+  const uint64_t cfg = snap_cfg_of(h);
+  sig = snap_fnv(sig, &cfg, sizeof(cfg));
+  for (int k = 0; k < nd && k < 16; k++) {
+    sig = snap_fnv(sig, lay[k].name, sizeof(lay[k].name));
+    sig = snap_fnv(sig, &lay[k].elem, sizeof(int32_t));
+    sig = snap_fnv(sig, &lay[k].planes, sizeof(int32_t));
+    sig = snap_fnv(sig, &lay[k].row_elems, sizeof(int64_t));
+  }
+  return sig;
+}
+static int snap_ptr_ok(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+int bcn_snapshot_save(bcn_env_t h, void* snap_dev, const void* out_buf_dev, void* stream) {
+  if (!h || !snap_dev) { bcn_set_error("bcn_snapshot_save: null handle/buffer"); return BCN_ERR_ARG; }
+  if (!snap_ptr_ok(snap_dev) || !snap_ptr_ok(out_buf_dev)) { bcn_set_error("bcn_snapshot_save: buffers must be 16-byte aligned"); return BCN_ERR_ARG; }
+  SnapTable t;
+  if (snap_build(h, h->batch, static_cast<char*>(const_cast<void*>(out_buf_dev)), &t, nullptr, 0, nullptr) < 0) return BCN_ERR_ARG;
+  DeviceGuard g(h->device);
+  return snapshot_launch(t, false, static_cast<char*>(snap_dev), nullptr, nullptr, static_cast<hipStream_t>(stream));
+}
+int bcn_snapshot_load(bcn_env_t h, const void* snap_dev, int n_src, const int32_t* src_dev, const uint8_t* mask_dev,
+                      void* out_buf_dev, void* stream) {
+  if (!h || !snap_dev) { bcn_set_error("bcn_snapshot_load: null handle/buffer"); return BCN_ERR_ARG; }
+  if (n_src < 1 || (!src_dev && n_src != h->batch)) {
+    bcn_set_error("bcn_snapshot_load: a snapshot of %d replicas into a batch of %d needs a source index per replica", n_src, h->batch);
+    return BCN_ERR_ARG;
+  }
+  if (!snap_ptr_ok(snap_dev) || !snap_ptr_ok(out_buf_dev)) { bcn_set_error("bcn_snapshot_load: buffers must be 16-byte aligned"); return BCN_ERR_ARG; }
+  SnapTable t;
+  if (snap_build(h, n_src, static_cast<char*>(out_buf_dev), &t, nullptr, 0, nullptr) < 0) return BCN_ERR_ARG;
+  DeviceGuard g(h->device);
+  return snapshot_launch(t, true, static_cast<char*>(const_cast<void*>(snap_dev)), src_dev, mask_dev, static_cast<hipStream_t>(stream));
 }
 const char* bcn_kernel_name(bcn_env_t h) { return h ? h->kernel_name() : ""; }
 int bcn_destroy(bcn_env_t h) {

@@ -1,5 +1,6 @@
 // beacon_torch.cpp -- the thin PyTorch-ROCm extension over the C ABI (include/beacon_hip.h): torch.library ops
 //   beacon::{rayleigh,mixing,burgers,shkadov,sloshing,lorenz,vortex}_{step,reset}(int handle, Tensor ...) -> ()
+//   beacon::snapshot_{save,load}(int handle, Tensor ...) -> ()
 // Each op is ONE dispatcher call that takes device tensors, reads torch's current HIP stream in C++ and forwards to the
 // bcn_* entry point of libbeacon_hip.so -- no ctypes marshalling, no Python-side stream query (what the per-call host cost of
 // the ctypes binding was made of: scripts/host_cost.py), and an op CUDA-graph capture and fake-tensor tracing can see (Meta kernels below).  The ops
@@ -181,6 +182,35 @@ void vortex_step(int64_t h_, OptT actions, const Tensor& obs, const Tensor& rwd,
         "bcn_vortex_step");
 }
 
+// ---- snapshots (include/beacon_hip.h: bcn_snapshot_save / bcn_snapshot_load) --------------------------------------------
+// bytes of the packed output buffer [obs | rwd | status | done | trunc] of the handle's batch, every part 16-byte aligned
+inline int64_t out_buf_bytes(bcn_env_t h) {
+  auto up = [](int64_t x) { return (x + 15) / 16 * 16; };
+  const int64_t B = bcn_batch(h), esz = bcn_dtype(h) == BCN_F64 ? 8 : 4;
+  return up(up(up(up(up(B * bcn_n_obs(h) * esz) + B * esz) + B * 4) + B) + B);
+}
+inline uint8_t* bytes_of(const Tensor& t, bcn_env_t h, int64_t n, const char* name) {
+  on_device(t, h, name);
+  TORCH_CHECK(t.scalar_type() == at::kByte, name, ": uint8 tensor expected");
+  TORCH_CHECK(t.numel() == n, name, ": ", t.numel(), " bytes, expected ", n);
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0, name, ": must be 16-byte aligned");
+  return t.data_ptr<uint8_t>();
+}
+void snapshot_save(int64_t h_, const Tensor& snap, const Tensor& out_buf) {
+  bcn_env_t h = H(h_);
+  uint8_t* s = bytes_of(snap, h, (int64_t)bcn_snapshot_bytes(h), "snap");
+  check(bcn_snapshot_save(h, s, bytes_of(out_buf, h, out_buf_bytes(h), "out_buf"), stream_of(snap)), "bcn_snapshot_save");
+}
+void snapshot_load(int64_t h_, const Tensor& snap, int64_t n_src, OptT src, OptT mask, const Tensor& out_buf) {
+  bcn_env_t h = H(h_);
+  TORCH_CHECK(n_src >= 1 && n_src <= INT32_MAX, "n_src: ", n_src, " replicas");
+  TORCH_CHECK(src.has_value() || n_src == bcn_batch(h), "snapshot of ", n_src, " replicas into a batch of ", bcn_batch(h), " needs src");
+  const uint8_t* s = bytes_of(snap, h, (int64_t)bcn_snapshot_bytes_n(h, (int)n_src), "snap");
+  const int32_t* idx = src.has_value() ? i32(*src, h, 1, "src") : nullptr;
+  const uint8_t* m = mask.has_value() ? u8(*mask, h, 1, "mask") : nullptr;
+  check(bcn_snapshot_load(h, s, (int)n_src, idx, m, bytes_of(out_buf, h, out_buf_bytes(h), "out_buf"), stream_of(out_buf)), "bcn_snapshot_load");
+}
+
 // Meta (fake-tensor) kernels: the ops return nothing and their outputs keep their shapes, so tracing needs no more than this.
 void reset2_meta(int64_t, const Tensor&) {}
 void reset3_meta(int64_t, OptT, const Tensor&) {}
@@ -188,6 +218,8 @@ void rayleigh_step_meta(int64_t, OptT, const Tensor&, const Tensor&, const Tenso
 void mixing_step_meta(int64_t, OptT, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&) {}
 void noisy_step_meta(int64_t, OptT, OptT, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&) {}
 void sloshing_step_meta(int64_t, OptT, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&) {}   // also lorenz, vortex
+void snapshot_save_meta(int64_t, const Tensor&, const Tensor&) {}
+void snapshot_load_meta(int64_t, const Tensor&, int64_t, OptT, OptT, const Tensor&) {}
 
 }  // namespace
 
@@ -215,6 +247,8 @@ TORCH_LIBRARY(beacon, m) {
   m.def("vortex_reset(int handle, Tensor(a!) obs) -> ()");
   m.def("vortex_step(int handle, Tensor? actions, Tensor(a!) obs, Tensor(b!) rwd, Tensor(c!) done, Tensor(d!) trunc, "
         "Tensor(e!) status) -> ()");
+  m.def("snapshot_save(int handle, Tensor(a!) snap, Tensor out_buf) -> ()");
+  m.def("snapshot_load(int handle, Tensor snap, int n_src, Tensor? src, Tensor? mask, Tensor(a!) out_buf) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(beacon, CUDA, m) {
@@ -232,6 +266,8 @@ TORCH_LIBRARY_IMPL(beacon, CUDA, m) {
   m.impl("lorenz_step", &lorenz_step);
   m.impl("vortex_reset", &vortex_reset);
   m.impl("vortex_step", &vortex_step);
+  m.impl("snapshot_save", &snapshot_save);
+  m.impl("snapshot_load", &snapshot_load);
 }
 
 TORCH_LIBRARY_IMPL(beacon, Meta, m) {
@@ -249,4 +285,6 @@ TORCH_LIBRARY_IMPL(beacon, Meta, m) {
   m.impl("lorenz_step", &sloshing_step_meta);
   m.impl("vortex_reset", &reset2_meta);
   m.impl("vortex_step", &sloshing_step_meta);
+  m.impl("snapshot_save", &snapshot_save_meta);
+  m.impl("snapshot_load", &snapshot_load_meta);
 }

@@ -53,13 +53,70 @@ def _ptr(t):
 _OPS = ("rayleigh_reset", "rayleigh_step", "mixing_reset", "mixing_step", "burgers_reset", "burgers_step", "shkadov_reset",
         "shkadov_step", "sloshing_reset", "sloshing_step")
 _ODE_OPS = ("lorenz_reset", "lorenz_step", "vortex_reset", "vortex_step")     # the ODE envs (csrc/ode_env.h)
+_STATE_OPS = ("snapshot_save", "snapshot_load")                               # every env (csrc/snapshot.hip)
 
 
 def _op_table():
     """{name: torch.ops.beacon.<name>.default} of the torch extension (beacon_amd/torch_ext.py), or None without it."""
     from . import torch_ext
     ops = torch_ext.load()
-    return None if ops is None else {n: getattr(ops, n).default for n in _OPS + _ODE_OPS}
+    return None if ops is None else {n: getattr(ops, n).default for n in _OPS + _ODE_OPS + _STATE_OPS}
+
+
+class Snapshot(object):
+    """Everything one VecEnv needs to continue its episodes bit for bit (VecEnv.snapshot / restore / fork), for `batch` replicas:
+    `buf`, one uint8 tensor in the layout of include/beacon_hip.h (bcn_snapshot_*), and `meta`, a dict of plain values:
+    env (class name), kind, dtype ("f32" / "f64"), batch, signature (bcn_snapshot_signature: env kind, dtype, constructor
+    values, segment shapes), layout (the segments: name, offset, elem, planes, row_elems), field_shape, ctor (the env's
+    constructor kwargs), version (of the library that wrote it), noise (sigma, seed, replica_offset: kernel arguments, recorded
+    only) and gen_state (the env's torch generator, or None)."""
+
+    _ELEM = {_lib.SNAP_I32: torch.int32, _lib.SNAP_U32: torch.int32, _lib.SNAP_U8: torch.uint8}
+
+    def __init__(self, buf, meta):
+        if not torch.is_tensor(buf) or buf.dtype != torch.uint8 or buf.dim() != 1:
+            raise ValueError("Snapshot: buf must be a 1-D uint8 tensor")
+        self.buf, self.meta = buf, dict(meta)
+
+    batch = property(lambda self: int(self.meta["batch"]))
+    signature = property(lambda self: int(self.meta["signature"]))
+    device = property(lambda self: self.buf.device)
+
+    def names(self):
+        return [seg["name"] for seg in self.meta["layout"]]
+
+    def view(self, name):
+        """Typed view (no copy) of one segment: "fields" [planes, batch, ...] (the planes of get_state() in front of the batch
+        axis), "obs_hist", "a_last" / "ia_last" / "iu", "a_prev", "stp", "nctr" (the uint32 counters as int32 bits), "obs", "rwd",
+        "status", "done", "trunc" -- whichever the env has (names()).  KeyError for any other name."""
+        for seg in self.meta["layout"]:
+            if seg["name"] == name:
+                break
+        else:
+            raise KeyError(name)
+        dt = self._ELEM.get(seg["elem"], _DT[self.meta["dtype"]][0])
+        esz = torch.empty((), dtype=dt).element_size()
+        n, planes, row = self.batch, int(seg["planes"]), int(seg["row_elems"])
+        v = self.buf[seg["offset"]:seg["offset"] + planes * n * row * esz].view(dt)
+        if name == "fields":
+            shape = tuple(self.meta.get("field_shape") or ())
+            return v.view((planes, n) + shape) if shape else v.view(planes, n)
+        return v.view(n, row) if row > 1 or name in ("obs", "obs_hist", "a_last", "a_prev") else v.view(n)
+
+    def to(self, device):
+        """The same snapshot with `buf` on `device` (self when it is there already)."""
+        buf = self.buf.to(device)
+        return self if buf is self.buf else Snapshot(buf, self.meta)
+
+    def save(self, path):
+        """torch.save of `buf` (moved to the CPU) and `meta`."""
+        torch.save({"buf": self.buf.cpu(), "meta": self.meta}, path)
+
+    @staticmethod
+    def load(path, device=None):
+        d = torch.load(path, map_location="cpu", weights_only=True)
+        snap = Snapshot(d["buf"], d["meta"])
+        return snap if device is None else snap.to(device)
 
 
 class VecEnv(object):
@@ -177,6 +234,124 @@ class VecEnv(object):
         st = self._real(state, (self.batch,) + self.state_shape())
         _lib.check(self.lib.bcn_set_state(self.h, _ptr(st), 1, self._stream()))
         torch.cuda.current_stream(self.device).synchronize()  # `st` may be a temporary
+
+    # -- snapshots --------------------------------------------------------------------------
+    def snapshot_signature(self):
+        """bcn_snapshot_signature of this env: equal for two envs exactly when they can exchange snapshots.  It covers env kind,
+        dtype, the constructor's values (set_ndt_act builds a new handle, so its ndt_act counts) and the segment shapes; options,
+        variant and noise settings made on the handle afterwards are not in it (they do not change what the bytes mean)."""
+        return int(self.lib.bcn_snapshot_signature(self.h))
+
+    def _snap_meta(self):
+        segs = (_lib.SnapshotSeg * 16)()
+        k = self.lib.bcn_snapshot_layout(self.h, self.batch, segs, 16)
+        if k <= 0:
+            raise _lib.BeaconHipError("libbeacon_hip: %s" % self.lib.bcn_last_error().decode())
+        lay = [dict(name=segs[i].name.decode(), offset=int(segs[i].offset), elem=int(segs[i].elem), planes=int(segs[i].planes),
+                    row_elems=int(segs[i].row_elems)) for i in range(k)]
+        shape = self.state_shape()
+        return dict(env=type(self).__name__, kind=int(self.lib.bcn_env_kind(self.h)), dtype="f64" if self.tdtype == torch.float64 else "f32",
+                    batch=self.batch, signature=self.snapshot_signature(), layout=lay,
+                    field_shape=list(shape[1:]) if len(shape) > 1 else [], ctor=dict(getattr(self, "_ctor", {})),
+                    version=self.lib.bcn_version().decode(), noise=None, gen_state=None)
+
+    def _snap_volatile(self, meta):
+        gen = getattr(self, "gen", None)
+        # (inside a graph capture the generator is left alone: its state is host-side and not part of what the graph replays)
+        meta["gen_state"] = None if gen is None or torch.cuda.is_current_stream_capturing() else gen.get_state()
+        meta["noise"] = (dict(sigma=float(self.sigma), seed=int(self.seed), replica_offset=int(self.replica_offset))
+                         if self.needs_noise else None)
+
+    def _check_snap(self, snap, what):
+        if not isinstance(snap, Snapshot):
+            raise ValueError("%s: a Snapshot expected, got %s" % (what, type(snap).__name__))
+        if snap.signature != self.snapshot_signature():
+            raise ValueError("%s: the snapshot was taken from another configuration (%s %s, signature %#x; this env: %s, %#x)"
+                             % (what, snap.meta.get("env"), snap.meta.get("dtype"), snap.signature, type(self).__name__,
+                                self.snapshot_signature()))
+        if snap.buf.device != self.device:
+            raise ValueError("%s: the snapshot lives on %s, this env on %s (Snapshot.to moves it)" % (what, snap.buf.device, self.device))
+        if snap.buf.numel() != self.lib.bcn_snapshot_bytes_n(self.h, snap.batch) or not snap.buf.is_contiguous():
+            raise ValueError("%s: %d bytes do not hold %d replicas of this env" % (what, snap.buf.numel(), snap.batch))
+
+    def snapshot(self, out=None):
+        """Save every replica -- solver fields, observation history, stored actions, episode and noise-draw counters, and the
+        outputs (obs, rwd, status, done, trunc) of the last reset() / step() -- into a Snapshot: ONE kernel launch on the current
+        stream, no host synchronisation, so it can be captured into a graph.  `out`: a Snapshot of this env's signature and batch to
+        overwrite (nothing is allocated; `out` itself is returned).  Not saved, because they are outputs only or kernel arguments:
+        `sweeps`, `actions_norm`, counters, options, the noise sigma / seed / replica_offset (recorded in meta["noise"])."""
+        if out is None:
+            nbytes = self.lib.bcn_snapshot_bytes(self.h)
+            out = Snapshot(torch.zeros((nbytes,), dtype=torch.uint8, device=self.device), self._snap_meta())
+        else:
+            self._check_snap(out, "snapshot(out=)")
+            if out.batch != self.batch:
+                raise ValueError("snapshot(out=): out holds %d replicas, this env %d" % (out.batch, self.batch))
+        self._snap_volatile(out.meta)
+        if self._ops is not None:
+            self._ops["snapshot_save"](self.h.value, out.buf, self.out_buf)
+        else:
+            _lib.check(self.lib.bcn_snapshot_save(self.h, _ptr(out.buf), _ptr(self.out_buf), self._stream()))
+        return out
+
+    def restore(self, snap, src=None, mask=None):
+        """Load replicas from a Snapshot of the same signature: replica b takes replica src[b] of `snap` (src None: b, which needs
+        snap.batch == batch) where mask[b] is nonzero (None: everywhere); the others keep state, counters and output rows.  ONE
+        launch on the current stream.  Returns (obs, rwd, done, trunc) as they were when the snapshot was taken (gathered); the
+        env's obs / rwd / done / trunc / status hold them (with double_buffer(): the current buffer).
+        Raises ValueError on the host, before any launch, when the signatures differ, the snapshot lives on another device,
+        src is None and the batches differ, or a `src` given as a list / array / CPU tensor holds an index outside [0, snap.batch).
+        A `src` that is a device tensor is not read on the host; the kernel leaves replicas with an index out of range untouched.
+        The noise sigma, seed and replica_offset are kernel arguments: restore does not change them (meta["noise"] records those
+        of the source).  The env's torch generator `gen` is set back on an identity restore (src and mask None) only."""
+        self._check_snap(snap, "restore")
+        if src is None:
+            if snap.batch != self.batch:
+                raise ValueError("restore: the snapshot holds %d replicas, this env %d: pass src" % (snap.batch, self.batch))
+        else:
+            if not torch.is_tensor(src) or src.device.type != "cuda":
+                host = np.asarray(src.numpy() if torch.is_tensor(src) else src)
+                if host.shape != (self.batch,) or not np.issubdtype(host.dtype, np.integer):
+                    raise ValueError("restore: src must hold %d integers" % self.batch)
+                if host.size and (host.min() < 0 or host.max() >= snap.batch):
+                    raise ValueError("restore: src holds an index outside [0, %d)" % snap.batch)
+                src = torch.as_tensor(host.astype(np.int32))
+            if src.numel() != self.batch:
+                raise ValueError("restore: src must hold %d integers" % self.batch)
+            if src.device != self.device or src.dtype != torch.int32 or not src.is_contiguous():
+                src = src.to(device=self.device, dtype=torch.int32).reshape(self.batch).contiguous()
+        if mask is not None:
+            if not torch.is_tensor(mask):
+                mask = torch.as_tensor(np.asarray(mask))
+            if mask.numel() != self.batch:
+                raise ValueError("restore: mask must hold %d values" % self.batch)
+            if mask.device != self.device or mask.dtype != torch.uint8 or not mask.is_contiguous():
+                mask = mask.to(device=self.device, dtype=torch.uint8).reshape(self.batch).contiguous()
+        self._keep_restore = (src, mask)
+        if self._ops is not None:
+            self._ops["snapshot_load"](self.h.value, snap.buf, snap.batch, src, mask, self.out_buf)
+        else:
+            _lib.check(self.lib.bcn_snapshot_load(self.h, _ptr(snap.buf), snap.batch, _ptr(src), _ptr(mask), _ptr(self.out_buf),
+                                                  self._stream()))
+        gen = getattr(self, "gen", None)
+        if (gen is not None and src is None and mask is None and snap.meta.get("gen_state") is not None
+                and not torch.cuda.is_current_stream_capturing()):
+            gen.set_state(snap.meta["gen_state"])
+        return self.obs, self.rwd, self.done, self.trunc
+
+    def fork(self, src, mask=None):
+        """replica b <- replica src[b] of THIS env (where mask[b] is nonzero): a snapshot() into a scratch Snapshot the env keeps
+        and reuses, then a restore() from it -- two launches, nothing allocated after the first call; any src (permutations,
+        duplicates) is safe because source and destination are different buffers.  What planning by shooting (copy the current
+        state into B candidates), population-based training (overwrite the worst with the best) and resets from a developed
+        replica need.  Device noise (burgers, shkadov; step() without `noise`): the draw counter is copied from the source but the
+        Philox counter is keyed by the replica's OWN global index, so copies of one source draw different noise from then on --
+        what exploration wants; identical continuations need an explicit `noise` tensor."""
+        scratch = getattr(self, "_fork_snap", None)
+        if scratch is not None and scratch.signature != self.snapshot_signature():
+            scratch = None
+        self._fork_snap = self.snapshot(out=scratch)
+        return self.restore(self._fork_snap, src, mask)
 
     def get_stp(self):
         buf = (C.c_int32 * self.batch)()
@@ -596,6 +771,7 @@ class VecBurgers(VecEnv):
     def __init__(self, batch, device="cuda:0", dtype="f32", u_target=0.5, amp=10.0, sigma=0.1,
                  ctrl_pos=1.0, L=2.0, nx=500, seed=0):
         self._derive(u_target, amp, sigma, ctrl_pos, L, nx)
+        self._ctor = dict(u_target=u_target, amp=amp, sigma=sigma, ctrl_pos=ctrl_pos, L=L, nx=nx, seed=seed)
         self.seed, self.replica_offset = int(seed), 0
         super().__init__(batch, device, dtype)
         self._make_spaces()
@@ -661,6 +837,7 @@ class VecShkadov(VecEnv):
     def __init__(self, batch, device="cuda:0", dtype="f32", init_fields=None, L0=150.0, n_jets=5,
                  jet_pos=150.0, jet_space=10.0, delta=0.1, t_act=20.0, seed=0):
         self._derive(L0, n_jets, jet_pos, jet_space, delta, t_act)
+        self._ctor = dict(L0=L0, n_jets=n_jets, jet_pos=jet_pos, jet_space=jet_space, delta=delta, t_act=t_act, seed=seed)
         self._init_np = None if init_fields is None else np.asarray(init_fields, dtype=np.float64)
         self.seed, self.replica_offset = int(seed), 0
         super().__init__(batch, device, dtype)
@@ -751,6 +928,7 @@ class VecSloshing(VecEnv):
     def __init__(self, batch, device="cuda:0", dtype="f32", init_fields=None, L=2.5, amp=5.0,
                  alpha=0.0005, g=9.81):
         self._derive(L, amp, alpha, g)
+        self._ctor = dict(L=L, amp=amp, alpha=alpha, g=g)
         self._init_np = None if init_fields is None else np.asarray(init_fields, dtype=np.float64)
         super().__init__(batch, device, dtype)
         self._make_spaces()
@@ -813,6 +991,7 @@ class VecLorenz(VecEnv):
 
     def __init__(self, batch, device="cuda:0", dtype="f32", sigma=10.0, rho=28.0, beta=8.0 / 3.0):
         self._derive(sigma, rho, beta)
+        self._ctor = dict(sigma=sigma, rho=rho, beta=beta)
         super().__init__(batch, device, dtype)
         self._make_spaces()
 
@@ -862,6 +1041,7 @@ class VecVortex(VecEnv):
 
     def __init__(self, batch, device="cuda:0", dtype="f32", re=50.0, weight=50.0):
         self._derive(re, weight)
+        self._ctor = dict(re=re, weight=weight)
         super().__init__(batch, device, dtype)
         self._make_spaces()
 

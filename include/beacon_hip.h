@@ -345,6 +345,56 @@ BCN_API int bcn_get_slow_mode_bound(bcn_env_t h, double* cutoff, double* bound);
  * lpt_min_batch = smallest batch that mode 1 splits (0 = CUs + 1).  Results do not depend on the mode.  BCN_ERR_ARG for lorenz
  * and vortex (one lane per replica, nothing to schedule). */
 BCN_API int bcn_set_sched(bcn_env_t h, int mode, int grid, int q, int lpt_min_batch);
+/* Snapshots: everything a handle needs to continue an episode bit for bit, for all its replicas, as ONE device byte buffer
+ * (no reference counterpart beyond dump()/load() of the fields, rayleigh.py:344-362: SURVEY.md 5 lists resume as missing there).
+ * bcn_get_state carries the solver fields only; a snapshot adds what the next *_step also reads -- the observation history, the
+ * stored action that actions_dev = NULL repeats and the 1D envs' action ramp starts from, the episode counter, the draw counter
+ * of the device noise -- and the packed outputs of the last call, so that a restored env also shows the observations a policy
+ * needs for its next action.
+ * Layout of a snapshot of n replicas: named segments in the order below, every segment start a multiple of 16 bytes; a segment
+ * is [planes][n][row_elems] elements (no padding between planes or rows), `real` = the handle's dtype:
+ *   rayleigh   fields real [4][n][(ny+2)(nx+2)] = u,v,p,S (per replica x fastest: bcn_get_state's [n][4][..] with the first two
+ *              axes exchanged), obs_hist real [n][n_obs], a_last real [n][n_sgts] (the conditioned action), stp int32 [n]
+ *   mixing     fields, obs_hist as rayleigh, ia_last int32 [n], stp int32 [n]
+ *   burgers    fields real [3][n][nx] = u,up,upp, a_last real [n][1], a_prev real [n][1], stp int32 [n], nctr uint32 [n]
+ *   shkadov    fields real [4][n][nx] = h,q,rhsh,rhsq, a_last / a_prev real [n][n_jets], stp, nctr
+ *   sloshing   fields real [4][n][nx+2], a_last / a_prev real [n][1], stp, nctr
+ *   lorenz     fields real [7][n][1] = x0,x1,x2, fx0,fx1,fx2, t, iu int32 [n] (the action index), stp
+ *   vortex     fields real [14][n][1] (the columns of bcn_get_state), stp
+ *   all        obs real [n][n_obs], rwd real [n], status int32 [n], done uint8 [n], trunc uint8 [n]
+ * bcn_snapshot_layout writes these as (name, byte offset, element type, planes, row_elems) and returns their number (at most 16;
+ * only the first max_segs are written); bcn_snapshot_bytes_n is the size (a multiple of 16) and bcn_snapshot_bytes that of the
+ * handle's own batch.  What is NOT in it, because every *_step rewrites it before reading it: us / vs and the work arrays of the 2D
+ * envs, their field scratch, sweep counts, scheduler block and cycle counters.  Kernel arguments are not state either: noise sigma,
+ * seed and replica offset (bcn_set_noise), options, the kernel variant, the replica mask.
+ * bcn_snapshot_signature: a hash of env kind, dtype, every value of the cfg struct the handle was CREATED from and the segment
+ * shapes -- two handles exchange snapshots exactly when it is equal; the batch is not part of it.  What is set on a handle after
+ * its creation (options, variant, noise, slow-mode bounds) is not hashed: none of it changes what the bytes mean.
+ * out_buf_dev: the caller's packed output buffer of the handle's batch B, [obs | rwd | status | done | trunc] with every part
+ * starting at a multiple of 16 bytes (obs at 0; B n_obs reals, B reals, B int32, B uint8, B uint8); NULL leaves the five output
+ * segments out of the copy.  snap_dev and out_buf_dev must be 16-byte aligned.
+ * bcn_snapshot_save: handle -> snap_dev (bcn_snapshot_bytes(h) bytes), every replica, the replica mask ignored.
+ * bcn_snapshot_load: snap_dev holds n_src replicas; replica b of the handle takes replica src_dev[b] (int32[B] on the device; NULL =
+ * b, which needs n_src == B) where mask_dev[b] != 0 (uint8[B], NULL = all; the mask of bcn_set_mask plays no part).  A replica whose
+ * index lies outside [0, n_src) is left untouched like a masked one: no address is formed from it.  snap_dev must not alias the
+ * handle's arrays or out_buf_dev (a gather inside one handle is a save followed by a load).
+ * Both are ONE kernel launch on `stream` -- no host synchronisation, no host read, no allocation -- so they can be captured into a
+ * graph next to *_step. */
+enum { BCN_SNAP_REAL = 0, BCN_SNAP_I32 = 1, BCN_SNAP_U32 = 2, BCN_SNAP_U8 = 3 };
+typedef struct {
+  char name[16];
+  uint64_t offset;                /* bytes from the start of the snapshot, a multiple of 16 */
+  int32_t elem;                   /* BCN_SNAP_* */
+  int32_t planes;
+  int64_t row_elems;
+} bcn_snapshot_seg;
+BCN_API size_t bcn_snapshot_bytes(bcn_env_t h);
+BCN_API size_t bcn_snapshot_bytes_n(bcn_env_t h, int n);
+BCN_API int bcn_snapshot_layout(bcn_env_t h, int n, bcn_snapshot_seg* segs, int max_segs);
+BCN_API uint64_t bcn_snapshot_signature(bcn_env_t h);
+BCN_API int bcn_snapshot_save(bcn_env_t h, void* snap_dev, const void* out_buf_dev, void* stream);
+BCN_API int bcn_snapshot_load(bcn_env_t h, const void* snap_dev, int n_src, const int32_t* src_dev, const uint8_t* mask_dev,
+                              void* out_buf_dev, void* stream);
 /* name of the kernel the last *_step dispatched, e.g. "ns2d_fast_sched" (before the first step: the
  * variant's plain kernel); for profiles */
 BCN_API const char* bcn_kernel_name(bcn_env_t h);
