@@ -131,6 +131,11 @@ SIGNATURES = {
     "bcn_snapshot_signature": (C.c_uint64, [vp]),
     "bcn_snapshot_save": (C.c_int, [vp, vp, vp, vp]),
     "bcn_snapshot_load": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp]),
+    "bcn_n_params": (C.c_int, [vp]),
+    "bcn_param_name": (C.c_char_p, [vp, C.c_int]),
+    "bcn_set_params": (C.c_int, [vp, C.POINTER(C.c_double), vp]),
+    "bcn_get_params": (C.c_int, [vp, C.POINTER(C.c_double)]),
+    "bcn_derive_params_host": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "bcn_kernel_name": (C.c_char_p, [vp]),
     "bcn_destroy": (C.c_int, [vp]),
     "bcn_last_error": (C.c_char_p, []),

@@ -66,7 +66,7 @@ struct bcn_env_s {
   int n_act = 0;
   int variant = 0;
   size_t esz = 4;
-  virtual ~bcn_env_s() {}
+  virtual ~bcn_env_s() { delete[] prm_host; }
   virtual size_t state_elems() const = 0;
   virtual int get_state(void* buf, int is_device, hipStream_t s) = 0;
   virtual int set_state(const void* buf, int is_device, hipStream_t s) = 0;
@@ -81,6 +81,12 @@ struct bcn_env_s {
   virtual int get_counters(uint64_t* host, hipStream_t) { memset(host, 0, (size_t)batch * 4 * sizeof(uint64_t)); return BCN_OK; }   // only the 2D register-resident kernels schedule
   virtual const char* kernel_name() const = 0;
   virtual void note_kernel(const char*) {}   // 1D envs: the step kernel the launcher chose (packed or general)
+  // per-replica physical parameters (bcn_set_params; params.h)
+  virtual void use_params(const void* table) = 0;   // the kernels read `table` from the next launch on (nullptr: the argument block's values)
+  void* prm_dev = nullptr;      // [n_derived][B] in the handle's dtype: allocated by the first bcn_set_params, never moved (freed by bcn_destroy)
+  double* prm_host = nullptr;   // [n_params][B], the values in force; nullptr: none set (every replica has the cfg's)
+  double prm_cfg[3] = {0, 0, 0};   // the cfg's values of the parameters, in the order of bcn_param_name
+  double prm_aux[2] = {0, 0};      // what else of the cfg the derived constants need (params.h: bcn_derive_params)
   int32_t* stp = nullptr;  // device int32[B]
   int ndt_act = 0;         // timesteps per action step (rows of the callers' sweeps / noise buffers: bcn_ndt_act)
 };

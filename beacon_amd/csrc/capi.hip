@@ -11,6 +11,7 @@
 #include "env1d.h"
 #include "ns2d.h"
 #include "ode_env.h"
+#include "params.h"
 #include "snapshot.h"
 
 thread_local const char* bcn_env1d_launched = nullptr;   // env1d.h: set by the 1D launchers
@@ -228,11 +229,17 @@ struct NS2DEnv : bcn_env_s {
     return BCN_OK;
   }
   NS2DHost host;   // launcher-side state: kernel name of the last step, options that no kernel reads
+  // per-replica parameters (bcn_set_params): the table is an argument of the generic kernel alone, so a handle that has one steps
+  // through it whatever its variant; clearing the table restores the previous dispatch
+  const real* prm = nullptr;
+  void use_params(const void* table) override { prm = static_cast<const real*>(table); host.launched = nullptr; }
   const char* kernel_name() const override {
+    if (prm) return "ns2d_generic_step";
     return host.launched ? host.launched : (variant == 1 ? "ns2d_fast_step" : "ns2d_generic_step");
   }
   int launch(hipStream_t s) {
     a.host = &host;
+    if (prm) return ns2d_launch_generic_prm<real>(a, batch, s, prm);
     if (variant == 1 && plugin) {
       // BCN_ERR_UNSUPPORTED: the batch does not fit the plugin's addressing (ns2d_fast4_impl.h: 32-bit offsets from a
       // replica's u): the generic kernel takes the step
@@ -268,8 +275,9 @@ int make_rayleigh(const bcn_rayleigh_cfg* c, int batch, int dtype, int device, b
   a.n_sgts = c->n_sgts; a.nx_sgts = c->nx_sgts;
   a.nxo = c->nx_obs_pts; a.nyo = c->ny_obs_pts; a.nx_obs = c->nx_obs; a.ny_obs = c->ny_obs;
   a.n_obs_steps = c->n_obs_steps; a.n_obs = 3 * c->n_obs_steps * c->nx_obs_pts * c->ny_obs_pts;
-  a.kmom = (real)sqrt(c->pr / c->ra);
-  a.ksc = (real)(1.0 / sqrt(c->pr * c->ra));
+  a.kmom = (real)bcn_rayleigh_kmom(c->pr, c->ra);
+  a.ksc = (real)bcn_rayleigh_ksc(c->pr, c->ra);
+  e->prm_cfg[0] = c->ra; e->prm_aux[0] = c->pr;
   a.Tc = (real)c->Tc; a.Th = (real)c->Th; a.C = (real)c->C;
   a.rwd_scale = (real)(1.0 / (0.5 * c->dy * c->nx));
   e->n_obs = a.n_obs; e->n_act = c->n_sgts; e->ndt_act = a.ndt_act;
@@ -292,9 +300,10 @@ int make_mixing(const bcn_mixing_cfg* c, int batch, int dtype, int device, bcn_e
   a.nxo = c->nx_obs_pts; a.nyo = c->ny_obs_pts; a.nx_obs = c->nx_obs; a.ny_obs = c->ny_obs;
   a.n_obs_steps = c->n_obs_steps; a.n_obs = 3 * c->n_obs_steps * c->nx_obs_pts * c->ny_obs_pts;
   a.i_min = c->i_min; a.i_max = c->i_max; a.j_min = c->j_min; a.j_max = c->j_max;
-  a.kmom = (real)(1.0 / c->re);
-  a.ksc = (real)(1.0 / c->pe);
-  a.u_max = (real)c->u_max; a.ref_c = (real)c->ref_c; a.C0 = (real)c->C0;
+  a.kmom = (real)bcn_mixing_kmom(c->re);
+  a.ksc = (real)bcn_mixing_ksc(c->pe);
+  e->prm_cfg[0] = c->re; e->prm_cfg[1] = c->pe; e->prm_aux[0] = c->re; e->prm_aux[1] = c->u_max;
+  a.u_max = (real)bcn_mixing_u_max(c->re, c->re, c->u_max); a.ref_c = (real)c->ref_c; a.C0 = (real)c->C0;
   e->n_obs = a.n_obs; e->n_act = 1; e->ndt_act = a.ndt_act;
   e->cfg_hash = snap_cfg_hash<bcn_mixing_cfg, 14, 9>(c);
   int rc = e->init();
@@ -371,6 +380,7 @@ struct Env1D : bcn_env_s {
   const char* kernel_name() const override { return kname; }
   void note_kernel(const char* n) override { kname = n; }
   void set_mask(const uint8_t* m) override { a.mask = m; }
+  void use_params(const void* table) override { a.prm = static_cast<const real*>(table); }
   int set_option(const char* name, int value) override {
     if (!strcmp(name, "cells_per_thread") && (value == 0 || value == 1 || value == 2 || value == 4 || value == 8)) { a.force_k = value; return BCN_OK; }
     if (!strcmp(name, "one_wave") && value >= 0 && value <= 2) { a.one_wave = value; return BCN_OK; }   // 2: without the packed float32 kernel
@@ -388,6 +398,7 @@ int make_burgers(const bcn_burgers_cfg* c, int batch, int dtype, int device, bcn
   a.n = a.nx = c->nx; a.ndt_act = c->ndt_act; a.n_act = c->n_act; a.n_obs = c->n_obs_pts;
   a.ctrl_pos = c->ctrl_pos; a.n_obs_pts = c->n_obs_pts;
   a.u_target = (real)c->u_target; a.amp = (real)c->amp;
+  e->prm_cfg[0] = c->u_target; e->prm_cfg[1] = c->amp;
   a.dx = (real)c->dx; a.rdx = (real)(1.0 / c->dx); a.dt = (real)c->dt;
   e->n_obs = c->n_obs_pts; e->n_act = 1; e->ndt_act = a.ndt_act;
   e->cfg_hash = snap_cfg_hash<bcn_burgers_cfg, 5, 4>(c);
@@ -408,7 +419,8 @@ int make_shkadov(const bcn_shkadov_cfg* c, int batch, int dtype, int device, bcn
   a.n_jets = c->n_jets; a.jet_pos = c->jet_pos; a.jet_hw = c->jet_hw; a.jet_space = c->jet_space;
   a.l_obs = c->l_obs; a.l_rwd = c->l_rwd; a.n_obs_jet = c->n_obs; a.obs_stride = c->obs_stride;
   a.n_interp = c->n_interp;
-  a.delta_p = (real)(1.0 / (5.0 * c->delta));
+  a.delta_p = (real)bcn_shkadov_delta_p(c->delta);
+  e->prm_cfg[0] = c->delta;
   a.jet_amp = (real)c->jet_amp; a.eps = (real)c->eps; a.h_blow = (real)c->h_blow;
   a.blowup_rwd = (real)c->blowup_rwd;
   a.dx = (real)c->dx; a.rdx = (real)(1.0 / c->dx); a.dt = (real)c->dt;
@@ -431,6 +443,7 @@ int make_sloshing(const bcn_sloshing_cfg* c, int batch, int dtype, int device, b
   a.n_obs = c->nx / 2 + (c->nx % 2 ? 1 : 0);
   a.n_interp = c->n_interp;
   a.g = (real)c->g; a.amp = (real)c->amp; a.alpha = (real)c->alpha;
+  e->prm_cfg[0] = c->amp; e->prm_cfg[1] = c->alpha; e->prm_cfg[2] = c->g;
   a.dx = (real)c->dx; a.rdx = (real)(1.0 / c->dx); a.dt = (real)c->dt;
   e->n_obs = a.n_obs; e->n_act = 1; e->ndt_act = a.ndt_act;
   e->cfg_hash = snap_cfg_hash<bcn_sloshing_cfg, 4, 5>(c);
@@ -500,6 +513,7 @@ struct OdeEnv : bcn_env_s {
     return bcn_env_s::set_option(name, value);
   }
   void set_mask(const uint8_t* m) override { a.mask = m; }
+  void use_params(const void* table) override { a.prm = static_cast<const real*>(table); }
   const char* kernel_name() const override { return kind == BCN_LORENZ ? "lorenz_step_k" : "vortex_step_k"; }
 };
 
@@ -512,6 +526,7 @@ int make_lorenz(const bcn_lorenz_cfg* c, int batch, int dtype, int device, bcn_e
   OdeArgs<real>& a = e->a;
   a.kind = BCN_LORENZ; a.ndt_act = c->ndt_act; a.n_act = c->n_act;
   a.dt = (real)c->dt; a.sigma = (real)c->sigma; a.rho = (real)c->rho; a.beta = (real)c->beta;
+  e->prm_cfg[0] = c->sigma; e->prm_cfg[1] = c->rho; e->prm_cfg[2] = c->beta;
   e->n_obs = 6; e->n_act = 1; e->ndt_act = c->ndt_act;
   e->cfg_hash = snap_cfg_hash<bcn_lorenz_cfg, 2, 4>(c);
   int rc = e->init();
@@ -532,7 +547,8 @@ int make_vortex(const bcn_vortex_cfg* c, int batch, int dtype, int device, bcn_e
   a.lmbda_re = (real)c->lmbda_re; a.lmbda_cx = (real)c->lmbda_cx; a.mu_re = (real)c->mu_re; a.mu_cx = (real)c->mu_cx;
   a.alpha_re = (real)c->alpha_re; a.alpha_cx = (real)c->alpha_cx;
   // the derived constants of vortex.py:26-42, in double and in the reference's order
-  a.ire = (real)(1.0 / c->re_crit - 1.0 / c->re);
+  a.ire = (real)bcn_vortex_ire(c->re_crit, c->re);
+  e->prm_cfg[0] = c->re; e->prm_cfg[1] = c->weight; e->prm_aux[0] = c->re_crit;
   a.omega_f = (real)c->omega_f;
   a.m_omega_f_gamma = (real)(-c->omega_f * c->gamma);
   a.domega = (real)(c->omega_s - c->omega_f);
@@ -709,6 +725,22 @@ int snap_build(bcn_env_t h, int n, char* out_buf, SnapTable* t, bcn_snapshot_seg
   if (bytes) *bytes = snap_up16(off);
   if (t) { t->nseg = ns; t->batch = h->batch; t->n_src = n; t->nblk = (unsigned)blk; }
   return nd;
+}
+
+// bcn_set_params: the table of derived constants of every replica, narrowed once to the handle's dtype, row k of replica b at
+// [k * B + b]
+template <typename real>
+void params_table(bcn_env_t h, const double* values, std::vector<char>& out) {
+  const BcnParamDesc* d = bcn_param_desc(h->kind);
+  const size_t B = (size_t)h->batch;
+  out.resize((size_t)d->n_derived * B * sizeof(real));
+  real* t = reinterpret_cast<real*>(out.data());
+  for (size_t b = 0; b < B; b++) {
+    double p[BCN_MAX_PARAMS] = {0, 0, 0}, dv[BCN_MAX_PARAMS] = {0, 0, 0};
+    for (int k = 0; k < d->n; k++) p[k] = values[(size_t)k * B + b];
+    bcn_derive_params(h->kind, p, h->prm_aux, dv);
+    for (int k = 0; k < d->n_derived; k++) t[(size_t)k * B + b] = (real)dv[k];
+  }
 }
 
 }  // namespace
@@ -981,6 +1013,67 @@ int bcn_set_sched(bcn_env_t h, int mode, int grid, int q, int lpt_min_batch) {
   if (mode < -1 || mode > 2 || grid < 0 || q < 0 || lpt_min_batch < 0) { bcn_set_error("bcn_set_sched: argument out of range"); return BCN_ERR_ARG; }
   return h->set_sched(mode, grid, q, lpt_min_batch);
 }
+// ---- per-replica physical parameters ---------------------------------------------------------
+int bcn_n_params(bcn_env_t h) {
+  const BcnParamDesc* d = h ? bcn_param_desc(h->kind) : nullptr;
+  return d ? d->n : 0;
+}
+const char* bcn_param_name(bcn_env_t h, int i) {
+  const BcnParamDesc* d = h ? bcn_param_desc(h->kind) : nullptr;
+  return d && i >= 0 && i < d->n ? d->name[i] : "";
+}
+int bcn_set_params(bcn_env_t h, const double* values_host, void* stream) {
+  const BcnParamDesc* d = h ? bcn_param_desc(h->kind) : nullptr;
+  if (!d) { bcn_set_error("bcn_set_params: null handle"); return BCN_ERR_ARG; }
+  if (!values_host) {   // back to the cfg's values for every replica; the table stays allocated (a captured graph may hold its address)
+    delete[] h->prm_host;
+    h->prm_host = nullptr;
+    h->use_params(nullptr);
+    return BCN_OK;
+  }
+  const size_t B = (size_t)h->batch;
+  // everything is checked before the device or the handle is touched
+  for (int k = 0; k < d->n; k++)
+    for (size_t b = 0; b < B; b++) {
+      const double v = values_host[(size_t)k * B + b];
+      if (!isfinite(v)) { bcn_set_error("bcn_set_params: %s of replica %zu is not finite (%g)", d->name[k], b, v); return BCN_ERR_ARG; }
+      if (d->positive[k] && !(v > 0.0)) { bcn_set_error("bcn_set_params: %s of replica %zu must be > 0 (%g)", d->name[k], b, v); return BCN_ERR_ARG; }
+    }
+  std::vector<char> table;
+  if (h->dtype == BCN_F32) params_table<float>(h, values_host, table);
+  else params_table<double>(h, values_host, table);
+  double* keep = new (std::nothrow) double[(size_t)d->n * B];
+  if (!keep) { bcn_set_error("out of host memory"); return BCN_ERR_ARG; }
+  memcpy(keep, values_host, (size_t)d->n * B * sizeof(double));
+  DeviceGuard g(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (!h->prm_dev) {
+    hipError_t e = hipMalloc(&h->prm_dev, table.size());
+    if (e != hipSuccess) { delete[] keep; h->prm_dev = nullptr; bcn_set_error("hipMalloc(%zu): %s", table.size(), hipGetErrorString(e)); return BCN_ERR_HIP; }
+  }
+  // in place, in stream order: a graph captured after the first call reads the new values at its next replay
+  hipError_t e = hipMemcpyAsync(h->prm_dev, table.data(), table.size(), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);   // `table` is a temporary
+  if (e != hipSuccess) { delete[] keep; bcn_set_error("bcn_set_params: copy to the device: %s", hipGetErrorString(e)); return BCN_ERR_HIP; }
+  delete[] h->prm_host;
+  h->prm_host = keep;
+  h->use_params(h->prm_dev);
+  return BCN_OK;
+}
+int bcn_get_params(bcn_env_t h, double* values_host) {
+  const BcnParamDesc* d = h ? bcn_param_desc(h->kind) : nullptr;
+  if (!d || !values_host) { bcn_set_error("bcn_get_params: null handle/buffer"); return BCN_ERR_ARG; }
+  const size_t B = (size_t)h->batch;
+  for (int k = 0; k < d->n; k++)
+    for (size_t b = 0; b < B; b++) values_host[(size_t)k * B + b] = h->prm_host ? h->prm_host[(size_t)k * B + b] : h->prm_cfg[k];
+  return BCN_OK;
+}
+int bcn_derive_params_host(int kind, const double* params, const double* aux, double* derived) {
+  const BcnParamDesc* d = bcn_param_desc(kind);
+  if (!d || !params || !aux || !derived) { bcn_set_error("bcn_derive_params_host: unknown kind or null array"); return -1; }
+  bcn_derive_params(kind, params, aux, derived);
+  return d->n_derived;
+}
 // ---- snapshots -------------------------------------------------------------------------------
 size_t bcn_snapshot_bytes_n(bcn_env_t h, int n) {
   size_t bytes = 0;
@@ -1037,6 +1130,7 @@ int bcn_destroy(bcn_env_t h) {
   {
     DeviceGuard g(h->device);
     (void)hipDeviceSynchronize();
+    if (h->prm_dev) (void)hipFree(h->prm_dev);
   }
   delete h;
   return BCN_OK;

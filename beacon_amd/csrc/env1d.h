@@ -35,6 +35,9 @@ struct Env1DArgs {
   uint32_t* nctr;           // [B] steps taken with device noise (advanced by the kernel: a captured graph replays fresh noise)
   const real* init_fields;
   const uint8_t* mask;      // per-replica enable (NULL = all)
+  // per-replica physical parameters (bcn_set_params): [k][B], burgers u_target, amp / shkadov delta_p / sloshing amp, alpha, g;
+  // NULL: the values above for every replica.  Every kernel overwrites those fields of its own copy of this block at entry.
+  const real* prm;
   real* obs_out;
   real* rwd_out;
   uint8_t* done;

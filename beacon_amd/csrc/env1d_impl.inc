@@ -72,6 +72,23 @@ template <> __device__ __forceinline__ float vanleer<float>(float a, float b) {
 template <typename real> __device__ __forceinline__ real fsqrt(real a) { return sqrt(a); }
 template <> __device__ __forceinline__ float fsqrt<float>(float a) { return __builtin_amdgcn_sqrtf(a); }
 
+// Per-replica physical parameters (bcn_set_params).  One workgroup is one replica (blockIdx.x of gridDim.x), so its parameters are
+// wave-uniform: at entry, before any store, a kernel overwrites the fields of ITS OWN by-value copy of the argument block from the
+// table [k][B] -- scalar loads into the scalar registers the kernel arguments would have occupied -- and every use site below reads
+// A.u_target, A.amp, A.delta_p, A.g, A.alpha as before.
+template <typename real>
+__device__ __forceinline__ void burgers_params(Env1DArgs<real>& A) {
+  if (A.prm) { const size_t B = gridDim.x; const real* __restrict__ p = A.prm + blockIdx.x; A.u_target = p[0]; A.amp = p[B]; }
+}
+template <typename real>
+__device__ __forceinline__ void shkadov_params(Env1DArgs<real>& A) {
+  if (A.prm) A.delta_p = A.prm[blockIdx.x];
+}
+template <typename real>
+__device__ __forceinline__ void sloshing_params(Env1DArgs<real>& A) {
+  if (A.prm) { const size_t B = gridDim.x; const real* __restrict__ p = A.prm + blockIdx.x; A.amp = p[0]; A.alpha = p[B]; A.g = p[2 * B]; }
+}
+
 template <typename real, int NT>
 __device__ __forceinline__ void finish(const Env1DArgs<real>& A, int b, real rwd, bool blow, real blow_rwd,
                                        bool blow_overrides_rwd) {
@@ -109,6 +126,7 @@ __device__ real burgers_obs_rwd(const Env1DArgs<real>& A, int b, real* red) {
 template <typename real, int K, int NT, bool FIT = false>
 __global__ __launch_bounds__(NT) void burgers_step_k(Env1DArgs<real> A) {
   if (A.mask && !A.mask[blockIdx.x]) return;
+  burgers_params(A);
   static_assert(!FIT || NT == 64, "FIT: one wave");
   // NT == 64: the replica is ONE wave -- its halo cells come from the neighbouring lanes by DPP wave shifts, and a
   // timestep needs neither LDS nor a barrier (B = 1024 replicas of 512 cells: 57 -> ~25 us per action step)
@@ -260,6 +278,7 @@ __global__ __launch_bounds__(NT) void burgers_step_k(Env1DArgs<real> A) {
 template <int K, bool FIT>
 __global__ __launch_bounds__(64) void burgers_step_pk_k(Env1DArgs<float> A) {
   if (A.mask && !A.mask[blockIdx.x]) return;
+  burgers_params(A);
   static_assert(K == 8 || K == 4, "pairs (k, k + K/2), vector loads of K/2 cells");
   constexpr int H = K / 2;
   typedef float fH __attribute__((ext_vector_type(H)));
@@ -413,6 +432,7 @@ __global__ __launch_bounds__(64) void burgers_step_pk_k(Env1DArgs<float> A) {
 template <typename real, int NT>
 __global__ __launch_bounds__(NT) void burgers_reset_k(Env1DArgs<real> A) {
   if (A.mask && !A.mask[blockIdx.x]) return;
+  burgers_params(A);
   __shared__ real red[NT / BCN_WAVE];
   const int b = blockIdx.x, n = A.n;
   for (int c = threadIdx.x; c < n; c += NT) {
@@ -460,6 +480,7 @@ __device__ real shkadov_obs_rwd(const Env1DArgs<real>& A, int b, real* red, bool
 template <typename real, int K, int NT>
 __global__ __launch_bounds__(NT) void shkadov_step_k(Env1DArgs<real> A) {
   if (A.mask && !A.mask[blockIdx.x]) return;
+  shkadov_params(A);
   constexpr int NB = (4 * NT * K * sizeof(real) <= 65536) ? 2 : 1;
   __shared__ __attribute__((aligned(8))) real lh[NB][NT * K + 8];   // + 8: guard words around the two halves of the interleaved layout (lidx
   __shared__ __attribute__((aligned(8))) real lq[NB][NT * K + 8];   //      below), one of them the slot holding 1 for reads outside the array
@@ -876,6 +897,7 @@ __global__ __launch_bounds__(NT) void shkadov_step_k(Env1DArgs<real> A) {
 template <typename real, int NT>
 __global__ __launch_bounds__(NT) void shkadov_reset_k(Env1DArgs<real> A) {
   if (A.mask && !A.mask[blockIdx.x]) return;
+  shkadov_params(A);
   __shared__ real red[NT / BCN_WAVE];
   const int b = blockIdx.x, n = A.n;
   for (int c = threadIdx.x; c < n; c += NT) {
@@ -918,6 +940,7 @@ __device__ real sloshing_obs_rwd(const Env1DArgs<real>& A, int b, real ua, real*
 template <typename real, int K, int NT>
 __global__ __launch_bounds__(NT) void sloshing_step_k(Env1DArgs<real> A) {
   if (A.mask && !A.mask[blockIdx.x]) return;
+  sloshing_params(A);
   constexpr bool ONEWAVE = (NT == 64);   // one wave per replica: halos by DPP wave shifts, no LDS, no barrier (see burgers)
   constexpr int NB = (4 * NT * K * sizeof(real) <= 65536) ? 2 : 1;
   __shared__ real lh[NB][ONEWAVE ? 1 : NT * K + 1];   // + 1: a slot holding 1 (h) / 0 (q) for reads outside the array
@@ -1052,6 +1075,7 @@ __global__ __launch_bounds__(NT) void sloshing_step_k(Env1DArgs<real> A) {
 template <int K>
 __global__ __launch_bounds__(64) void sloshing_step_pk_k(Env1DArgs<float> A) {
   if (A.mask && !A.mask[blockIdx.x]) return;
+  sloshing_params(A);
   static_assert(K == 4, "pairs (c0, c2), (c1, c3)");
   typedef bcn_f2 f2;
   const int b = blockIdx.x, lane = threadIdx.x, n = A.n, nx = A.nx, i0 = lane * K;
@@ -1168,6 +1192,7 @@ __global__ __launch_bounds__(64) void sloshing_step_pk_k(Env1DArgs<float> A) {
 template <typename real, int NT>
 __global__ __launch_bounds__(NT) void sloshing_reset_k(Env1DArgs<real> A) {
   if (A.mask && !A.mask[blockIdx.x]) return;
+  sloshing_params(A);
   __shared__ real red[NT / BCN_WAVE];
   const int b = blockIdx.x, n = A.n;
   for (int c = threadIdx.x; c < n; c += NT) {

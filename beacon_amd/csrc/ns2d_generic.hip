@@ -20,16 +20,25 @@
 
 #include "ns2d.h"
 #include "ns2d_device.h"
+#include "params.h"
 
 namespace {
 
 
 template <typename real, int NT, bool LDSW>
-__global__ __launch_bounds__(NT) void ns2d_generic_step(NS2DArgs<real> A) {
+__global__ __launch_bounds__(NT) void ns2d_generic_step(NS2DArgs<real> A, const real* __restrict__ prm) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NW = NT / BCN_WAVE;
   const int b = blockIdx.x;
   if (A.mask && !A.mask[b]) return;
+  // per-replica physical parameters (bcn_set_params): this workgroup's copy of the argument block takes its replica's constants
+  // from the table [k][B] before anything is stored (uniform addresses: scalar loads); every use below stays as it is
+  if (prm) {
+    const size_t B = gridDim.x;
+    A.kmom = prm[b];
+    A.ksc = prm[B + b];
+    if (A.kind == 1) A.u_max = prm[2 * B + b];
+  }
   const int tid = threadIdx.x;
   const int tx = tid & (BCN_WAVE - 1), ty = tid >> 6;
   const int nx = A.nx, ny = A.ny, sx = A.sx;
@@ -415,7 +424,7 @@ template <typename real, int NT>
 size_t fixed_lds() { return (2 * (NT / BCN_WAVE) + 64) * sizeof(real); }
 
 template <typename real, int NT>
-int launch_step(const NS2DArgs<real>& a_in, int batch, hipStream_t s) {
+int launch_step(const NS2DArgs<real>& a_in, int batch, hipStream_t s, const real* prm) {
   NS2DArgs<real> a = a_in;
   size_t lds = fixed_lds<real, NT>();
   const size_t work = 3 * (size_t)a.ncell * sizeof(real);
@@ -424,10 +433,10 @@ int launch_step(const NS2DArgs<real>& a_in, int batch, hipStream_t s) {
     lds += work;
     auto k = ns2d_generic_step<real, NT, true>;
     BCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k, dim3(batch), dim3(NT), lds, s, a);
+    hipLaunchKernelGGL(k, dim3(batch), dim3(NT), lds, s, a, prm);
   } else {
     auto k = ns2d_generic_step<real, NT, false>;
-    hipLaunchKernelGGL(k, dim3(batch), dim3(NT), lds, s, a);
+    hipLaunchKernelGGL(k, dim3(batch), dim3(NT), lds, s, a, prm);
   }
   BCN_HIP(hipGetLastError());
   if (a.host) a.host->launched = "ns2d_generic_step";
@@ -443,11 +452,16 @@ size_t ns2d_generic_lds_bytes(int ncell, size_t esz) {
 }
 
 template <typename real>
-int ns2d_launch_generic(const NS2DArgs<real>& a, int batch, hipStream_t s) {
+int ns2d_launch_generic_prm(const NS2DArgs<real>& a, int batch, hipStream_t s, const real* prm) {
   // 16 waves when there is enough work per replica to feed them, else 4 (bcn_set_option "generic_threads": 256 / 1024)
   const int force_nt = a.host ? a.host->generic_nt : 0;
-  if (force_nt == 1024 || (force_nt == 0 && a.nx * a.ny >= 4096)) return launch_step<real, 1024>(a, batch, s);
-  return launch_step<real, 256>(a, batch, s);
+  if (force_nt == 1024 || (force_nt == 0 && a.nx * a.ny >= 4096)) return launch_step<real, 1024>(a, batch, s, prm);
+  return launch_step<real, 256>(a, batch, s, prm);
+}
+
+template <typename real>
+int ns2d_launch_generic(const NS2DArgs<real>& a, int batch, hipStream_t s) {
+  return ns2d_launch_generic_prm<real>(a, batch, s, nullptr);
 }
 
 template <typename real>
@@ -457,6 +471,8 @@ int ns2d_launch_reset(const NS2DArgs<real>& a, int batch, hipStream_t s) {
   return BCN_OK;
 }
 
+template int ns2d_launch_generic_prm<float>(const NS2DArgs<float>&, int, hipStream_t, const float*);
+template int ns2d_launch_generic_prm<double>(const NS2DArgs<double>&, int, hipStream_t, const double*);
 template int ns2d_launch_generic<float>(const NS2DArgs<float>&, int, hipStream_t);
 template int ns2d_launch_generic<double>(const NS2DArgs<double>&, int, hipStream_t);
 template int ns2d_launch_reset<float>(const NS2DArgs<float>&, int, hipStream_t);

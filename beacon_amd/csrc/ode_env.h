@@ -31,6 +31,9 @@ struct OdeArgs {
   int32_t* iu;              // lorenz: [B] last action index
   int32_t* stp;
   const uint8_t* mask;
+  // per-replica physical parameters (bcn_set_params): [3][B] sigma, rho, beta (lorenz) / [2][B] ire, weight (vortex), one more
+  // coalesced column each; NULL: the values above for every replica
+  const real* prm;
   // per call
   const void* actions;      // lorenz int32 [B], vortex real [B][2]; NULL = repeat the stored action
   real* obs_out;            // [B][n_obs], may be NULL on reset
@@ -113,7 +116,8 @@ __global__ __launch_bounds__(BCN_ODE_NT) void lorenz_step_k(OdeArgs<real> A) {
     }
     // self.actions[u] of (-1, 0, 1); an index outside 0..2 applies no force
     const real force = u == 0 ? real(-1) : u == 2 ? real(1) : real(0);
-    const real sigma = A.sigma, rho = A.rho, beta = A.beta, dt = A.dt;
+    const real* prm = A.prm;
+    const real sigma = prm ? prm[b] : A.sigma, rho = prm ? prm[B + b] : A.rho, beta = prm ? prm[2 * B + b] : A.beta, dt = A.dt;
     real f0 = 0, f1 = 0, f2 = 0;
     for (int n = 0; n < A.ndt_act; n++) {
       real k0 = x0, k1 = x1, k2 = x2;
@@ -187,7 +191,9 @@ __global__ __launch_bounds__(BCN_ODE_NT) void vortex_step_k(OdeArgs<real> A) {
     const real kphase = A.phase_min + real(0.5) * (u1 + real(1)) * A.dphase;
     // cos / sin of the phase: the reference evaluates them in every stage; they are the same values
     const real ck = ode_cos(kphase), sk = ode_sin(kphase);
-    const real ire = A.ire, lre = A.lmbda_re, lcx = A.lmbda_cx, mre = A.mu_re, mcx = A.mu_cx, are = A.alpha_re, acx = A.alpha_cx;
+    const real* prm = A.prm;
+    const real ire = prm ? prm[b] : A.ire, weight = prm ? prm[B + b] : A.weight;
+    const real lre = A.lmbda_re, lcx = A.lmbda_cx, mre = A.mu_re, mcx = A.mu_cx, are = A.alpha_re, acx = A.alpha_cx;
     const real mwg = A.m_omega_f_gamma, dw = A.domega, bm = A.beta_m, dt = A.dt;
     real f0 = 0, f1 = 0, f2 = 0, f3 = 0;
     for (int n = 0; n < A.ndt_act; n++) {
@@ -215,7 +221,7 @@ __global__ __launch_bounds__(BCN_ODE_NT) void vortex_step_k(OdeArgs<real> A) {
     real cost = real(2) * kmod * ck * (x0 * c - x1 * s) - real(2) * kmod * sk * (x1 * c + x0 * s);
     cost = real(0.5) * (cost * cost);
     const real dy = (y - yp) / dt;
-    const real r = A.rwd_k * (dy * dy) - A.weight * cost;
+    const real r = A.rwd_k * (dy * dy) - weight * cost;
     st[VX_X * B + b] = x0; st[(VX_X + 1) * B + b] = x1; st[(VX_X + 2) * B + b] = x2; st[(VX_X + 3) * B + b] = x3;
     st[VX_FX * B + b] = f0; st[(VX_FX + 1) * B + b] = f1; st[(VX_FX + 2) * B + b] = f2; st[(VX_FX + 3) * B + b] = f3;
     st[VX_T * B + b] = t; st[VX_Y * B + b] = y;

@@ -50,6 +50,8 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+_POSITIVE_PARAMS = ("ra", "re", "pe", "delta", "g")       # divisors / arguments of roots (include/beacon_hip.h: bcn_set_params)
+
 _OPS = ("rayleigh_reset", "rayleigh_step", "mixing_reset", "mixing_step", "burgers_reset", "burgers_step", "shkadov_reset",
         "shkadov_step", "sloshing_reset", "sloshing_step")
 _ODE_OPS = ("lorenz_reset", "lorenz_step", "vortex_reset", "vortex_step")     # the ODE envs (csrc/ode_env.h)
@@ -119,10 +121,16 @@ class Snapshot(object):
         return snap if device is None else snap.to(device)
 
 
+class ParamsWarning(UserWarning):
+    """A 2D env whose default kernel is a register-resident one received per-replica parameters: it steps through the generic
+    kernel until clear_params() (VecEnv.set_params)."""
+
+
 class VecEnv(object):
     """Common machinery.  Subclasses set self.cfg and implement _create/_reset/_step."""
 
     action_is_int = False
+    PARAMS = ()              # names of the per-replica physical parameters (set_params), in the order of the C ABI's value rows
     needs_noise = False
     _plugin_defs = None      # extra -D flags of this class's on-demand kernels (tests: the deliberately broken plugin)
 
@@ -457,6 +465,79 @@ class VecEnv(object):
             raise RuntimeError("Exceeded max number of iterations in solver (replicas %s)" % bad[:8].tolist())
         return st
 
+    # -- per-replica physical parameters ----------------------------------------------------
+    @property
+    def params(self):
+        """{name: float64 [B] ndarray} of the physical parameters in force, one value per replica (PARAMS of the class; the
+        constructor's values broadcast when set_params was never called or clear_params() undid it)."""
+        n, B = len(self.PARAMS), self.batch
+        buf = np.empty((n, B), dtype=np.float64)
+        _lib.check(self.lib.bcn_get_params(self.h, buf.ctypes.data_as(C.POINTER(C.c_double))))
+        return {name: buf[k].copy() for k, name in enumerate(self.PARAMS)}
+
+    def set_params(self, **cols):
+        """Give every replica its own physics: each keyword is one of PARAMS (the reference's constructor arguments: lorenz sigma,
+        rho, beta; vortex re, weight; burgers u_target, amp; shkadov delta; sloshing amp, alpha, g; rayleigh ra; mixing re, pe) and
+        takes a scalar or a length-B sequence / ndarray / tensor; names not given keep their current per-replica values.
+        ValueError -- before anything is launched or changed -- for an unknown name, a wrong length, a non-finite value or a value
+        <= 0 where the solver divides by it (ra, re, pe, delta, g).
+        Parameters are configuration, like the noise sigma / seed: they take effect at the next reset() / step() and alter no
+        state; they are not part of a Snapshot or of snapshot_signature(), and restore() / fork() move state between replicas
+        while every replica keeps its physics; masks work as before.  A replica whose parameters equal the constructor arguments
+        of another env computes what that env computes, bit for bit (the same kernel reads the same constants).
+        Graphs: the device table keeps its address from the first call on and later calls rewrite it in place, so a graph
+        captured after a set_params replays whatever table is in force at replay time; one captured before the first call keeps
+        the constructor's values.
+        2D envs: only the generic kernel reads the table.  While parameters are set the env steps through ns2d_generic_step
+        (kernel_name says so; the first call warns once with ParamsWarning when that is not the default kernel), and
+        clear_params() restores the previous dispatch."""
+        unknown = [k for k in cols if k not in self.PARAMS]
+        if unknown:
+            raise ValueError("%s.set_params: unknown parameter %s (this env has %s)" % (type(self).__name__, ", ".join(map(repr, unknown)),
+                                                                                     ", ".join(self.PARAMS)))
+        cur, B = self.params, self.batch
+        vals = np.empty((len(self.PARAMS), B), dtype=np.float64)
+        for k, name in enumerate(self.PARAMS):
+            if name not in cols:
+                vals[k] = cur[name]
+                continue
+            v = cols[name]
+            v = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+            v = v.astype(np.float64)
+            if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != B):
+                raise ValueError("%s.set_params: %s has shape %s; a scalar or %d values (one per replica)" % (type(self).__name__, name,
+                                                                                                           tuple(v.shape), B))
+            vals[k] = v
+        for k, name in enumerate(self.PARAMS):
+            bad = ~np.isfinite(vals[k])
+            if name in _POSITIVE_PARAMS:
+                bad |= ~(vals[k] > 0.0)
+            if bad.any():
+                b = int(np.nonzero(bad)[0][0])
+                raise ValueError("%s.set_params: %s of replica %d is %r; it must be finite%s" % (
+                    type(self).__name__, name, b, float(vals[k, b]), " and > 0" if name in _POSITIVE_PARAMS else ""))
+        before = self.kernel_name
+        _lib.check(self.lib.bcn_set_params(self.h, vals.ctypes.data_as(C.POINTER(C.c_double)), self._stream()))
+        self._params = vals                       # re-applied when the handle is rebuilt (set_ndt_act)
+        if before != self.kernel_name and not getattr(self, "_params_warned", False):
+            import warnings
+            self._params_warned = True
+            warnings.warn("%s: per-replica parameters are read by the generic kernel only: this env now steps through %s instead of "
+                          "%s, until clear_params()" % (type(self).__name__, self.kernel_name, before), ParamsWarning, stacklevel=2)
+        return self
+
+    def clear_params(self):
+        """Back to the constructor's parameters for every replica (and, 2D envs, to the kernel that ran before set_params)."""
+        _lib.check(self.lib.bcn_set_params(self.h, None, self._stream()))
+        self._params = None
+        return self
+
+    def _reapply_params(self):
+        """After the handle was rebuilt: the new one takes the table the old one had."""
+        vals = getattr(self, "_params", None)
+        if vals is not None:
+            _lib.check(self.lib.bcn_set_params(self.h, vals.ctypes.data_as(C.POINTER(C.c_double)), self._stream()))
+
     # -- replica masks ----------------------------------------------------------------------
     def _apply_mask(self, mask):
         """mask: None (all replicas) or a [B] bool/uint8 tensor/array; replicas with 0 are skipped
@@ -573,6 +654,8 @@ class VecRayleigh(VecEnv):
     layout (u, v, p, T) -- what load() parses from init_field.dat (:356-362) -- or None
     (init=False: all-zero fields)."""
 
+    PARAMS = ("ra",)
+
     def __init__(self, batch, device="cuda:0", dtype="f32", init_fields=None,
                  L=1.0, H=1.0, n_sgts=10, ra=1.0e4):
         self._derive(L, H, n_sgts, ra)
@@ -633,6 +716,7 @@ class VecRayleigh(VecEnv):
         self.ndt_act = int(n)
         self.h = C.c_void_p()
         self._create()
+        self._reapply_params()
         self.sweeps = torch.zeros((self.batch, self.ndt_act), dtype=torch.int32, device=self.device)
 
     def state_shape(self):
@@ -685,6 +769,8 @@ class VecRayleigh(VecEnv):
 
 class VecMixing(VecEnv):
     """mixing/mixing.py:16-378"""
+
+    PARAMS = ("re", "pe")
 
     action_is_int = True
 
@@ -739,6 +825,7 @@ class VecMixing(VecEnv):
         self.ndt_act = int(n)
         self.h = C.c_void_p()
         self._create()
+        self._reapply_params()
         self.sweeps = torch.zeros((self.batch, self.ndt_act), dtype=torch.int32, device=self.device)
 
     def state_shape(self):
@@ -765,6 +852,8 @@ class VecMixing(VecEnv):
 
 class VecBurgers(VecEnv):
     """burgers/burgers.py:17-227.  `nx` is a kwarg here (a literal 500 in the reference, :26)."""
+
+    PARAMS = ("u_target", "amp")
 
     needs_noise = True
 
@@ -831,6 +920,8 @@ class VecBurgers(VecEnv):
 class VecShkadov(VecEnv):
     """shkadov/shkadov.py:16-372.  `init_fields`: [2, >=nx] (h_init, q_init) as load() parses
     them (:364-368), or None for the flat film h=q=1."""
+
+    PARAMS = ("delta",)
 
     needs_noise = True
 
@@ -925,6 +1016,8 @@ class VecShkadov(VecEnv):
 class VecSloshing(VecEnv):
     """sloshing/sloshing.py:16-320.  `init_fields`: [2, nx+2] (h_init, q_init incl. ghosts)."""
 
+    PARAMS = ("amp", "alpha", "g")
+
     def __init__(self, batch, device="cuda:0", dtype="f32", init_fields=None, L=2.5, amp=5.0,
                  alpha=0.0005, g=9.81):
         self._derive(L, amp, alpha, g)
@@ -987,6 +1080,8 @@ class VecLorenz(VecEnv):
     actions as int32 [B] (force -1, 0, 1), obs = (x, f(x) of the last RK stage), reward 1 while x0 < 0.
     State rows (get_state / set_state): [B, 8] = x0, x1, x2, fx0, fx1, fx2, t, u."""
 
+    PARAMS = ("sigma", "rho", "beta")
+
     action_is_int = True
 
     def __init__(self, batch, device="cuda:0", dtype="f32", sigma=10.0, rho=28.0, beta=8.0 / 3.0):
@@ -1038,6 +1133,8 @@ class VecVortex(VecEnv):
     """vortex/vortex.py:17-283 (the host port: beacon_amd/vortex.py).  One lane per replica (csrc/ode_env.h); Box(-1, 1, (2,))
     actions [B, 2] = (modulus, phase) of the feedback.  State rows (get_state / set_state): [B, 14] = ar, ai, yr, yi,
     fx0..fx3, t, y, kmod, kphase, u0, u1."""
+
+    PARAMS = ("re", "weight")
 
     def __init__(self, batch, device="cuda:0", dtype="f32", re=50.0, weight=50.0):
         self._derive(re, weight)

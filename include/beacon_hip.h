@@ -395,6 +395,34 @@ BCN_API uint64_t bcn_snapshot_signature(bcn_env_t h);
 BCN_API int bcn_snapshot_save(bcn_env_t h, void* snap_dev, const void* out_buf_dev, void* stream);
 BCN_API int bcn_snapshot_load(bcn_env_t h, const void* snap_dev, int n_src, const int32_t* src_dev, const uint8_t* mask_dev,
                               void* out_buf_dev, void* stream);
+/* Per-replica physical parameters.  Every handle is created from ONE cfg; these calls give each replica of the batch its own values
+ * of the reference's constructor arguments (everything else in a cfg -- grids, counts, segment and jet layout, dt, tolerances -- is
+ * structural and stays per handle).  Parameters, in the order of bcn_param_name and of the value rows:
+ *   lorenz    sigma, rho, beta        vortex   re, weight         burgers  u_target, amp      shkadov  delta
+ *   sloshing  amp, alpha, g           rayleigh ra                 mixing   re, pe (the lid speed follows: u_max = re nu / L)
+ * bcn_set_params: values_host is double [n_params][B] on the host (row k = parameter k of every replica); NULL clears them (every
+ * replica has the cfg's values again).  Checked before the handle or the device is touched: every value finite, and ra, re, pe,
+ * delta, g > 0 (divisors, arguments of roots); otherwise BCN_ERR_ARG, and bcn_last_error names the parameter and the replica.  The
+ * constants the kernels read (rayleigh sqrt(pr / ra), 1 / sqrt(pr ra); mixing 1 / re, 1 / pe, u_max; shkadov 1 / (5 delta); vortex
+ * 1 / re_crit - 1 / re) are computed on the host in double by the expressions *_create uses and narrowed once to the handle's dtype:
+ * a replica whose parameters equal another handle's cfg computes what that handle computes, bit for bit.
+ * The device table is allocated by the first call and never moves; later calls overwrite it in place on `stream` (and wait for the
+ * copy: a set-up call like bcn_set_stp).  So a graph captured AFTER the first call reads whatever table is in force when it is
+ * replayed -- also after a later NULL, which only stops new launches from reading it -- and a graph captured BEFORE it keeps the
+ * uniform cfg.  Parameters are configuration, like the noise settings: they take effect at the next *_reset / *_step (burgers'
+ * reset fills a replica with its own u_target), alter no state, are not part of a snapshot or of bcn_snapshot_signature, and
+ * bcn_snapshot_load moves state between replicas while each replica keeps its physics.
+ * rayleigh / mixing: the table is an argument of the generic kernel only; while it is set, *_step runs ns2d_generic_step whatever
+ * bcn_set_variant selected (bcn_kernel_name says so), and NULL restores the previous dispatch.
+ * bcn_get_params: the values in force, double [n_params][B]; the cfg's values broadcast when none are set.
+ * bcn_derive_params_host (no device, no handle; for tests): the derived constants, in double, of one parameter set of env `kind`;
+ * aux = what the expressions need of the cfg besides (rayleigh: pr; mixing: the cfg's re, u_max; vortex: re_crit; else unused but
+ * not NULL).  Returns their number, -1 on a bad argument. */
+BCN_API int bcn_n_params(bcn_env_t h);
+BCN_API const char* bcn_param_name(bcn_env_t h, int i);
+BCN_API int bcn_set_params(bcn_env_t h, const double* values_host, void* stream);
+BCN_API int bcn_get_params(bcn_env_t h, double* values_host);
+BCN_API int bcn_derive_params_host(int kind, const double* params, const double* aux, double* derived);
 /* name of the kernel the last *_step dispatched, e.g. "ns2d_fast_sched" (before the first step: the
  * variant's plain kernel); for profiles */
 BCN_API const char* bcn_kernel_name(bcn_env_t h);
