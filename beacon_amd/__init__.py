@@ -5,10 +5,13 @@ Batched envs (tensors on the GPU, one HIP launch per step):
 Drop-in single-env mirrors of the reference classes:  beacon_amd.envs.{rayleigh, mixing, ...}
 Multi-GPU replica sharding:  beacon_amd.dist.ShardedVecEnv
 Full on-device state of a batch:  VecEnv.snapshot() -> Snapshot, VecEnv.restore(snap, src, mask), VecEnv.fork(src)
+Auto-reset and episode statistics on the device:  VecEnv.step_autoreset(a) -> (obs, rwd, done, trunc, EpisodeStats) -- the step, one
+bookkeeping launch (episode return / length, the terminal observation in final_obs) and the masked reset of finished replicas;
+VecEnv.track_episodes() for the bookkeeping alone, VecEnv.capture(..., autoreset=True) for graph rollouts across episode ends
 
 Importing the package does not touch the GPU; constructing an env does, and raises if the HIP
 library or a ROCm device is missing (there is no CPU fallback for the solver path)."""
-from .vec import Box, Discrete, Snapshot, VecBurgers, VecEnv, VecLorenz, VecMixing, VecRayleigh, VecShkadov, VecSloshing, VecVortex  # noqa: F401
+from .vec import Box, Discrete, EpisodeStats, Snapshot, VecBurgers, VecEnv, VecLorenz, VecMixing, VecRayleigh, VecShkadov, VecSloshing, VecVortex  # noqa: F401
 from .lorenz import lorenz  # noqa: F401
 from .vortex import vortex  # noqa: F401
 

@@ -78,6 +78,7 @@ class SnapshotSeg(C.Structure):
 
 
 SNAP_REAL, SNAP_I32, SNAP_U32, SNAP_U8 = 0, 1, 2, 3      # include/beacon_hip.h: BCN_SNAP_*
+SNAP_F64, SNAP_I64 = 4, 5                                # (bcn_episode_layout only)
 
 # every symbol include/beacon_hip.h declares: (restype, argtypes)
 SIGNATURES = {
@@ -131,6 +132,9 @@ SIGNATURES = {
     "bcn_snapshot_signature": (C.c_uint64, [vp]),
     "bcn_snapshot_save": (C.c_int, [vp, vp, vp, vp]),
     "bcn_snapshot_load": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp]),
+    "bcn_episode_bytes": (C.c_size_t, [vp]),
+    "bcn_episode_layout": (C.c_int, [vp, C.POINTER(SnapshotSeg), C.c_int]),
+    "bcn_episode_track": (C.c_int, [vp, vp, vp, vp, vp]),
     "bcn_n_params": (C.c_int, [vp]),
     "bcn_param_name": (C.c_char_p, [vp, C.c_int]),
     "bcn_set_params": (C.c_int, [vp, C.POINTER(C.c_double), vp]),

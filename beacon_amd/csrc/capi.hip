@@ -13,6 +13,7 @@
 #include "ode_env.h"
 #include "params.h"
 #include "snapshot.h"
+#include "episode.h"
 
 thread_local const char* bcn_env1d_launched = nullptr;   // env1d.h: set by the 1D launchers
 
@@ -676,6 +677,19 @@ uint64_t snap_cfg_of(bcn_env_t h) {
 
 inline size_t snap_up16(size_t x) { return (x + 15) / 16 * 16; }
 
+// Byte offsets of the packed per-step outputs [obs | rwd | status | done | trunc] of the handle's batch (obs at 0), every part
+// 16-byte aligned: the layout of the callers' out_buf (bcn_snapshot_save, bcn_episode_track)
+struct OutOffsets { size_t rwd, status, done, trunc; };
+inline OutOffsets out_offsets(bcn_env_t h) {
+  const size_t B = (size_t)h->batch, esz = h->esz;
+  OutOffsets o;
+  o.rwd = snap_up16(B * h->n_obs * esz);
+  o.status = snap_up16(o.rwd + B * esz);
+  o.done = snap_up16(o.status + B * 4);
+  o.trunc = snap_up16(o.done + B);
+  return o;
+}
+
 // Lays out a snapshot of n replicas of this handle's configuration: the bytes it takes, optionally the named segments (`lay`, up to
 // max_lay; the count is returned) and the kernels' table `t` (handle side: this handle's arrays and the packed output buffer
 // `out_buf` of its `batch` replicas; NULL out_buf leaves the five output segments out of the copy).
@@ -683,14 +697,12 @@ int snap_build(bcn_env_t h, int n, char* out_buf, SnapTable* t, bcn_snapshot_seg
   SnapDesc d[16];
   int nd = h->dtype == BCN_F32 ? snap_desc<float>(h, d) : snap_desc<double>(h, d);
   const size_t B = (size_t)h->batch, esz = h->esz;
-  // the packed per-step outputs [obs | rwd | status | done | trunc], every part 16-byte aligned (bcn_snapshot_save)
-  const size_t o_rwd = snap_up16(B * h->n_obs * esz), o_status = snap_up16(o_rwd + B * esz), o_done = snap_up16(o_status + B * 4),
-               o_trunc = snap_up16(o_done + B);
+  const OutOffsets o = out_offsets(h);
   d[nd++] = {"obs", BCN_SNAP_REAL, 1, (size_t)h->n_obs, out_buf};
-  d[nd++] = {"rwd", BCN_SNAP_REAL, 1, 1, out_buf ? out_buf + o_rwd : nullptr};
-  d[nd++] = {"status", BCN_SNAP_I32, 1, 1, out_buf ? out_buf + o_status : nullptr};
-  d[nd++] = {"done", BCN_SNAP_U8, 1, 1, out_buf ? out_buf + o_done : nullptr};
-  d[nd++] = {"trunc", BCN_SNAP_U8, 1, 1, out_buf ? out_buf + o_trunc : nullptr};
+  d[nd++] = {"rwd", BCN_SNAP_REAL, 1, 1, out_buf ? out_buf + o.rwd : nullptr};
+  d[nd++] = {"status", BCN_SNAP_I32, 1, 1, out_buf ? out_buf + o.status : nullptr};
+  d[nd++] = {"done", BCN_SNAP_U8, 1, 1, out_buf ? out_buf + o.done : nullptr};
+  d[nd++] = {"trunc", BCN_SNAP_U8, 1, 1, out_buf ? out_buf + o.trunc : nullptr};
   size_t off = 0, blk = 0;
   int ns = 0;
   for (int k = 0; k < nd; k++) {
@@ -725,6 +737,32 @@ int snap_build(bcn_env_t h, int n, char* out_buf, SnapTable* t, bcn_snapshot_seg
   if (bytes) *bytes = snap_up16(off);
   if (t) { t->nseg = ns; t->batch = h->batch; t->n_src = n; t->nblk = (unsigned)blk; }
   return nd;
+}
+
+// Lays out the episode buffer of this handle's batch (episode.h): the nine segments into `lay` (room for BCN_EP_NSEG) and / or the
+// bytes it takes.  Only batch, observation length and dtype of the handle are used.
+int episode_build(bcn_env_t h, bcn_snapshot_seg* lay, size_t* bytes) {
+  const size_t B = (size_t)h->batch, esz = h->esz;
+  if (h->batch < 1 || h->n_obs < 1 || B * (size_t)h->n_obs * esz / 4 > 0x7fffffffull) {
+    bcn_set_error("episode: batch %d x %d observations is outside what one launch covers", h->batch, h->n_obs);
+    return -1;
+  }
+  const struct { const char* name; int elem; size_t row_bytes; int64_t row_elems; } d[BCN_EP_NSEG] = {
+      {"ret", BCN_SNAP_REAL, esz, 1},      {"len", BCN_SNAP_I32, 4, 1},     {"last_ret", BCN_SNAP_REAL, esz, 1},
+      {"last_len", BCN_SNAP_I32, 4, 1},    {"count", BCN_SNAP_I32, 4, 1},   {"sum_ret", BCN_SNAP_F64, 8, 1},
+      {"sum_len", BCN_SNAP_I64, 8, 1},     {"finished", BCN_SNAP_U8, 1, 1}, {"final_obs", BCN_SNAP_REAL, (size_t)h->n_obs * esz, h->n_obs}};
+  size_t off = 0;
+  for (int k = 0; k < BCN_EP_NSEG; k++) {
+    off = snap_up16(off);
+    if (lay) {
+      memset(&lay[k], 0, sizeof(lay[k]));
+      strncpy(lay[k].name, d[k].name, sizeof(lay[k].name) - 1);
+      lay[k].offset = off; lay[k].elem = d[k].elem; lay[k].planes = 1; lay[k].row_elems = d[k].row_elems;
+    }
+    off += B * d[k].row_bytes;
+  }
+  if (bytes) *bytes = snap_up16(off);
+  return BCN_EP_NSEG;
 }
 
 // bcn_set_params: the table of derived constants of every replica, narrowed once to the handle's dtype, row k of replica b at
@@ -1123,6 +1161,47 @@ int bcn_snapshot_load(bcn_env_t h, const void* snap_dev, int n_src, const int32_
   if (snap_build(h, n_src, static_cast<char*>(out_buf_dev), &t, nullptr, 0, nullptr) < 0) return BCN_ERR_ARG;
   DeviceGuard g(h->device);
   return snapshot_launch(t, true, static_cast<char*>(const_cast<void*>(snap_dev)), src_dev, mask_dev, static_cast<hipStream_t>(stream));
+}
+// ---- episode statistics (episode.h) ------------------------------------------------------------
+size_t bcn_episode_bytes(bcn_env_t h) {
+  size_t bytes = 0;
+  if (!h) { bcn_set_error("bcn_episode_bytes: null handle"); return 0; }
+  if (episode_build(h, nullptr, &bytes) < 0) return 0;      // (episode_build has set the message)
+  return bytes;
+}
+int bcn_episode_layout(bcn_env_t h, bcn_snapshot_seg* segs, int max_segs) {
+  if (!h || (max_segs > 0 && !segs)) { bcn_set_error("bcn_episode_layout: null handle/array"); return 0; }
+  bcn_snapshot_seg lay[BCN_EP_NSEG];
+  const int nd = episode_build(h, lay, nullptr);
+  for (int k = 0; k < nd && k < max_segs; k++) segs[k] = lay[k];
+  return nd < 0 ? 0 : nd;
+}
+int bcn_episode_track(bcn_env_t h, const void* out_buf_dev, void* ep_buf_dev, const uint8_t* mask_dev, void* stream) {
+  if (!h || !out_buf_dev || !ep_buf_dev) { bcn_set_error("bcn_episode_track: null handle/buffer"); return BCN_ERR_ARG; }
+  if (!snap_ptr_ok(out_buf_dev) || !snap_ptr_ok(ep_buf_dev)) { bcn_set_error("bcn_episode_track: buffers must be 16-byte aligned"); return BCN_ERR_ARG; }
+  bcn_snapshot_seg lay[BCN_EP_NSEG];
+  if (episode_build(h, lay, nullptr) < 0) return BCN_ERR_ARG;
+  const size_t B = (size_t)h->batch, row = (size_t)h->n_obs * h->esz;
+  const OutOffsets o = out_offsets(h);
+  const char* out = static_cast<const char*>(out_buf_dev);
+  char* ep = static_cast<char*>(ep_buf_dev);
+  EpisodeArgs a;
+  a.obs = out; a.rwd = out + o.rwd;
+  a.done = reinterpret_cast<const uint8_t*>(out + o.done); a.trunc = reinterpret_cast<const uint8_t*>(out + o.trunc);
+  a.mask = mask_dev;
+  a.ret = ep + lay[0].offset; a.len = reinterpret_cast<int32_t*>(ep + lay[1].offset);
+  a.last_ret = ep + lay[2].offset; a.last_len = reinterpret_cast<int32_t*>(ep + lay[3].offset);
+  a.count = reinterpret_cast<int32_t*>(ep + lay[4].offset); a.sum_ret = reinterpret_cast<double*>(ep + lay[5].offset);
+  a.sum_len = reinterpret_cast<long long*>(ep + lay[6].offset); a.finished = reinterpret_cast<uint8_t*>(ep + lay[7].offset);
+  a.final_obs = ep + lay[8].offset;
+  a.batch = (unsigned)B;
+  a.nbk = (unsigned)((B + BCN_EP_NT - 1) / BCN_EP_NT);
+  a.unit = row % 16 == 0 ? 16 : row % 8 == 0 ? 8 : 4;      // rows are reals: multiples of 4 bytes
+  a.upr = (unsigned)(row / a.unit);
+  a.total = (unsigned)(B * a.upr);
+  a.f64 = h->dtype == BCN_F64;
+  DeviceGuard g(h->device);
+  return episode_launch(a, static_cast<hipStream_t>(stream));
 }
 const char* bcn_kernel_name(bcn_env_t h) { return h ? h->kernel_name() : ""; }
 int bcn_destroy(bcn_env_t h) {

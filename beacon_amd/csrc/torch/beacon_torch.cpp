@@ -1,6 +1,7 @@
 // beacon_torch.cpp -- the thin PyTorch-ROCm extension over the C ABI (include/beacon_hip.h): torch.library ops
 //   beacon::{rayleigh,mixing,burgers,shkadov,sloshing,lorenz,vortex}_{step,reset}(int handle, Tensor ...) -> ()
 //   beacon::snapshot_{save,load}(int handle, Tensor ...) -> ()
+//   beacon::episode_track(int handle, Tensor out_buf, Tensor ep_buf, Tensor? mask) -> ()
 // Each op is ONE dispatcher call that takes device tensors, reads torch's current HIP stream in C++ and forwards to the
 // bcn_* entry point of libbeacon_hip.so -- no ctypes marshalling, no Python-side stream query (what the per-call host cost of
 // the ctypes binding was made of: scripts/host_cost.py), and an op CUDA-graph capture and fake-tensor tracing can see (Meta kernels below).  The ops
@@ -211,6 +212,15 @@ void snapshot_load(int64_t h_, const Tensor& snap, int64_t n_src, OptT src, OptT
   check(bcn_snapshot_load(h, s, (int)n_src, idx, m, bytes_of(out_buf, h, out_buf_bytes(h), "out_buf"), stream_of(out_buf)), "bcn_snapshot_load");
 }
 
+// ---- episode statistics (include/beacon_hip.h: bcn_episode_track) -------------------------------------------------------
+void episode_track(int64_t h_, const Tensor& out_buf, const Tensor& ep_buf, OptT mask) {
+  bcn_env_t h = H(h_);
+  const uint8_t* o = bytes_of(out_buf, h, out_buf_bytes(h), "out_buf");
+  uint8_t* e = bytes_of(ep_buf, h, (int64_t)bcn_episode_bytes(h), "ep_buf");
+  const uint8_t* m = mask.has_value() ? u8(*mask, h, 1, "mask") : nullptr;
+  check(bcn_episode_track(h, o, e, m, stream_of(ep_buf)), "bcn_episode_track");
+}
+
 // Meta (fake-tensor) kernels: the ops return nothing and their outputs keep their shapes, so tracing needs no more than this.
 void reset2_meta(int64_t, const Tensor&) {}
 void reset3_meta(int64_t, OptT, const Tensor&) {}
@@ -220,6 +230,7 @@ void noisy_step_meta(int64_t, OptT, OptT, const Tensor&, const Tensor&, const Te
 void sloshing_step_meta(int64_t, OptT, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&) {}   // also lorenz, vortex
 void snapshot_save_meta(int64_t, const Tensor&, const Tensor&) {}
 void snapshot_load_meta(int64_t, const Tensor&, int64_t, OptT, OptT, const Tensor&) {}
+void episode_track_meta(int64_t, const Tensor&, const Tensor&, OptT) {}
 
 }  // namespace
 
@@ -249,6 +260,7 @@ TORCH_LIBRARY(beacon, m) {
         "Tensor(e!) status) -> ()");
   m.def("snapshot_save(int handle, Tensor(a!) snap, Tensor out_buf) -> ()");
   m.def("snapshot_load(int handle, Tensor snap, int n_src, Tensor? src, Tensor? mask, Tensor(a!) out_buf) -> ()");
+  m.def("episode_track(int handle, Tensor out_buf, Tensor(a!) ep_buf, Tensor? mask) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(beacon, CUDA, m) {
@@ -268,6 +280,7 @@ TORCH_LIBRARY_IMPL(beacon, CUDA, m) {
   m.impl("vortex_step", &vortex_step);
   m.impl("snapshot_save", &snapshot_save);
   m.impl("snapshot_load", &snapshot_load);
+  m.impl("episode_track", &episode_track);
 }
 
 TORCH_LIBRARY_IMPL(beacon, Meta, m) {
@@ -287,4 +300,5 @@ TORCH_LIBRARY_IMPL(beacon, Meta, m) {
   m.impl("vortex_step", &sloshing_step_meta);
   m.impl("snapshot_save", &snapshot_save_meta);
   m.impl("snapshot_load", &snapshot_load_meta);
+  m.impl("episode_track", &episode_track_meta);
 }

@@ -56,13 +56,14 @@ _OPS = ("rayleigh_reset", "rayleigh_step", "mixing_reset", "mixing_step", "burge
         "shkadov_step", "sloshing_reset", "sloshing_step")
 _ODE_OPS = ("lorenz_reset", "lorenz_step", "vortex_reset", "vortex_step")     # the ODE envs (csrc/ode_env.h)
 _STATE_OPS = ("snapshot_save", "snapshot_load")                               # every env (csrc/snapshot.hip)
+_EPISODE_OPS = ("episode_track",)                                             # every env (csrc/episode.hip)
 
 
 def _op_table():
     """{name: torch.ops.beacon.<name>.default} of the torch extension (beacon_amd/torch_ext.py), or None without it."""
     from . import torch_ext
     ops = torch_ext.load()
-    return None if ops is None else {n: getattr(ops, n).default for n in _OPS + _ODE_OPS + _STATE_OPS}
+    return None if ops is None else {n: getattr(ops, n).default for n in _OPS + _ODE_OPS + _STATE_OPS + _EPISODE_OPS}
 
 
 class Snapshot(object):
@@ -119,6 +120,85 @@ class Snapshot(object):
         d = torch.load(path, map_location="cpu", weights_only=True)
         snap = Snapshot(d["buf"], d["meta"])
         return snap if device is None else snap.to(device)
+
+
+class EpisodeStats(object):
+    """Episode statistics of one VecEnv, kept on the device by VecEnv.step_autoreset / track_episodes (csrc/episode.hip): `buf`,
+    one uint8 tensor in the layout of bcn_episode_layout (include/beacon_hip.h), and typed no-copy views of its segments, all [B]
+    but the last:
+      ret, len            return (env dtype) and length (int32) of the episode in progress
+      last_ret, last_len  those of the replica's last finished episode
+      count               finished episodes (int32)
+      sum_ret, sum_len    sums of the returns (float64) and lengths (int64) of the finished episodes
+      finished            uint8, 1 where the last tracked step ended an episode (done | trunc): which rows of `obs` are fresh
+      final_obs           [B, obs_dim], the terminal observation; a row is written when its replica finishes and kept until it finishes again
+    Batch totals are not kept: totals() sums the columns.
+    Bookkeeping, like `sweeps`: not part of a Snapshot or of snapshot_signature(); restore() / fork() move env state and leave
+    these statistics where they are -- clear(mask) is the tool after a fork."""
+
+    NAMES = ("ret", "len", "last_ret", "last_len", "count", "sum_ret", "sum_len", "finished", "final_obs")
+    _ELEM = {_lib.SNAP_I32: torch.int32, _lib.SNAP_U8: torch.uint8, _lib.SNAP_F64: torch.float64, _lib.SNAP_I64: torch.int64}
+
+    def __init__(self, env):
+        segs = (_lib.SnapshotSeg * 16)()
+        k = env.lib.bcn_episode_layout(env.h, segs, 16)
+        nbytes = env.lib.bcn_episode_bytes(env.h)
+        if k != len(self.NAMES) or nbytes == 0:
+            raise _lib.BeaconHipError("libbeacon_hip: %s" % env.lib.bcn_last_error().decode())
+        self.batch, self.obs_dim, self.tdtype = env.batch, env.obs_dim, env.tdtype
+        self.buf = torch.zeros((nbytes,), dtype=torch.uint8, device=env.device)
+        self.layout = [dict(name=segs[i].name.decode(), offset=int(segs[i].offset), elem=int(segs[i].elem),
+                            row_elems=int(segs[i].row_elems)) for i in range(k)]
+        assert tuple(seg["name"] for seg in self.layout) == self.NAMES
+        for seg in self.layout:
+            setattr(self, seg["name"], self.view(seg["name"]))
+
+    def view(self, name):
+        """Typed view (no copy) of one segment; KeyError for an unknown name."""
+        for seg in self.layout:
+            if seg["name"] == name:
+                break
+        else:
+            raise KeyError(name)
+        dt = self._ELEM.get(seg["elem"], self.tdtype)
+        esz = torch.empty((), dtype=dt).element_size()
+        v = self.buf[seg["offset"]:seg["offset"] + self.batch * seg["row_elems"] * esz].view(dt)
+        return v.view(self.batch, seg["row_elems"]) if name == "final_obs" else v
+
+    def clear(self, mask=None):
+        """Zero every segment of the replicas selected by `mask` ([B] bool / uint8 tensor or array; None: all).  No host
+        synchronisation."""
+        if mask is None:
+            self.buf.zero_()
+            return self
+        if not torch.is_tensor(mask):
+            mask = torch.as_tensor(np.asarray(mask))
+        m = mask.to(device=self.buf.device).reshape(self.batch) != 0
+        for name in self.NAMES:
+            v = getattr(self, name)
+            v.masked_fill_(m[:, None] if v.dim() == 2 else m, 0)
+        return self
+
+    def totals(self):
+        """The one host read: {"episodes", "return_sum", "length_sum", "return_mean", "length_mean"} over the batch, from
+        count.sum(), sum_ret.sum() and sum_len.sum() (the means are nan before the first episode ends)."""
+        t = torch.stack([self.count.sum().double(), self.sum_ret.sum(), self.sum_len.sum().double()]).cpu().tolist()
+        n, ls = int(round(t[0])), int(round(t[2]))
+        return {"episodes": n, "return_sum": t[1], "length_sum": ls,
+                "return_mean": t[1] / n if n else float("nan"), "length_mean": ls / n if n else float("nan")}
+
+    def state_dict(self):
+        """For checkpoints: the buffer on the CPU and what it was laid out for."""
+        return {"buf": self.buf.cpu(), "batch": self.batch, "obs_dim": self.obs_dim,
+                "dtype": "f64" if self.tdtype == torch.float64 else "f32"}
+
+    def load_state_dict(self, d):
+        if (int(d["batch"]), int(d["obs_dim"]), _DT[d["dtype"]][0]) != (self.batch, self.obs_dim, self.tdtype) or \
+                d["buf"].numel() != self.buf.numel():
+            raise ValueError("EpisodeStats.load_state_dict: statistics of %s replicas x %s observations (%s), this env has %d x %d"
+                             % (d["batch"], d["obs_dim"], d["dtype"], self.batch, self.obs_dim))
+        self.buf.copy_(d["buf"])
+        return self
 
 
 class ParamsWarning(UserWarning):
@@ -577,7 +657,69 @@ class VecEnv(object):
                     self._apply_mask(None)
         return self.obs, self.rwd, self.done, self.trunc, None
 
-    def capture(self, actions, noise=None, n_steps=None, keep_steps=True):
+    # -- episodes ---------------------------------------------------------------------------
+    @property
+    def episodes(self):
+        """The EpisodeStats of this env, created (zeroed) on first use."""
+        ep = getattr(self, "_episodes", None)
+        if ep is None:
+            ep = self._episodes = EpisodeStats(self)
+        return ep
+
+    def _track(self, ep, mask):
+        if self._ops is not None:
+            return self._ops["episode_track"](self.h.value, self.out_buf, ep.buf, mask)
+        _lib.check(self.lib.bcn_episode_track(self.h, _ptr(self.out_buf), _ptr(ep.buf), _ptr(mask), self._stream()))
+
+    def _reset_finished(self, ep):
+        """the env's own masked reset with ep.finished as the device mask (what reset_done() launches with done.clone()); the
+        caller clears the mask"""
+        self._mask = ep.finished
+        _lib.check(self.lib.bcn_set_mask(self.h, _ptr(ep.finished)))
+        self._reset()
+
+    def track_episodes(self, mask=None):
+        """The bookkeeping launch alone, for callers who keep resetting by hand: updates `episodes` from the outputs of the last
+        step() (call it once per step, before reset_done(), which overwrites the terminal rows of `obs`).  `mask`: the mask that
+        step was given.  Returns the EpisodeStats."""
+        if mask is not None:
+            if not torch.is_tensor(mask):
+                mask = torch.as_tensor(np.asarray(mask))
+            mask = mask.to(device=self.device, dtype=torch.uint8).reshape(self.batch).contiguous()
+        ep = self.episodes
+        self._keep_track = mask           # keeps the converted mask alive behind the asynchronous launch (as _keep, _done_mask do)
+        self._track(ep, mask)
+        return ep
+
+    def step_autoreset(self, actions=None, noise=None, mask=None):
+        """step() with same-step auto-reset and on-device episode statistics: the step kernel, ONE bookkeeping launch
+        (csrc/episode.hip) and the env's own masked reset of the replicas that finished (done | trunc) -- three launches, no host
+        synchronisation, nothing allocated after the first call.  Returns (obs, rwd, done, trunc, info):
+          rwd, done, trunc  the terminal step's;
+          obs               rows of finished replicas hold the RESET observation (the first of the next episode);
+          info              `episodes` (EpisodeStats): info.final_obs rows hold the terminal observation -- what bootstrapping on
+                            truncation needs -- info.finished says which rows are fresh, and ret / len / last_ret / last_len /
+                            count / sum_ret / sum_len are the running statistics.
+        Bit for bit what step(...); final = obs.clone(); reset_done() computes.  `mask`: as in step(); a skipped replica keeps
+        state, output rows and statistics, and is not reset even when its stale done byte is 1.  With double_buffer() it acts
+        on the buffer the step just wrote.
+        Not covered: restore() / fork() do not move episode statistics (EpisodeStats.clear(mask) after a fork); ShardedVecEnv has
+        no step_autoreset; the single-env mirrors (beacon_amd/envs.py) neither; next-step autoreset mode is not offered."""
+        ep = self.episodes
+        if self._rotate:
+            self._next_outputs(carry=mask is not None)
+        if mask is not None or self._mask is not None:
+            self._apply_mask(mask)
+        try:
+            self._step(actions, noise)
+            self._track(ep, self._mask)
+            self._reset_finished(ep)
+        finally:
+            if self._mask is not None:
+                self._apply_mask(None)
+        return self.obs, self.rwd, self.done, self.trunc, ep
+
+    def capture(self, actions, noise=None, n_steps=None, keep_steps=True, autoreset=False):
         """Record step() calls into ONE HIP graph (torch.cuda.CUDAGraph) and return it as a StepGraph: replay()
         relaunches them with a single host call.  step() only enqueues work on the current stream (no host
         synchronisation, no host read), so it can be captured -- on its own, as here, or inside a caller's graph next to
@@ -588,8 +730,12 @@ class VecEnv(object):
         keep_steps=False leaves out the per-step copies of obs / rwd / done / trunc (only the last step's stay, in the
         env's own tensors): every extra graph node costs a few microseconds between two kernels.
         The recorded kernels keep the noise seed / sigma they were captured with (set_noise_seed): change the seed, then
-        capture again."""
-        return StepGraph(self, actions, noise, n_steps, keep_steps)
+        capture again.
+        autoreset=True records step_autoreset() instead: per step the step kernel, the bookkeeping launch and the masked reset, so
+        a replayed rollout crosses episode ends.  obs_seq[k] then holds the post-reset observations, done_seq / trunc_seq the
+        terminal flags, and `episodes` accumulates across replays (its final_obs holds the LAST terminal observation of each
+        replica).  The default records exactly the step() calls."""
+        return StepGraph(self, actions, noise, n_steps, keep_steps, autoreset)
 
     def reset_done(self):
         """Auto-reset: re-initialise the replicas whose last step() returned done (their rows of
@@ -613,12 +759,13 @@ class VecEnv(object):
 
 
 class StepGraph(object):
-    """n step() calls of one VecEnv on static inputs, as a HIP graph (VecEnv.capture).  After replay() the env's own
+    """n step() calls (autoreset: step_autoreset() calls) of one VecEnv on static inputs, as a HIP graph (VecEnv.capture).  After replay() the env's own
     obs / rwd / done / trunc hold the last step's results; `obs_seq`, `rwd_seq`, `done_seq`, `trunc_seq` ([n, B, ...])
     hold every step's."""
 
-    def __init__(self, env, actions, noise=None, n_steps=None, keep_steps=True):
-        self.env, self.actions, self.noise = env, actions, noise
+    def __init__(self, env, actions, noise=None, n_steps=None, keep_steps=True, autoreset=False):
+        self.env, self.actions, self.noise, self.autoreset = env, actions, noise, bool(autoreset)
+        ep = env.episodes if autoreset else None          # allocated before the capture
         self.n = 1 if n_steps is None else int(n_steps)
         seq = n_steps is not None
         n = self.n if keep_steps else 0
@@ -636,6 +783,10 @@ class StepGraph(object):
                 a = actions[k] if seq else actions
                 z = None if noise is None else (noise[k] if seq else noise)
                 env._step(a, z)
+                if autoreset:
+                    env._track(ep, None)
+                    env._reset_finished(ep)
+                    env._apply_mask(None)
                 if not keep_steps:
                     continue
                 self.obs_seq[k].copy_(env.obs)

@@ -423,6 +423,31 @@ BCN_API const char* bcn_param_name(bcn_env_t h, int i);
 BCN_API int bcn_set_params(bcn_env_t h, const double* values_host, void* stream);
 BCN_API int bcn_get_params(bcn_env_t h, double* values_host);
 BCN_API int bcn_derive_params_host(int kind, const double* params, const double* aux, double* derived);
+/* Episode statistics and the rescue of terminal observations: the bookkeeping a trainer does between a *_step and the masked
+ * *_reset of the replicas whose episode ended, as ONE kernel launch on `stream` (no host synchronisation, no host read, no
+ * allocation: it can be captured into a graph between the two).  The handle is used for batch B, observation length and dtype
+ * only; the episode buffer belongs to the caller (bcn_episode_bytes(h) bytes -- 0 and bcn_last_error for a NULL handle --, 16-byte
+ * aligned, zeroed before its first use).
+ * Its segments, in this order, every start a multiple of 16 bytes (bcn_episode_layout writes them as bcn_snapshot_seg with
+ * planes = 1 and returns their number, 9; only the first max_segs are written; 0 and bcn_last_error on a bad argument):
+ *   ret real [B], len int32 [B]             return and length of the episode in progress
+ *   last_ret real [B], last_len int32 [B]   those of the replica's last finished episode
+ *   count int32 [B]                         finished episodes
+ *   sum_ret float64 [B], sum_len int64 [B]  sums of the returns and lengths of the finished episodes
+ *   finished uint8 [B]                      1 where the tracked step ended an episode -- the mask of the reset that follows
+ *   final_obs real [B][n_obs]               the terminal observation, written for finished replicas only
+ * bcn_episode_track: out_buf_dev is the packed output buffer of the step (bcn_snapshot_save: [obs | rwd | status | done | trunc]).
+ * For every replica b with mask_dev[b] != 0 (uint8[B]; NULL = all; the mask of bcn_set_mask plays no part), fin = done[b] | trunc[b]:
+ *   ret[b] += rwd[b] (one add in the handle's dtype); len[b] += 1;
+ *   if fin: last_ret[b] = ret[b]; last_len[b] = len[b]; count[b] += 1; sum_ret[b] += (double)ret[b]; sum_len[b] += len[b];
+ *           ret[b] = 0; len[b] = 0; final_obs[b][:] = obs[b][:];
+ *   finished[b] = fin.
+ * A replica with mask_dev[b] == 0 keeps every entry and gets finished[b] = 0 (its stale done byte must not start a reset).
+ * Batch totals are the sums of the count / sum_ret / sum_len columns, taken by the reader. */
+enum { BCN_SNAP_F64 = 4, BCN_SNAP_I64 = 5 };   /* element types of bcn_episode_layout besides BCN_SNAP_* above */
+BCN_API size_t bcn_episode_bytes(bcn_env_t h);
+BCN_API int bcn_episode_layout(bcn_env_t h, bcn_snapshot_seg* segs, int max_segs);
+BCN_API int bcn_episode_track(bcn_env_t h, const void* out_buf_dev, void* ep_buf_dev, const uint8_t* mask_dev, void* stream);
 /* name of the kernel the last *_step dispatched, e.g. "ns2d_fast_sched" (before the first step: the
  * variant's plain kernel); for profiles */
 BCN_API const char* bcn_kernel_name(bcn_env_t h);
