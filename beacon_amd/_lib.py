@@ -141,6 +141,7 @@ SIGNATURES = {
     "bcn_get_params": (C.c_int, [vp, C.POINTER(C.c_double)]),
     "bcn_derive_params_host": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "bcn_kernel_name": (C.c_char_p, [vp]),
+    "bcn_kernel_shape": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bcn_destroy": (C.c_int, [vp]),
     "bcn_last_error": (C.c_char_p, []),
     "bcn_version": (C.c_char_p, []),

@@ -16,6 +16,7 @@
 #include "episode.h"
 
 thread_local const char* bcn_env1d_launched = nullptr;   // env1d.h: set by the 1D launchers
+thread_local int bcn_env1d_shape_k = 0, bcn_env1d_shape_nt = 0;
 
 static thread_local char g_err[512] = "";
 
@@ -324,6 +325,7 @@ struct Env1D : bcn_env_s {
   uint64_t cfg_hash = 0;           // of the constructor's cfg (bcn_snapshot_signature)
   DevBuf fields, a_last, a_prev, stpbuf, nctrbuf;
   const char* kname = "";
+  int shape_k = 0, shape_nt = 0;   // of the last step launch (bcn_kernel_shape); 0, 0 before the first step
 
   int init(int n_actions) {
     int rc;
@@ -380,6 +382,8 @@ struct Env1D : bcn_env_s {
   }
   const char* kernel_name() const override { return kname; }
   void note_kernel(const char* n) override { kname = n; }
+  void note_shape(int k, int nt) override { shape_k = k; shape_nt = nt; }
+  void kernel_shape(int* k, int* nt) const override { *k = shape_k; *nt = shape_nt; }
   void set_mask(const uint8_t* m) override { a.mask = m; }
   void use_params(const void* table) override { a.prm = static_cast<const real*>(table); }
   int set_option(const char* name, int value) override {
@@ -867,9 +871,11 @@ int bcn_burgers_step(bcn_env_t h, const void* actions_dev, const void* noise_dev
   BCN_CHECK_KIND(h, BCN_BURGERS);
   DeviceGuard g(h->device);
   bcn_env1d_launched = nullptr;
+  bcn_env1d_shape_k = bcn_env1d_shape_nt = 0;
   const int rc_ = BCN_1D_CALL(h, burgers_launch_step, actions_dev, noise_dev, nullptr, obs_dev, rwd_dev, done_dev, trunc_dev,
                      status_dev);
   h->note_kernel(bcn_env1d_launched ? bcn_env1d_launched : "burgers_step_k");
+  h->note_shape(bcn_env1d_shape_k, bcn_env1d_shape_nt);
   return rc_;
 }
 
@@ -897,8 +903,13 @@ int bcn_shkadov_step(bcn_env_t h, const void* actions_dev, const void* noise_dev
                      uint8_t* done_dev, uint8_t* trunc_dev, int32_t* status_dev, void* stream) {
   BCN_CHECK_KIND(h, BCN_SHKADOV);
   DeviceGuard g(h->device);
-  return BCN_1D_CALL(h, shkadov_launch_step, actions_dev, noise_dev, nullptr, obs_dev, rwd_dev, done_dev, trunc_dev,
+  bcn_env1d_launched = nullptr;
+  bcn_env1d_shape_k = bcn_env1d_shape_nt = 0;
+  const int rc_ = BCN_1D_CALL(h, shkadov_launch_step, actions_dev, noise_dev, nullptr, obs_dev, rwd_dev, done_dev, trunc_dev,
                      status_dev);
+  h->note_kernel(bcn_env1d_launched ? bcn_env1d_launched : "shkadov_step_k");
+  h->note_shape(bcn_env1d_shape_k, bcn_env1d_shape_nt);
+  return rc_;
 }
 
 int bcn_sloshing_create(const bcn_sloshing_cfg* c, int batch, int dtype, int device, bcn_env_t* out) {
@@ -920,9 +931,11 @@ int bcn_sloshing_step(bcn_env_t h, const void* actions_dev, void* obs_dev, void*
   BCN_CHECK_KIND(h, BCN_SLOSHING);
   DeviceGuard g(h->device);
   bcn_env1d_launched = nullptr;
+  bcn_env1d_shape_k = bcn_env1d_shape_nt = 0;
   const int rc_ = BCN_1D_CALL(h, sloshing_launch_step, actions_dev, nullptr, nullptr, obs_dev, rwd_dev, done_dev, trunc_dev,
                      status_dev);
   h->note_kernel(bcn_env1d_launched ? bcn_env1d_launched : "sloshing_step_k");
+  h->note_shape(bcn_env1d_shape_k, bcn_env1d_shape_nt);
   return rc_;
 }
 
@@ -1204,6 +1217,11 @@ int bcn_episode_track(bcn_env_t h, const void* out_buf_dev, void* ep_buf_dev, co
   return episode_launch(a, static_cast<hipStream_t>(stream));
 }
 const char* bcn_kernel_name(bcn_env_t h) { return h ? h->kernel_name() : ""; }
+int bcn_kernel_shape(bcn_env_t h, int* cells_per_thread, int* threads) {
+  if (!h || !cells_per_thread || !threads) { bcn_set_error("bcn_kernel_shape: null argument"); return BCN_ERR_ARG; }
+  h->kernel_shape(cells_per_thread, threads);
+  return BCN_OK;
+}
 int bcn_destroy(bcn_env_t h) {
   if (!h) return BCN_OK;
   {

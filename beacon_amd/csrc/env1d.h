@@ -73,6 +73,8 @@ __device__ __forceinline__ real bcn_device_noise(const Env1DArgs<real>& A, int b
 
 // name of the step kernel the last *_launch_step of this thread dispatched when it is not the env's general one (else nullptr)
 extern thread_local const char* bcn_env1d_launched;
+// ... and the shape of that launch: cells per thread K and threads per replica NT of the instantiation (bcn_kernel_shape)
+extern thread_local int bcn_env1d_shape_k, bcn_env1d_shape_nt;
 template <typename real> int burgers_launch_step(const Env1DArgs<real>& a, int batch, hipStream_t s);
 template <typename real> int burgers_launch_reset(const Env1DArgs<real>& a, int batch, hipStream_t s);
 template <typename real> int shkadov_launch_step(const Env1DArgs<real>& a, int batch, hipStream_t s);

@@ -1234,14 +1234,20 @@ inline int pick_k_onewave(int n, int one_wave) {
   return n <= 64 ? 1 : (n <= 128 ? 2 : (n <= 256 ? 4 : 8));
 }
 
+// (K, NT) of the instantiation that is launched goes to bcn_env1d_shape_* (env1d.h): bcn_kernel_shape reports it
+#define BCN_LAUNCH_NT_(KERNEL, K_, NT_, A, BATCH, STREAM)                                                       \
+  do {                                                                                                          \
+    hipLaunchKernelGGL((KERNEL<real, K_, NT_>), dim3(BATCH), dim3(NT_), 0, STREAM, A);                          \
+    bcn_env1d_shape_k = K_; bcn_env1d_shape_nt = NT_;                                                           \
+  } while (0)
 #define BCN_LAUNCH_NT(KERNEL, K_, A, BATCH, STREAM)                                                             \
   do {                                                                                                          \
     const int n__ = (A).n;                                                                                      \
-    if (n__ <= K_ * 64) hipLaunchKernelGGL((KERNEL<real, K_, 64>), dim3(BATCH), dim3(64), 0, STREAM, A);        \
-    else if (n__ <= K_ * 128) hipLaunchKernelGGL((KERNEL<real, K_, 128>), dim3(BATCH), dim3(128), 0, STREAM, A); \
-    else if (n__ <= K_ * 256) hipLaunchKernelGGL((KERNEL<real, K_, 256>), dim3(BATCH), dim3(256), 0, STREAM, A); \
-    else if (n__ <= K_ * 512) hipLaunchKernelGGL((KERNEL<real, K_, 512>), dim3(BATCH), dim3(512), 0, STREAM, A); \
-    else hipLaunchKernelGGL((KERNEL<real, K_, 1024>), dim3(BATCH), dim3(1024), 0, STREAM, A);                   \
+    if (n__ <= K_ * 64) BCN_LAUNCH_NT_(KERNEL, K_, 64, A, BATCH, STREAM);                                       \
+    else if (n__ <= K_ * 128) BCN_LAUNCH_NT_(KERNEL, K_, 128, A, BATCH, STREAM);                                \
+    else if (n__ <= K_ * 256) BCN_LAUNCH_NT_(KERNEL, K_, 256, A, BATCH, STREAM);                                \
+    else if (n__ <= K_ * 512) BCN_LAUNCH_NT_(KERNEL, K_, 512, A, BATCH, STREAM);                                \
+    else BCN_LAUNCH_NT_(KERNEL, K_, 1024, A, BATCH, STREAM);                                                    \
   } while (0)
 
 #define BCN_DISPATCH_1D(KERNEL, A, BATCH, STREAM, ONEWAVE_OK)                                  \
@@ -1271,6 +1277,7 @@ template <typename real> int burgers_launch_step(const Env1DArgs<real>& a, int b
       if (a.n > 256) hipLaunchKernelGGL((burgers_step_pk_k<8, false>), dim3(batch), dim3(64), 0, s, a);
       else hipLaunchKernelGGL((burgers_step_pk_k<4, false>), dim3(batch), dim3(64), 0, s, a);
       bcn_env1d_launched = "burgers_step_pk_k";
+      bcn_env1d_shape_k = a.n > 256 ? 8 : 4; bcn_env1d_shape_nt = 64;
       BCN_HIP(hipGetLastError());
       return BCN_OK;
     }
@@ -1284,6 +1291,7 @@ template <typename real> int burgers_launch_step(const Env1DArgs<real>& a, int b
         if (a.n == 512) hipLaunchKernelGGL((burgers_step_pk_k<8, true>), dim3(batch), dim3(64), 0, s, a);
         else hipLaunchKernelGGL((burgers_step_pk_k<4, true>), dim3(batch), dim3(64), 0, s, a);
         bcn_env1d_launched = "burgers_step_pk_k";
+        bcn_env1d_shape_k = a.n / 64; bcn_env1d_shape_nt = 64;
         BCN_HIP(hipGetLastError());
         return BCN_OK;
       }
@@ -1292,6 +1300,7 @@ template <typename real> int burgers_launch_step(const Env1DArgs<real>& a, int b
     if (a.n == 512) hipLaunchKernelGGL((burgers_step_k<real, 8, 64, true>), dim3(batch), dim3(64), 0, s, a);
     else if (a.n == 256) hipLaunchKernelGGL((burgers_step_k<real, 4, 64, true>), dim3(batch), dim3(64), 0, s, a);
     else hipLaunchKernelGGL((burgers_step_k<real, 2, 64, true>), dim3(batch), dim3(64), 0, s, a);
+    bcn_env1d_shape_k = a.n / 64; bcn_env1d_shape_nt = 64;   // FIT: n == 64 K
     BCN_HIP(hipGetLastError());
     return BCN_OK;
   }
@@ -1319,6 +1328,7 @@ template <typename real> int sloshing_launch_step(const Env1DArgs<real>& a, int 
     if (a.one_wave == 1 && a.force_k == 0 && a.n > 128 && a.n <= 256 && ((a.n - 1) & 3) != 0 && a.ndt_act <= 64 && a.nx == a.n - 2) {
       hipLaunchKernelGGL((sloshing_step_pk_k<4>), dim3(batch), dim3(64), 0, s, a);
       bcn_env1d_launched = "sloshing_step_pk_k";
+      bcn_env1d_shape_k = 4; bcn_env1d_shape_nt = 64;
       BCN_HIP(hipGetLastError());
       return BCN_OK;
     }

@@ -536,6 +536,15 @@ class VecEnv(object):
     def kernel_name(self):
         return self.lib.bcn_kernel_name(self.h).decode()
 
+    @property
+    def kernel_shape(self):
+        """(cells per thread, threads per replica) of the 1D step kernel the last step() launched -- the launcher overrides
+        the options cells_per_thread / one_wave where they do not fit the grid (include/beacon_hip.h: bcn_kernel_shape);
+        (0, 0) before the first step and for the envs without the notion."""
+        k, nt = C.c_int(0), C.c_int(0)
+        _lib.check(self.lib.bcn_kernel_shape(self.h, C.byref(k), C.byref(nt)))
+        return (k.value, nt.value)
+
     def check_status(self):
         """Synchronise and raise if any replica reported a solver failure (the reference
         prints and exit(1)s on Poisson non-convergence: rayleigh.py:221-224)."""

@@ -451,6 +451,12 @@ BCN_API int bcn_episode_track(bcn_env_t h, const void* out_buf_dev, void* ep_buf
 /* name of the kernel the last *_step dispatched, e.g. "ns2d_fast_sched" (before the first step: the
  * variant's plain kernel); for profiles */
 BCN_API const char* bcn_kernel_name(bcn_env_t h);
+/* shape of the 1D step kernel the last *_step dispatched (burgers, shkadov, sloshing): cells per thread K and threads per
+ * replica NT of the instantiation, K * NT >= n.  The launcher picks them from the grid length, the batch and the options
+ * "cells_per_thread" / "one_wave" -- and overrides a request that does not fit (K is raised while n > 1024 K; grids up to 512
+ * cells run as one wave unless one_wave is 0) -- so this is how a caller learns what ran.  The packed and exact-fit one-wave
+ * kernels report K = n / 64 or 4 / 8 with NT = 64.  Before the first step, and for envs without the notion: 0, 0. */
+BCN_API int bcn_kernel_shape(bcn_env_t h, int* cells_per_thread, int* threads);
 BCN_API int bcn_destroy(bcn_env_t h);
 BCN_API const char* bcn_last_error(void);
 BCN_API const char* bcn_version(void);

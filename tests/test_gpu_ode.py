@@ -383,3 +383,141 @@ def test_large_batch_matches_host_port(name, dtype):
     else:
         _report(name + "_f32_10steps", _rel(dev_obs, ref_obs))
     env.close()
+
+
+# ---- 8. the two observation stores (option obs_stage) at workgroup boundaries -------------------------------------------------------
+# float32 defaults to obs_stage 0 (one row per lane), float64 to 1 (rows staged through LDS): without the option <float, true> and
+# <double, false> of both step kernels never run.  B = 257 leaves ONE live lane in the second workgroup, 300 leaves 44.
+def _ode_make(name, dtype, B, stage):
+    env = (V.VecLorenz if name == "lorenz" else V.VecVortex)(B, DEV, dtype)
+    env.set_option("obs_stage", stage)
+    return env
+
+
+def _ode_actions(name, rng, n, B):
+    return rng.integers(0, 3, (n, B)) if name == "lorenz" else rng.uniform(-1, 1, (n, B, 2))
+
+
+def _ode_step(name, env, a):
+    return env.step(torch.as_tensor(a, dtype=torch.int32, device=DEV) if name == "lorenz" else torch.as_tensor(a, device=DEV))
+
+
+def _ode_check_rows(name, dtype, dev_obs, dev_rwd, ref_obs, ref_rwd, what):
+    """device rows against the host port's, with the bounds of this file: float64 lorenz bit for bit, float64 vortex the measured
+    cos / sin difference, float32 the bounds of the 10-step comparison from reset (observations, relative per column) and of the
+    one-step comparisons (vortex reward, relative; lorenz reward: the sign, outside the rounding zone of x0)"""
+    dev_obs, ref_obs = np.asarray(dev_obs, np.float64), np.asarray(ref_obs, np.float64)
+    dev_rwd, ref_rwd = np.asarray(dev_rwd, np.float64), np.asarray(ref_rwd, np.float64)
+    if dtype == "f64" and name == "lorenz":
+        assert np.array_equal(dev_obs, ref_obs) and np.array_equal(dev_rwd, ref_rwd), what
+    elif dtype == "f64":
+        eo, er = float(np.abs(dev_obs - ref_obs).max()), float(np.abs(dev_rwd - ref_rwd).max())
+        print("MEASURED %s vortex f64 obs %.3e rwd %.3e" % (what, eo, er))
+        assert eo <= TOL["vortex_f64_obs"] and er <= TOL["vortex_f64_rwd"], (what, eo, er)
+    else:
+        eo = _rel(dev_obs, ref_obs)
+        print("MEASURED %s %s f32 obs rel %.3e" % (what, name, eo))
+        assert eo <= TOL[name + "_f32_10steps"], (what, eo)
+        if name == "vortex":
+            er = _rel(dev_rwd.reshape(-1), ref_rwd.reshape(-1))
+            print("MEASURED %s vortex f32 rwd rel %.3e" % (what, er))
+            assert er <= TOL["vortex_f32_rwd"], (what, er)
+        else:
+            x0 = ref_obs[..., 0]
+            keep = np.abs(x0) > TOL["lorenz_f32_10steps"] * np.abs(x0).max()
+            assert np.array_equal(dev_rwd[keep], ref_rwd[keep]), what
+
+
+@pytest.mark.parametrize("B", [1, 257, 300])
+@pytest.mark.parametrize("stage", [0, 1])
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+@pytest.mark.parametrize("name", ["lorenz", "vortex"])
+def test_obs_store_variants_match_the_host_port(name, dtype, stage, B):
+    """Five action steps from reset with random actions, every replica against the host port; float64: state, observations, reward,
+    done and status of the two stores are bitwise equal (the arithmetic is the same code, built without contraction)."""
+    _need_gpu()
+    n = 5
+    acts = _ode_actions(name, np.random.default_rng(B), n, B)
+    env = _ode_make(name, dtype, B, stage)
+    other = _ode_make(name, dtype, B, 1 - stage) if dtype == "f64" else None
+    hosts = [(beacon_amd.lorenz if name == "lorenz" else beacon_amd.vortex)() for _ in range(B)]
+    obs0, _ = env.reset()
+    for b, h in enumerate(hosts):
+        h.reset()
+    _ode_check_rows(name, dtype, _np(obs0), np.zeros(B), np.stack([h.get_obs() for h in hosts]), np.zeros(B), "reset B=%d" % B)
+    if other is not None:
+        assert torch.equal(other.reset()[0], obs0)
+    ref_obs, ref_rwd, dev_obs, dev_rwd = np.zeros((n, B, env.n_obs)), np.zeros((n, B)), [], []
+    for k in range(n):
+        obs, rwd, done, trunc, _ = _ode_step(name, env, acts[k])
+        dev_obs.append(_np(obs).copy()), dev_rwd.append(_np(rwd).copy())
+        for b, h in enumerate(hosts):
+            o, r, d, t, _ = h.step(np.int64(acts[k, b]) if name == "lorenz" else acts[k, b])
+            ref_obs[k, b], ref_rwd[k, b] = o, r
+            assert bool(done[b]) == d and bool(trunc[b]) == t
+        assert int(env.status.abs().max()) == 0
+        if other is not None:
+            o2 = _ode_step(name, other, acts[k])
+            for x, y in zip((obs, rwd, done, trunc, env.status, env.get_state()), o2[:4] + (other.status, other.get_state())):
+                assert torch.equal(x, y), (k, "the two stores differ")
+    _ode_check_rows(name, dtype, np.stack(dev_obs), np.stack(dev_rwd), ref_obs, ref_rwd, "%d steps B=%d stage=%d" % (n, B, stage))
+    assert np.array_equal(env.get_stp(), np.full(B, n))
+    env.close()
+    if other is not None:
+        other.close()
+
+
+@pytest.mark.parametrize("stage", [0, 1])
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+@pytest.mark.parametrize("name", ["lorenz", "vortex"])
+def test_obs_store_variants_leave_masked_rows_untouched(name, dtype, stage):
+    """B = 300 with rows switched off on both sides of the workgroup boundary and at the end of the partial workgroup (b = 255,
+    256, 299): the staged store's guard is `e < n && act[e / NOBS]`, element by element.  The masked rows of an obs_out filled
+    with a sentinel stay bitwise untouched, as do their state, reward, done and status; the live rows are right.  The same for a
+    masked reset, which always stores through LDS."""
+    _need_gpu()
+    B, SENT = 300, -777.25
+    acts = _ode_actions(name, np.random.default_rng(7), 3, B)
+    env = _ode_make(name, dtype, B, stage)
+    hosts = [(beacon_amd.lorenz if name == "lorenz" else beacon_amd.vortex)() for _ in range(B)]
+    env.reset()
+    for h in hosts:
+        h.reset()
+    _ode_step(name, env, acts[0])
+    for b, h in enumerate(hosts):
+        h.step(np.int64(acts[0, b]) if name == "lorenz" else acts[0, b])
+    live = np.ones(B, bool)
+    live[[255, 256, 299]] = False
+    off = torch.as_tensor(~live, device=DEV)
+    # a masked step
+    env.obs.fill_(SENT)
+    before = [x.clone() for x in (env.get_state(), env.rwd, env.done, env.trunc, env.status)]
+    a = acts[1]
+    obs, rwd, done, trunc, _ = env.step(torch.as_tensor(a, dtype=torch.int32 if name == "lorenz" else env.tdtype, device=DEV),
+                                        mask=torch.as_tensor(live, device=DEV))
+    assert torch.equal(obs[off], torch.full_like(obs[off], SENT)), "a masked observation row was written"
+    for x, y in zip(before, (env.get_state(), rwd, done, trunc, env.status)):
+        assert torch.equal(x[off], y[off])
+    ref = [hosts[b].step(np.int64(a[b]) if name == "lorenz" else a[b]) for b in np.nonzero(live)[0]]
+    _ode_check_rows(name, dtype, _np(obs)[live], _np(rwd)[live], np.stack([r[0] for r in ref]), np.array([r[1] for r in ref]),
+                    "masked step stage=%d" % stage)
+    # a masked reset: the rows on both sides of the boundary are reset, their neighbours are not
+    sel = np.zeros(B, bool)
+    sel[[0, 254, 257, 298]] = True
+    env.obs.fill_(SENT)
+    st_before = env.get_state().clone()
+    obs, _ = env.reset(mask=torch.as_tensor(sel, device=DEV))
+    keep = torch.as_tensor(~sel, device=DEV)
+    assert torch.equal(obs[keep], torch.full_like(obs[keep], SENT)), "a masked observation row was written by reset"
+    assert _state_rows_equal(_np(env.get_state())[~sel], _np(st_before)[~sel])
+    for b in np.nonzero(sel)[0]:
+        hosts[b].reset()
+    _ode_check_rows(name, dtype, _np(obs)[sel], np.zeros(sel.sum()), np.stack([hosts[b].get_obs() for b in np.nonzero(sel)[0]]),
+                    np.zeros(sel.sum()), "masked reset stage=%d" % stage)
+    # ... and everybody steps on from there
+    obs, rwd, _, _, _ = _ode_step(name, env, acts[2])
+    ref = [h.step(np.int64(acts[2, b]) if name == "lorenz" else acts[2, b]) for b, h in enumerate(hosts)]
+    # (b = 255, 256, 299 missed one step: their hosts did too)
+    _ode_check_rows(name, dtype, _np(obs), _np(rwd), np.stack([r[0] for r in ref]), np.array([r[1] for r in ref]),
+                    "step after the masked reset stage=%d" % stage)
+    env.close()
