@@ -80,8 +80,6 @@ struct bcn_env_s {
   virtual int get_slow_mode_bound(double*, double*) const { return 0; }
   virtual int get_counters(uint64_t* host, hipStream_t) { memset(host, 0, (size_t)batch * 4 * sizeof(uint64_t)); return BCN_OK; }   // only the 2D register-resident kernels schedule
   virtual const char* kernel_name() const = 0;
-  virtual void note_kernel(const char*) {}   // 1D envs: the step kernel the launcher chose (packed or general)
-  virtual void note_shape(int, int) {}       // 1D envs: cells per thread and threads per replica of that launch
   virtual void kernel_shape(int* k, int* nt) const { *k = 0; *nt = 0; }   // (0, 0): the env has no such notion
   // per-replica physical parameters (bcn_set_params; params.h)
   virtual void use_params(const void* table) = 0;   // the kernels read `table` from the next launch on (nullptr: the argument block's values)
@@ -91,6 +89,7 @@ struct bcn_env_s {
   double prm_aux[2] = {0, 0};      // what else of the cfg the derived constants need (params.h: bcn_derive_params)
   int32_t* stp = nullptr;  // device int32[B]
   int ndt_act = 0;         // timesteps per action step (rows of the callers' sweeps / noise buffers: bcn_ndt_act)
+  uint64_t cfg_hash = 0;   // of the constructor's cfg (bcn_snapshot_signature)
 };
 
 // device allocation tracked per handle

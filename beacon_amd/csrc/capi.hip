@@ -15,9 +15,6 @@
 #include "snapshot.h"
 #include "episode.h"
 
-thread_local const char* bcn_env1d_launched = nullptr;   // env1d.h: set by the 1D launchers
-thread_local int bcn_env1d_shape_k = 0, bcn_env1d_shape_nt = 0;
-
 static thread_local char g_err[512] = "";
 
 // default visibility: the on-demand kernel plugins (csrc/jit/ns2d_jit.hip) report through the library's error buffer
@@ -35,6 +32,40 @@ struct DeviceGuard {
   explicit DeviceGuard(int dev) { (void)hipGetDevice(&prev); (void)hipSetDevice(dev); }
   ~DeviceGuard() { (void)hipSetDevice(prev); }
 };
+
+// F<float>(...) or F<double>(...) by a handle's (or a create call's) dtype
+#define BCN_BY_DTYPE(dtype, F, ...) ((dtype) == BCN_F32 ? F<float>(__VA_ARGS__) : F<double>(__VA_ARGS__))
+
+// The constructor skeleton of every env: allocate, fill the handle's header, let `fill` set the argument block from the cfg, init(),
+// hand the handle out (or delete it when init() failed)
+template <typename Env, typename Fill>
+int make_env(int kind, int batch, int dtype, int device, uint64_t cfg_hash, bcn_env_t* out, Fill fill) {
+  auto* e = new (std::nothrow) Env();
+  if (!e) { bcn_set_error("out of host memory"); return BCN_ERR_ARG; }
+  e->kind = kind; e->batch = batch; e->dtype = dtype; e->device = device; e->esz = dtype == BCN_F64 ? 8 : 4;
+  e->cfg_hash = cfg_hash;
+  fill(e);
+  const int rc = e->init();
+  if (rc) { delete e; return rc; }
+  *out = e;
+  return BCN_OK;
+}
+
+// bcn_get_state / bcn_set_state of the grid envs.  State buffer layout: [B][planes][row]; device layout: [planes][B][row]
+int copy_planes(void* buf, void* dev, int planes, size_t row, int batch, int is_device, hipStream_t s, bool out) {
+  const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : (out ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice);
+  for (int k = 0; k < planes; k++) {
+    char* e = static_cast<char*>(buf) + (size_t)k * row;
+    char* d = static_cast<char*>(dev) + (size_t)k * batch * row;
+    if (out) BCN_HIP(hipMemcpy2DAsync(e, planes * row, d, row, row, batch, kind, s));
+    else BCN_HIP(hipMemcpy2DAsync(d, row, e, planes * row, row, batch, kind, s));
+  }
+  if (!is_device) BCN_HIP(hipStreamSynchronize(s));
+  return BCN_OK;
+}
+
+// widest unit (bytes) in which the copy kernels move rows of `row` bytes (snapshot.h, episode.h)
+inline unsigned copy_unit(size_t row) { return row % 16 == 0 ? 16 : row % 8 == 0 ? 8 : row % 4 == 0 ? 4 : 1; }
 
 // FNV-1a over the values of a cfg struct (its int32 members, then its doubles: the layout of every bcn_*_cfg), without the padding
 // between the two groups: the part of bcn_snapshot_signature that says "same constructor arguments"
@@ -63,7 +94,6 @@ struct NS2DEnv : bcn_env_s {
   DevBuf obs_hist, a_last, ia_last, stpbuf, sweepbuf, orderbuf, schedbuf, fscrbuf, statusbuf;
   int32_t* status_int = nullptr;   // per-replica status words when the caller passes no status_dev
   bool fast_ok = false;
-  uint64_t cfg_hash = 0;           // of the constructor's cfg (bcn_snapshot_signature)
   bool guard_holds() const { return a.nx >= 48 && a.ny >= 48; }
 
   int init() {
@@ -170,23 +200,11 @@ struct NS2DEnv : bcn_env_s {
     stpbuf.release(); sweepbuf.release(); orderbuf.release(); schedbuf.release(); statusbuf.release();
   }
   size_t state_elems() const override { return 4 * (size_t)a.ncell; }
-  // state buffer layout: [B][4][ncell]; device layout: [4][B][ncell]
-  int copy_state(void* buf, int is_device, hipStream_t s, bool out) {
-    const size_t row = (size_t)a.ncell * sizeof(real);
-    real* f = static_cast<real*>(fields.p);
-    for (int k = 0; k < 4; k++) {
-      char* ext = static_cast<char*>(buf) + (size_t)k * row;
-      real* dev = f + (size_t)k * batch * a.ncell;
-      hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : (out ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice);
-      if (out) BCN_HIP(hipMemcpy2DAsync(ext, 4 * row, dev, row, row, batch, kind, s));
-      else BCN_HIP(hipMemcpy2DAsync(dev, row, ext, 4 * row, row, batch, kind, s));
-    }
-    if (!is_device) BCN_HIP(hipStreamSynchronize(s));
-    return BCN_OK;
+  int get_state(void* buf, int is_device, hipStream_t s) override {
+    return copy_planes(buf, fields.p, 4, (size_t)a.ncell * sizeof(real), batch, is_device, s, true);
   }
-  int get_state(void* buf, int is_device, hipStream_t s) override { return copy_state(buf, is_device, s, true); }
   int set_state(const void* buf, int is_device, hipStream_t s) override {
-    return copy_state(const_cast<void*>(buf), is_device, s, false);
+    return copy_planes(const_cast<void*>(buf), fields.p, 4, (size_t)a.ncell * sizeof(real), batch, is_device, s, false);
   }
   int set_variant(int v) override { variant = (v == 1 && fast_ok) ? 1 : 0; host.launched = nullptr; return variant; }
   void set_mask(const uint8_t* m) override { a.mask = m; }
@@ -268,50 +286,38 @@ void ns2d_common(NS2DArgs<real>& a, int nx, int ny, double dx, double dy, double
 
 template <typename real>
 int make_rayleigh(const bcn_rayleigh_cfg* c, int batch, int dtype, int device, bcn_env_t* out) {
-  auto* e = new (std::nothrow) NS2DEnv<real>();
-  if (!e) { bcn_set_error("out of host memory"); return BCN_ERR_ARG; }
-  e->kind = BCN_RAYLEIGH; e->batch = batch; e->dtype = dtype; e->device = device; e->esz = sizeof(real);
-  NS2DArgs<real>& a = e->a;
-  ns2d_common(a, c->nx, c->ny, c->dx, c->dy, c->dt, c->tol);
-  a.kind = 0; a.ndt_act = c->ndt_act; a.n_act = c->n_act; a.itmax = c->itmax;
-  a.n_sgts = c->n_sgts; a.nx_sgts = c->nx_sgts;
-  a.nxo = c->nx_obs_pts; a.nyo = c->ny_obs_pts; a.nx_obs = c->nx_obs; a.ny_obs = c->ny_obs;
-  a.n_obs_steps = c->n_obs_steps; a.n_obs = 3 * c->n_obs_steps * c->nx_obs_pts * c->ny_obs_pts;
-  a.kmom = (real)bcn_rayleigh_kmom(c->pr, c->ra);
-  a.ksc = (real)bcn_rayleigh_ksc(c->pr, c->ra);
-  e->prm_cfg[0] = c->ra; e->prm_aux[0] = c->pr;
-  a.Tc = (real)c->Tc; a.Th = (real)c->Th; a.C = (real)c->C;
-  a.rwd_scale = (real)(1.0 / (0.5 * c->dy * c->nx));
-  e->n_obs = a.n_obs; e->n_act = c->n_sgts; e->ndt_act = a.ndt_act;
-  e->cfg_hash = snap_cfg_hash<bcn_rayleigh_cfg, 12, 9>(c);
-  int rc = e->init();
-  if (rc) { delete e; return rc; }
-  *out = e;
-  return BCN_OK;
+  return make_env<NS2DEnv<real>>(BCN_RAYLEIGH, batch, dtype, device, snap_cfg_hash<bcn_rayleigh_cfg, 12, 9>(c), out, [c](NS2DEnv<real>* e) {
+    NS2DArgs<real>& a = e->a;
+    ns2d_common(a, c->nx, c->ny, c->dx, c->dy, c->dt, c->tol);
+    a.kind = 0; a.ndt_act = c->ndt_act; a.n_act = c->n_act; a.itmax = c->itmax;
+    a.n_sgts = c->n_sgts; a.nx_sgts = c->nx_sgts;
+    a.nxo = c->nx_obs_pts; a.nyo = c->ny_obs_pts; a.nx_obs = c->nx_obs; a.ny_obs = c->ny_obs;
+    a.n_obs_steps = c->n_obs_steps; a.n_obs = 3 * c->n_obs_steps * c->nx_obs_pts * c->ny_obs_pts;
+    a.kmom = (real)bcn_rayleigh_kmom(c->pr, c->ra);
+    a.ksc = (real)bcn_rayleigh_ksc(c->pr, c->ra);
+    e->prm_cfg[0] = c->ra; e->prm_aux[0] = c->pr;
+    a.Tc = (real)c->Tc; a.Th = (real)c->Th; a.C = (real)c->C;
+    a.rwd_scale = (real)(1.0 / (0.5 * c->dy * c->nx));
+    e->n_obs = a.n_obs; e->n_act = c->n_sgts; e->ndt_act = a.ndt_act;
+  });
 }
 
 template <typename real>
 int make_mixing(const bcn_mixing_cfg* c, int batch, int dtype, int device, bcn_env_t* out) {
-  auto* e = new (std::nothrow) NS2DEnv<real>();
-  if (!e) { bcn_set_error("out of host memory"); return BCN_ERR_ARG; }
-  e->kind = BCN_MIXING; e->batch = batch; e->dtype = dtype; e->device = device; e->esz = sizeof(real);
-  NS2DArgs<real>& a = e->a;
-  ns2d_common(a, c->nx, c->ny, c->dx, c->dy, c->dt, c->tol);
-  a.kind = 1; a.ndt_act = c->ndt_act; a.n_act = c->n_act; a.itmax = c->itmax;
-  a.n_sgts = 0; a.nx_sgts = 1;
-  a.nxo = c->nx_obs_pts; a.nyo = c->ny_obs_pts; a.nx_obs = c->nx_obs; a.ny_obs = c->ny_obs;
-  a.n_obs_steps = c->n_obs_steps; a.n_obs = 3 * c->n_obs_steps * c->nx_obs_pts * c->ny_obs_pts;
-  a.i_min = c->i_min; a.i_max = c->i_max; a.j_min = c->j_min; a.j_max = c->j_max;
-  a.kmom = (real)bcn_mixing_kmom(c->re);
-  a.ksc = (real)bcn_mixing_ksc(c->pe);
-  e->prm_cfg[0] = c->re; e->prm_cfg[1] = c->pe; e->prm_aux[0] = c->re; e->prm_aux[1] = c->u_max;
-  a.u_max = (real)bcn_mixing_u_max(c->re, c->re, c->u_max); a.ref_c = (real)c->ref_c; a.C0 = (real)c->C0;
-  e->n_obs = a.n_obs; e->n_act = 1; e->ndt_act = a.ndt_act;
-  e->cfg_hash = snap_cfg_hash<bcn_mixing_cfg, 14, 9>(c);
-  int rc = e->init();
-  if (rc) { delete e; return rc; }
-  *out = e;
-  return BCN_OK;
+  return make_env<NS2DEnv<real>>(BCN_MIXING, batch, dtype, device, snap_cfg_hash<bcn_mixing_cfg, 14, 9>(c), out, [c](NS2DEnv<real>* e) {
+    NS2DArgs<real>& a = e->a;
+    ns2d_common(a, c->nx, c->ny, c->dx, c->dy, c->dt, c->tol);
+    a.kind = 1; a.ndt_act = c->ndt_act; a.n_act = c->n_act; a.itmax = c->itmax;
+    a.n_sgts = 0; a.nx_sgts = 1;
+    a.nxo = c->nx_obs_pts; a.nyo = c->ny_obs_pts; a.nx_obs = c->nx_obs; a.ny_obs = c->ny_obs;
+    a.n_obs_steps = c->n_obs_steps; a.n_obs = 3 * c->n_obs_steps * c->nx_obs_pts * c->ny_obs_pts;
+    a.i_min = c->i_min; a.i_max = c->i_max; a.j_min = c->j_min; a.j_max = c->j_max;
+    a.kmom = (real)bcn_mixing_kmom(c->re);
+    a.ksc = (real)bcn_mixing_ksc(c->pe);
+    e->prm_cfg[0] = c->re; e->prm_cfg[1] = c->pe; e->prm_aux[0] = c->re; e->prm_aux[1] = c->u_max;
+    a.u_max = (real)bcn_mixing_u_max(c->re, c->re, c->u_max); a.ref_c = (real)c->ref_c; a.C0 = (real)c->C0;
+    e->n_obs = a.n_obs; e->n_act = 1; e->ndt_act = a.ndt_act;
+  });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -322,22 +328,20 @@ struct Env1D : bcn_env_s {
   Env1DArgs<real> a{};
   int nfields = 4;
   int nact = 1;                    // columns of a_last / a_prev
-  uint64_t cfg_hash = 0;           // of the constructor's cfg (bcn_snapshot_signature)
   DevBuf fields, a_last, a_prev, stpbuf, nctrbuf;
-  const char* kname = "";
-  int shape_k = 0, shape_nt = 0;   // of the last step launch (bcn_kernel_shape); 0, 0 before the first step
+  const char* general = "";        // name of the env's general step kernel
+  Env1DLaunch last;                // what the last step launched (env1d_step_t); nothing before the first step and after a failed one
 
-  int init(int n_actions) {
+  int init() {
     int rc;
-    nact = n_actions;
     const size_t per = (size_t)batch * a.n * sizeof(real);
     if ((rc = fields.alloc(4 * per))) return rc;
     BCN_HIP(hipMemset(fields.p, 0, 4 * per));
     real* f = static_cast<real*>(fields.p);
     const size_t n = (size_t)batch * a.n;
     a.f0 = f; a.f1 = f + n; a.f2 = f + 2 * n; a.f3 = f + 3 * n;
-    if ((rc = a_last.alloc((size_t)batch * n_actions * sizeof(real)))) return rc;
-    if ((rc = a_prev.alloc((size_t)batch * n_actions * sizeof(real)))) return rc;
+    if ((rc = a_last.alloc((size_t)batch * nact * sizeof(real)))) return rc;
+    if ((rc = a_prev.alloc((size_t)batch * nact * sizeof(real)))) return rc;
     BCN_HIP(hipMemset(a_last.p, 0, a_last.bytes));
     BCN_HIP(hipMemset(a_prev.p, 0, a_prev.bytes));
     a.a_last = static_cast<real*>(a_last.p);
@@ -363,27 +367,14 @@ struct Env1D : bcn_env_s {
     return BCN_OK;
   }
   size_t state_elems() const override { return (size_t)nfields * a.n; }
-  int copy_state(void* buf, int is_device, hipStream_t s, bool out) {
-    const size_t row = (size_t)a.n * sizeof(real);
-    real* f = static_cast<real*>(fields.p);
-    for (int k = 0; k < nfields; k++) {
-      char* ext = static_cast<char*>(buf) + (size_t)k * row;
-      real* dev = f + (size_t)k * batch * a.n;
-      hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : (out ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice);
-      if (out) BCN_HIP(hipMemcpy2DAsync(ext, nfields * row, dev, row, row, batch, kind, s));
-      else BCN_HIP(hipMemcpy2DAsync(dev, row, ext, nfields * row, row, batch, kind, s));
-    }
-    if (!is_device) BCN_HIP(hipStreamSynchronize(s));
-    return BCN_OK;
+  int get_state(void* buf, int is_device, hipStream_t s) override {
+    return copy_planes(buf, fields.p, nfields, (size_t)a.n * sizeof(real), batch, is_device, s, true);
   }
-  int get_state(void* buf, int is_device, hipStream_t s) override { return copy_state(buf, is_device, s, true); }
   int set_state(const void* buf, int is_device, hipStream_t s) override {
-    return copy_state(const_cast<void*>(buf), is_device, s, false);
+    return copy_planes(const_cast<void*>(buf), fields.p, nfields, (size_t)a.n * sizeof(real), batch, is_device, s, false);
   }
-  const char* kernel_name() const override { return kname; }
-  void note_kernel(const char* n) override { kname = n; }
-  void note_shape(int k, int nt) override { shape_k = k; shape_nt = nt; }
-  void kernel_shape(int* k, int* nt) const override { *k = shape_k; *nt = shape_nt; }
+  const char* kernel_name() const override { return last.name ? last.name : general; }
+  void kernel_shape(int* k, int* nt) const override { *k = last.k; *nt = last.nt; }
   void set_mask(const uint8_t* m) override { a.mask = m; }
   void use_params(const void* table) override { a.prm = static_cast<const real*>(table); }
   int set_option(const char* name, int value) override {
@@ -395,67 +386,49 @@ struct Env1D : bcn_env_s {
 
 template <typename real>
 int make_burgers(const bcn_burgers_cfg* c, int batch, int dtype, int device, bcn_env_t* out) {
-  auto* e = new (std::nothrow) Env1D<real>();
-  if (!e) { bcn_set_error("out of host memory"); return BCN_ERR_ARG; }
-  e->kind = BCN_BURGERS; e->batch = batch; e->dtype = dtype; e->device = device; e->esz = sizeof(real);
-  e->nfields = 3; e->kname = "burgers_step_k";
-  Env1DArgs<real>& a = e->a;
-  a.n = a.nx = c->nx; a.ndt_act = c->ndt_act; a.n_act = c->n_act; a.n_obs = c->n_obs_pts;
-  a.ctrl_pos = c->ctrl_pos; a.n_obs_pts = c->n_obs_pts;
-  a.u_target = (real)c->u_target; a.amp = (real)c->amp;
-  e->prm_cfg[0] = c->u_target; e->prm_cfg[1] = c->amp;
-  a.dx = (real)c->dx; a.rdx = (real)(1.0 / c->dx); a.dt = (real)c->dt;
-  e->n_obs = c->n_obs_pts; e->n_act = 1; e->ndt_act = a.ndt_act;
-  e->cfg_hash = snap_cfg_hash<bcn_burgers_cfg, 5, 4>(c);
-  int rc = e->init(1);
-  if (rc) { delete e; return rc; }
-  *out = e;
-  return BCN_OK;
+  return make_env<Env1D<real>>(BCN_BURGERS, batch, dtype, device, snap_cfg_hash<bcn_burgers_cfg, 5, 4>(c), out, [c](Env1D<real>* e) {
+    e->nfields = 3; e->nact = 1; e->general = "burgers_step_k";
+    Env1DArgs<real>& a = e->a;
+    a.n = a.nx = c->nx; a.ndt_act = c->ndt_act; a.n_act = c->n_act; a.n_obs = c->n_obs_pts;
+    a.ctrl_pos = c->ctrl_pos; a.n_obs_pts = c->n_obs_pts;
+    a.u_target = (real)c->u_target; a.amp = (real)c->amp;
+    e->prm_cfg[0] = c->u_target; e->prm_cfg[1] = c->amp;
+    a.dx = (real)c->dx; a.rdx = (real)(1.0 / c->dx); a.dt = (real)c->dt;
+    e->n_obs = c->n_obs_pts; e->n_act = 1; e->ndt_act = a.ndt_act;
+  });
 }
 
 template <typename real>
 int make_shkadov(const bcn_shkadov_cfg* c, int batch, int dtype, int device, bcn_env_t* out) {
-  auto* e = new (std::nothrow) Env1D<real>();
-  if (!e) { bcn_set_error("out of host memory"); return BCN_ERR_ARG; }
-  e->kind = BCN_SHKADOV; e->batch = batch; e->dtype = dtype; e->device = device; e->esz = sizeof(real);
-  e->nfields = 4; e->kname = "shkadov_step_k";
-  Env1DArgs<real>& a = e->a;
-  a.n = a.nx = c->nx; a.ndt_act = c->ndt_act; a.n_act = c->n_act; a.n_obs = c->n_obs * c->n_jets;
-  a.n_jets = c->n_jets; a.jet_pos = c->jet_pos; a.jet_hw = c->jet_hw; a.jet_space = c->jet_space;
-  a.l_obs = c->l_obs; a.l_rwd = c->l_rwd; a.n_obs_jet = c->n_obs; a.obs_stride = c->obs_stride;
-  a.n_interp = c->n_interp;
-  a.delta_p = (real)bcn_shkadov_delta_p(c->delta);
-  e->prm_cfg[0] = c->delta;
-  a.jet_amp = (real)c->jet_amp; a.eps = (real)c->eps; a.h_blow = (real)c->h_blow;
-  a.blowup_rwd = (real)c->blowup_rwd;
-  a.dx = (real)c->dx; a.rdx = (real)(1.0 / c->dx); a.dt = (real)c->dt;
-  e->n_obs = a.n_obs; e->n_act = c->n_jets; e->ndt_act = a.ndt_act;
-  e->cfg_hash = snap_cfg_hash<bcn_shkadov_cfg, 12, 7>(c);
-  int rc = e->init(c->n_jets);
-  if (rc) { delete e; return rc; }
-  *out = e;
-  return BCN_OK;
+  return make_env<Env1D<real>>(BCN_SHKADOV, batch, dtype, device, snap_cfg_hash<bcn_shkadov_cfg, 12, 7>(c), out, [c](Env1D<real>* e) {
+    e->nfields = 4; e->nact = c->n_jets; e->general = "shkadov_step_k";
+    Env1DArgs<real>& a = e->a;
+    a.n = a.nx = c->nx; a.ndt_act = c->ndt_act; a.n_act = c->n_act; a.n_obs = c->n_obs * c->n_jets;
+    a.n_jets = c->n_jets; a.jet_pos = c->jet_pos; a.jet_hw = c->jet_hw; a.jet_space = c->jet_space;
+    a.l_obs = c->l_obs; a.l_rwd = c->l_rwd; a.n_obs_jet = c->n_obs; a.obs_stride = c->obs_stride;
+    a.n_interp = c->n_interp;
+    a.delta_p = (real)bcn_shkadov_delta_p(c->delta);
+    e->prm_cfg[0] = c->delta;
+    a.jet_amp = (real)c->jet_amp; a.eps = (real)c->eps; a.h_blow = (real)c->h_blow;
+    a.blowup_rwd = (real)c->blowup_rwd;
+    a.dx = (real)c->dx; a.rdx = (real)(1.0 / c->dx); a.dt = (real)c->dt;
+    e->n_obs = a.n_obs; e->n_act = c->n_jets; e->ndt_act = a.ndt_act;
+  });
 }
 
 template <typename real>
 int make_sloshing(const bcn_sloshing_cfg* c, int batch, int dtype, int device, bcn_env_t* out) {
-  auto* e = new (std::nothrow) Env1D<real>();
-  if (!e) { bcn_set_error("out of host memory"); return BCN_ERR_ARG; }
-  e->kind = BCN_SLOSHING; e->batch = batch; e->dtype = dtype; e->device = device; e->esz = sizeof(real);
-  e->nfields = 4; e->kname = "sloshing_step_k";
-  Env1DArgs<real>& a = e->a;
-  a.nx = c->nx; a.n = c->nx + 2; a.ndt_act = c->ndt_act; a.n_act = c->n_act;
-  a.n_obs = c->nx / 2 + (c->nx % 2 ? 1 : 0);
-  a.n_interp = c->n_interp;
-  a.g = (real)c->g; a.amp = (real)c->amp; a.alpha = (real)c->alpha;
-  e->prm_cfg[0] = c->amp; e->prm_cfg[1] = c->alpha; e->prm_cfg[2] = c->g;
-  a.dx = (real)c->dx; a.rdx = (real)(1.0 / c->dx); a.dt = (real)c->dt;
-  e->n_obs = a.n_obs; e->n_act = 1; e->ndt_act = a.ndt_act;
-  e->cfg_hash = snap_cfg_hash<bcn_sloshing_cfg, 4, 5>(c);
-  int rc = e->init(1);
-  if (rc) { delete e; return rc; }
-  *out = e;
-  return BCN_OK;
+  return make_env<Env1D<real>>(BCN_SLOSHING, batch, dtype, device, snap_cfg_hash<bcn_sloshing_cfg, 4, 5>(c), out, [c](Env1D<real>* e) {
+    e->nfields = 4; e->nact = 1; e->general = "sloshing_step_k";
+    Env1DArgs<real>& a = e->a;
+    a.nx = c->nx; a.n = c->nx + 2; a.ndt_act = c->ndt_act; a.n_act = c->n_act;
+    a.n_obs = c->nx / 2 + (c->nx % 2 ? 1 : 0);
+    a.n_interp = c->n_interp;
+    a.g = (real)c->g; a.amp = (real)c->amp; a.alpha = (real)c->alpha;
+    e->prm_cfg[0] = c->amp; e->prm_cfg[1] = c->alpha; e->prm_cfg[2] = c->g;
+    a.dx = (real)c->dx; a.rdx = (real)(1.0 / c->dx); a.dt = (real)c->dt;
+    e->n_obs = a.n_obs; e->n_act = 1; e->ndt_act = a.ndt_act;
+  });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -466,7 +439,6 @@ struct OdeEnv : bcn_env_s {
   OdeArgs<real> a{};
   DevBuf st, iubuf, stpbuf, stage;   // stage: [B][n_state] rows of a host-side state copy
   int nreal = 0, nstate = 0;
-  uint64_t cfg_hash = 0;           // of the constructor's cfg (bcn_snapshot_signature)
 
   int init() {
     int rc;
@@ -524,50 +496,38 @@ struct OdeEnv : bcn_env_s {
 
 template <typename real>
 int make_lorenz(const bcn_lorenz_cfg* c, int batch, int dtype, int device, bcn_env_t* out) {
-  auto* e = new (std::nothrow) OdeEnv<real>();
-  if (!e) { bcn_set_error("out of host memory"); return BCN_ERR_ARG; }
-  e->kind = BCN_LORENZ; e->batch = batch; e->dtype = dtype; e->device = device; e->esz = sizeof(real);
-  e->nreal = LZ_NREAL; e->nstate = LZ_NSTATE;
-  OdeArgs<real>& a = e->a;
-  a.kind = BCN_LORENZ; a.ndt_act = c->ndt_act; a.n_act = c->n_act;
-  a.dt = (real)c->dt; a.sigma = (real)c->sigma; a.rho = (real)c->rho; a.beta = (real)c->beta;
-  e->prm_cfg[0] = c->sigma; e->prm_cfg[1] = c->rho; e->prm_cfg[2] = c->beta;
-  e->n_obs = 6; e->n_act = 1; e->ndt_act = c->ndt_act;
-  e->cfg_hash = snap_cfg_hash<bcn_lorenz_cfg, 2, 4>(c);
-  int rc = e->init();
-  if (rc) { delete e; return rc; }
-  *out = e;
-  return BCN_OK;
+  return make_env<OdeEnv<real>>(BCN_LORENZ, batch, dtype, device, snap_cfg_hash<bcn_lorenz_cfg, 2, 4>(c), out, [c](OdeEnv<real>* e) {
+    e->nreal = LZ_NREAL; e->nstate = LZ_NSTATE;
+    OdeArgs<real>& a = e->a;
+    a.kind = BCN_LORENZ; a.ndt_act = c->ndt_act; a.n_act = c->n_act;
+    a.dt = (real)c->dt; a.sigma = (real)c->sigma; a.rho = (real)c->rho; a.beta = (real)c->beta;
+    e->prm_cfg[0] = c->sigma; e->prm_cfg[1] = c->rho; e->prm_cfg[2] = c->beta;
+    e->n_obs = 6; e->n_act = 1; e->ndt_act = c->ndt_act;
+  });
 }
 
 template <typename real>
 int make_vortex(const bcn_vortex_cfg* c, int batch, int dtype, int device, bcn_env_t* out) {
-  auto* e = new (std::nothrow) OdeEnv<real>();
-  if (!e) { bcn_set_error("out of host memory"); return BCN_ERR_ARG; }
-  e->kind = BCN_VORTEX; e->batch = batch; e->dtype = dtype; e->device = device; e->esz = sizeof(real);
-  e->nreal = VX_NREAL; e->nstate = VX_NSTATE;
-  OdeArgs<real>& a = e->a;
-  a.kind = BCN_VORTEX; a.ndt_act = c->ndt_act; a.n_act = c->n_act;
-  a.dt = (real)c->dt;
-  a.lmbda_re = (real)c->lmbda_re; a.lmbda_cx = (real)c->lmbda_cx; a.mu_re = (real)c->mu_re; a.mu_cx = (real)c->mu_cx;
-  a.alpha_re = (real)c->alpha_re; a.alpha_cx = (real)c->alpha_cx;
-  // the derived constants of vortex.py:26-42, in double and in the reference's order
-  a.ire = (real)bcn_vortex_ire(c->re_crit, c->re);
-  e->prm_cfg[0] = c->re; e->prm_cfg[1] = c->weight; e->prm_aux[0] = c->re_crit;
-  a.omega_f = (real)c->omega_f;
-  a.m_omega_f_gamma = (real)(-c->omega_f * c->gamma);
-  a.domega = (real)(c->omega_s - c->omega_f);
-  a.beta_m = (real)(c->beta / (c->omega_f * c->mass));
-  a.mod_min = (real)c->mod_min; a.dmod = (real)(c->mod_max - c->mod_min);
-  a.phase_min = (real)c->phase_min; a.dphase = (real)(c->phase_max - c->phase_min);
-  a.rwd_k = (real)(2.0 * c->omega_s * c->gamma);
-  a.weight = (real)c->weight;
-  e->n_obs = 8; e->n_act = 2; e->ndt_act = c->ndt_act;
-  e->cfg_hash = snap_cfg_hash<bcn_vortex_cfg, 2, 19>(c);
-  int rc = e->init();
-  if (rc) { delete e; return rc; }
-  *out = e;
-  return BCN_OK;
+  return make_env<OdeEnv<real>>(BCN_VORTEX, batch, dtype, device, snap_cfg_hash<bcn_vortex_cfg, 2, 19>(c), out, [c](OdeEnv<real>* e) {
+    e->nreal = VX_NREAL; e->nstate = VX_NSTATE;
+    OdeArgs<real>& a = e->a;
+    a.kind = BCN_VORTEX; a.ndt_act = c->ndt_act; a.n_act = c->n_act;
+    a.dt = (real)c->dt;
+    a.lmbda_re = (real)c->lmbda_re; a.lmbda_cx = (real)c->lmbda_cx; a.mu_re = (real)c->mu_re; a.mu_cx = (real)c->mu_cx;
+    a.alpha_re = (real)c->alpha_re; a.alpha_cx = (real)c->alpha_cx;
+    // the derived constants of vortex.py:26-42, in double and in the reference's order
+    a.ire = (real)bcn_vortex_ire(c->re_crit, c->re);
+    e->prm_cfg[0] = c->re; e->prm_cfg[1] = c->weight; e->prm_aux[0] = c->re_crit;
+    a.omega_f = (real)c->omega_f;
+    a.m_omega_f_gamma = (real)(-c->omega_f * c->gamma);
+    a.domega = (real)(c->omega_s - c->omega_f);
+    a.beta_m = (real)(c->beta / (c->omega_f * c->mass));
+    a.mod_min = (real)c->mod_min; a.dmod = (real)(c->mod_max - c->mod_min);
+    a.phase_min = (real)c->phase_min; a.dphase = (real)(c->phase_max - c->phase_min);
+    a.rwd_k = (real)(2.0 * c->omega_s * c->gamma);
+    a.weight = (real)c->weight;
+    e->n_obs = 8; e->n_act = 2; e->ndt_act = c->ndt_act;
+  });
 }
 
 template <typename real>
@@ -636,6 +596,24 @@ static Env1DArgs<real>& env1d_io(bcn_env_t h, const void* actions, const void* n
   return a;
 }
 
+template <typename real>
+static int env1d_reset_t(bcn_env_t h, int (*launch)(const Env1DArgs<real>&, int, hipStream_t), const void* init, void* obs, void* stream) {
+  DeviceGuard g(h->device);
+  return launch(env1d_io<real>(h, nullptr, nullptr, init, obs, nullptr, nullptr, nullptr, nullptr), h->batch, static_cast<hipStream_t>(stream));
+}
+
+// The step of a 1D env: the launcher says which kernel it dispatched through its return path (Env1DLaunch), and the handle keeps
+// that for bcn_kernel_name / bcn_kernel_shape; a launcher that failed leaves the general name and (0, 0)
+template <typename real>
+static int env1d_step_t(bcn_env_t h, int (*launch)(const Env1DArgs<real>&, int, hipStream_t, Env1DLaunch*), const void* actions,
+                        const void* noise, void* obs, void* rwd, uint8_t* done, uint8_t* trunc, int32_t* status, void* stream) {
+  DeviceGuard g(h->device);
+  Env1DLaunch note;
+  const int rc = launch(env1d_io<real>(h, actions, noise, nullptr, obs, rwd, done, trunc, status), h->batch, static_cast<hipStream_t>(stream), &note);
+  static_cast<Env1D<real>*>(h)->last = rc ? Env1DLaunch() : note;
+  return rc;
+}
+
 // ------------------------------------------------------------------------------------------
 // snapshots (snapshot.h): which arrays of a handle are state, and where they sit in a snapshot of n replicas
 // ------------------------------------------------------------------------------------------
@@ -671,37 +649,16 @@ int snap_desc(bcn_env_t h, SnapDesc* d) {
   return n;
 }
 
-uint64_t snap_cfg_of(bcn_env_t h) {
-  if (h->kind == BCN_RAYLEIGH || h->kind == BCN_MIXING)
-    return h->dtype == BCN_F32 ? static_cast<NS2DEnv<float>*>(h)->cfg_hash : static_cast<NS2DEnv<double>*>(h)->cfg_hash;
-  if (h->kind == BCN_LORENZ || h->kind == BCN_VORTEX)
-    return h->dtype == BCN_F32 ? static_cast<OdeEnv<float>*>(h)->cfg_hash : static_cast<OdeEnv<double>*>(h)->cfg_hash;
-  return h->dtype == BCN_F32 ? static_cast<Env1D<float>*>(h)->cfg_hash : static_cast<Env1D<double>*>(h)->cfg_hash;
-}
-
 inline size_t snap_up16(size_t x) { return (x + 15) / 16 * 16; }
-
-// Byte offsets of the packed per-step outputs [obs | rwd | status | done | trunc] of the handle's batch (obs at 0), every part
-// 16-byte aligned: the layout of the callers' out_buf (bcn_snapshot_save, bcn_episode_track)
-struct OutOffsets { size_t rwd, status, done, trunc; };
-inline OutOffsets out_offsets(bcn_env_t h) {
-  const size_t B = (size_t)h->batch, esz = h->esz;
-  OutOffsets o;
-  o.rwd = snap_up16(B * h->n_obs * esz);
-  o.status = snap_up16(o.rwd + B * esz);
-  o.done = snap_up16(o.status + B * 4);
-  o.trunc = snap_up16(o.done + B);
-  return o;
-}
 
 // Lays out a snapshot of n replicas of this handle's configuration: the bytes it takes, optionally the named segments (`lay`, up to
 // max_lay; the count is returned) and the kernels' table `t` (handle side: this handle's arrays and the packed output buffer
 // `out_buf` of its `batch` replicas; NULL out_buf leaves the five output segments out of the copy).
 int snap_build(bcn_env_t h, int n, char* out_buf, SnapTable* t, bcn_snapshot_seg* lay, int max_lay, size_t* bytes) {
   SnapDesc d[16];
-  int nd = h->dtype == BCN_F32 ? snap_desc<float>(h, d) : snap_desc<double>(h, d);
+  int nd = BCN_BY_DTYPE(h->dtype, snap_desc, h, d);
   const size_t B = (size_t)h->batch, esz = h->esz;
-  const OutOffsets o = out_offsets(h);
+  const bcn_out_layout_t o = bcn_out_layout(B, (size_t)h->n_obs, esz);   // the callers' out_buf
   d[nd++] = {"obs", BCN_SNAP_REAL, 1, (size_t)h->n_obs, out_buf};
   d[nd++] = {"rwd", BCN_SNAP_REAL, 1, 1, out_buf ? out_buf + o.rwd : nullptr};
   d[nd++] = {"status", BCN_SNAP_I32, 1, 1, out_buf ? out_buf + o.status : nullptr};
@@ -731,7 +688,7 @@ int snap_build(bcn_env_t h, int n, char* out_buf, SnapTable* t, bcn_snapshot_seg
         blk += B * g.bpr;
       } else {
         g.bpr = 0;
-        g.unit = row % 16 == 0 ? 16 : row % 8 == 0 ? 8 : row % 4 == 0 ? 4 : 1;
+        g.unit = copy_unit(row);
         blk += (B * (row / g.unit) + BCN_SNAP_NT * 4 - 1) / (BCN_SNAP_NT * 4);
       }
       if (blk > 0x7fffffffull) { bcn_set_error("snapshot: batch too large for one launch"); return -1; }
@@ -798,25 +755,20 @@ int bcn_rayleigh_create(const bcn_rayleigh_cfg* c, int batch, int dtype, int dev
     return BCN_ERR_ARG;
   }
   DeviceGuard g(device);
-  return dtype == BCN_F32 ? make_rayleigh<float>(c, batch, dtype, device, out)
-                          : make_rayleigh<double>(c, batch, dtype, device, out);
+  return BCN_BY_DTYPE(dtype, make_rayleigh, c, batch, dtype, device, out);
 }
 
 int bcn_rayleigh_reset(bcn_env_t h, const void* init_fields_dev, void* obs_dev, void* stream) {
   BCN_CHECK_KIND(h, BCN_RAYLEIGH);
-  return h->dtype == BCN_F32 ? ns2d_reset_t<float>(h, init_fields_dev, obs_dev, stream)
-                             : ns2d_reset_t<double>(h, init_fields_dev, obs_dev, stream);
+  return BCN_BY_DTYPE(h->dtype, ns2d_reset_t, h, init_fields_dev, obs_dev, stream);
 }
 
 int bcn_rayleigh_step(bcn_env_t h, const void* actions_dev, void* actions_norm_dev, void* obs_dev, void* rwd_dev,
                       uint8_t* done_dev, uint8_t* trunc_dev, int32_t* status_dev, int32_t* sweeps_dev,
                       void* stream) {
   BCN_CHECK_KIND(h, BCN_RAYLEIGH);
-  return h->dtype == BCN_F32
-             ? ns2d_step_t<float>(h, actions_dev, nullptr, actions_norm_dev, obs_dev, rwd_dev, done_dev, trunc_dev,
-                                  status_dev, sweeps_dev, stream)
-             : ns2d_step_t<double>(h, actions_dev, nullptr, actions_norm_dev, obs_dev, rwd_dev, done_dev, trunc_dev,
-                                   status_dev, sweeps_dev, stream);
+  return BCN_BY_DTYPE(h->dtype, ns2d_step_t, h, actions_dev, nullptr, actions_norm_dev, obs_dev, rwd_dev, done_dev, trunc_dev, status_dev,
+                      sweeps_dev, stream);
 }
 
 // ---- mixing ----------------------------------------------------------------------------------
@@ -825,31 +777,22 @@ int bcn_mixing_create(const bcn_mixing_cfg* c, int batch, int dtype, int device,
   if (rc) return rc;
   if (c->nx < 2 || c->ny < 2 || c->ndt_act < 0) { bcn_set_error("mixing cfg out of range"); return BCN_ERR_ARG; }
   DeviceGuard g(device);
-  return dtype == BCN_F32 ? make_mixing<float>(c, batch, dtype, device, out)
-                          : make_mixing<double>(c, batch, dtype, device, out);
+  return BCN_BY_DTYPE(dtype, make_mixing, c, batch, dtype, device, out);
 }
 
 int bcn_mixing_reset(bcn_env_t h, void* obs_dev, void* stream) {
   BCN_CHECK_KIND(h, BCN_MIXING);
-  return h->dtype == BCN_F32 ? ns2d_reset_t<float>(h, nullptr, obs_dev, stream)
-                             : ns2d_reset_t<double>(h, nullptr, obs_dev, stream);
+  return BCN_BY_DTYPE(h->dtype, ns2d_reset_t, h, nullptr, obs_dev, stream);
 }
 
 int bcn_mixing_step(bcn_env_t h, const int32_t* actions_dev, void* obs_dev, void* rwd_dev, uint8_t* done_dev,
                     uint8_t* trunc_dev, int32_t* status_dev, int32_t* sweeps_dev, void* stream) {
   BCN_CHECK_KIND(h, BCN_MIXING);
-  return h->dtype == BCN_F32
-             ? ns2d_step_t<float>(h, nullptr, actions_dev, nullptr, obs_dev, rwd_dev, done_dev, trunc_dev,
-                                  status_dev, sweeps_dev, stream)
-             : ns2d_step_t<double>(h, nullptr, actions_dev, nullptr, obs_dev, rwd_dev, done_dev, trunc_dev,
-                                   status_dev, sweeps_dev, stream);
+  return BCN_BY_DTYPE(h->dtype, ns2d_step_t, h, nullptr, actions_dev, nullptr, obs_dev, rwd_dev, done_dev, trunc_dev, status_dev, sweeps_dev,
+                      stream);
 }
 
 // ---- 1D envs ---------------------------------------------------------------------------------
-#define BCN_1D_CALL(h, FN, ...)                                                                       \
-  (h->dtype == BCN_F32 ? FN<float>(env1d_io<float>(h, __VA_ARGS__), h->batch, static_cast<hipStream_t>(stream)) \
-                       : FN<double>(env1d_io<double>(h, __VA_ARGS__), h->batch, static_cast<hipStream_t>(stream)))
-
 int bcn_burgers_create(const bcn_burgers_cfg* c, int batch, int dtype, int device, bcn_env_t* out) {
   int rc = check_create(c, batch, dtype, device, out);
   if (rc) return rc;
@@ -858,25 +801,17 @@ int bcn_burgers_create(const bcn_burgers_cfg* c, int batch, int dtype, int devic
     return BCN_ERR_ARG;
   }
   DeviceGuard g(device);
-  return dtype == BCN_F32 ? make_burgers<float>(c, batch, dtype, device, out)
-                          : make_burgers<double>(c, batch, dtype, device, out);
+  return BCN_BY_DTYPE(dtype, make_burgers, c, batch, dtype, device, out);
 }
 int bcn_burgers_reset(bcn_env_t h, void* obs_dev, void* stream) {
   BCN_CHECK_KIND(h, BCN_BURGERS);
-  DeviceGuard g(h->device);
-  return BCN_1D_CALL(h, burgers_launch_reset, nullptr, nullptr, nullptr, obs_dev, nullptr, nullptr, nullptr, nullptr);
+  return BCN_BY_DTYPE(h->dtype, env1d_reset_t, h, burgers_launch_reset, nullptr, obs_dev, stream);
 }
 int bcn_burgers_step(bcn_env_t h, const void* actions_dev, const void* noise_dev, void* obs_dev, void* rwd_dev,
                      uint8_t* done_dev, uint8_t* trunc_dev, int32_t* status_dev, void* stream) {
   BCN_CHECK_KIND(h, BCN_BURGERS);
-  DeviceGuard g(h->device);
-  bcn_env1d_launched = nullptr;
-  bcn_env1d_shape_k = bcn_env1d_shape_nt = 0;
-  const int rc_ = BCN_1D_CALL(h, burgers_launch_step, actions_dev, noise_dev, nullptr, obs_dev, rwd_dev, done_dev, trunc_dev,
-                     status_dev);
-  h->note_kernel(bcn_env1d_launched ? bcn_env1d_launched : "burgers_step_k");
-  h->note_shape(bcn_env1d_shape_k, bcn_env1d_shape_nt);
-  return rc_;
+  return BCN_BY_DTYPE(h->dtype, env1d_step_t, h, burgers_launch_step, actions_dev, noise_dev, obs_dev, rwd_dev, done_dev, trunc_dev, status_dev,
+                      stream);
 }
 
 int bcn_shkadov_create(const bcn_shkadov_cfg* c, int batch, int dtype, int device, bcn_env_t* out) {
@@ -890,26 +825,17 @@ int bcn_shkadov_create(const bcn_shkadov_cfg* c, int batch, int dtype, int devic
     return BCN_ERR_ARG;
   }
   DeviceGuard g(device);
-  return dtype == BCN_F32 ? make_shkadov<float>(c, batch, dtype, device, out)
-                          : make_shkadov<double>(c, batch, dtype, device, out);
+  return BCN_BY_DTYPE(dtype, make_shkadov, c, batch, dtype, device, out);
 }
 int bcn_shkadov_reset(bcn_env_t h, const void* init_fields_dev, void* obs_dev, void* stream) {
   BCN_CHECK_KIND(h, BCN_SHKADOV);
-  DeviceGuard g(h->device);
-  return BCN_1D_CALL(h, shkadov_launch_reset, nullptr, nullptr, init_fields_dev, obs_dev, nullptr, nullptr, nullptr,
-                     nullptr);
+  return BCN_BY_DTYPE(h->dtype, env1d_reset_t, h, shkadov_launch_reset, init_fields_dev, obs_dev, stream);
 }
 int bcn_shkadov_step(bcn_env_t h, const void* actions_dev, const void* noise_dev, void* obs_dev, void* rwd_dev,
                      uint8_t* done_dev, uint8_t* trunc_dev, int32_t* status_dev, void* stream) {
   BCN_CHECK_KIND(h, BCN_SHKADOV);
-  DeviceGuard g(h->device);
-  bcn_env1d_launched = nullptr;
-  bcn_env1d_shape_k = bcn_env1d_shape_nt = 0;
-  const int rc_ = BCN_1D_CALL(h, shkadov_launch_step, actions_dev, noise_dev, nullptr, obs_dev, rwd_dev, done_dev, trunc_dev,
-                     status_dev);
-  h->note_kernel(bcn_env1d_launched ? bcn_env1d_launched : "shkadov_step_k");
-  h->note_shape(bcn_env1d_shape_k, bcn_env1d_shape_nt);
-  return rc_;
+  return BCN_BY_DTYPE(h->dtype, env1d_step_t, h, shkadov_launch_step, actions_dev, noise_dev, obs_dev, rwd_dev, done_dev, trunc_dev, status_dev,
+                      stream);
 }
 
 int bcn_sloshing_create(const bcn_sloshing_cfg* c, int batch, int dtype, int device, bcn_env_t* out) {
@@ -917,38 +843,28 @@ int bcn_sloshing_create(const bcn_sloshing_cfg* c, int batch, int dtype, int dev
   if (rc) return rc;
   if (c->nx < 4 || c->nx + 2 > 8192 || c->n_interp < 1) { bcn_set_error("sloshing cfg out of range"); return BCN_ERR_ARG; }
   DeviceGuard g(device);
-  return dtype == BCN_F32 ? make_sloshing<float>(c, batch, dtype, device, out)
-                          : make_sloshing<double>(c, batch, dtype, device, out);
+  return BCN_BY_DTYPE(dtype, make_sloshing, c, batch, dtype, device, out);
 }
 int bcn_sloshing_reset(bcn_env_t h, const void* init_fields_dev, void* obs_dev, void* stream) {
   BCN_CHECK_KIND(h, BCN_SLOSHING);
-  DeviceGuard g(h->device);
-  return BCN_1D_CALL(h, sloshing_launch_reset, nullptr, nullptr, init_fields_dev, obs_dev, nullptr, nullptr, nullptr,
-                     nullptr);
+  return BCN_BY_DTYPE(h->dtype, env1d_reset_t, h, sloshing_launch_reset, init_fields_dev, obs_dev, stream);
 }
 int bcn_sloshing_step(bcn_env_t h, const void* actions_dev, void* obs_dev, void* rwd_dev, uint8_t* done_dev,
                       uint8_t* trunc_dev, int32_t* status_dev, void* stream) {
   BCN_CHECK_KIND(h, BCN_SLOSHING);
-  DeviceGuard g(h->device);
-  bcn_env1d_launched = nullptr;
-  bcn_env1d_shape_k = bcn_env1d_shape_nt = 0;
-  const int rc_ = BCN_1D_CALL(h, sloshing_launch_step, actions_dev, nullptr, nullptr, obs_dev, rwd_dev, done_dev, trunc_dev,
-                     status_dev);
-  h->note_kernel(bcn_env1d_launched ? bcn_env1d_launched : "sloshing_step_k");
-  h->note_shape(bcn_env1d_shape_k, bcn_env1d_shape_nt);
-  return rc_;
+  return BCN_BY_DTYPE(h->dtype, env1d_step_t, h, sloshing_launch_step, actions_dev, nullptr, obs_dev, rwd_dev, done_dev, trunc_dev, status_dev,
+                      stream);
 }
 
 // ---- lorenz / vortex --------------------------------------------------------------------------
-#define BCN_ODE_CALL(h, ...) \
-  (h->dtype == BCN_F32 ? ode_call<float>(h, __VA_ARGS__) : ode_call<double>(h, __VA_ARGS__))
+#define BCN_ODE_CALL(h, ...) BCN_BY_DTYPE(h->dtype, ode_call, h, __VA_ARGS__)
 
 int bcn_lorenz_create(const bcn_lorenz_cfg* c, int batch, int dtype, int device, bcn_env_t* out) {
   int rc = check_create(c, batch, dtype, device, out);
   if (rc) return rc;
   if (c->ndt_act < 1 || c->n_act < 1 || !(c->dt > 0)) { bcn_set_error("lorenz cfg out of range (ndt_act, n_act >= 1, dt > 0)"); return BCN_ERR_ARG; }
   DeviceGuard g(device);
-  return dtype == BCN_F32 ? make_lorenz<float>(c, batch, dtype, device, out) : make_lorenz<double>(c, batch, dtype, device, out);
+  return BCN_BY_DTYPE(dtype, make_lorenz, c, batch, dtype, device, out);
 }
 int bcn_lorenz_reset(bcn_env_t h, void* obs_dev, void* stream) {
   BCN_CHECK_KIND(h, BCN_LORENZ);
@@ -968,7 +884,7 @@ int bcn_vortex_create(const bcn_vortex_cfg* c, int batch, int dtype, int device,
     return BCN_ERR_ARG;
   }
   DeviceGuard g(device);
-  return dtype == BCN_F32 ? make_vortex<float>(c, batch, dtype, device, out) : make_vortex<double>(c, batch, dtype, device, out);
+  return BCN_BY_DTYPE(dtype, make_vortex, c, batch, dtype, device, out);
 }
 int bcn_vortex_reset(bcn_env_t h, void* obs_dev, void* stream) {
   BCN_CHECK_KIND(h, BCN_VORTEX);
@@ -1091,8 +1007,7 @@ int bcn_set_params(bcn_env_t h, const double* values_host, void* stream) {
       if (d->positive[k] && !(v > 0.0)) { bcn_set_error("bcn_set_params: %s of replica %zu must be > 0 (%g)", d->name[k], b, v); return BCN_ERR_ARG; }
     }
   std::vector<char> table;
-  if (h->dtype == BCN_F32) params_table<float>(h, values_host, table);
-  else params_table<double>(h, values_host, table);
+  BCN_BY_DTYPE(h->dtype, params_table, h, values_host, table);
   double* keep = new (std::nothrow) double[(size_t)d->n * B];
   if (!keep) { bcn_set_error("out of host memory"); return BCN_ERR_ARG; }
   memcpy(keep, values_host, (size_t)d->n * B * sizeof(double));
@@ -1143,8 +1058,7 @@ uint64_t bcn_snapshot_signature(bcn_env_t h) {
   const int nd = snap_build(h, 1, nullptr, nullptr, lay, 16, nullptr);
   const int32_t head[2] = {h->kind, h->dtype};
   uint64_t sig = snap_fnv(14695981039346656037ull, head, sizeof(head));
-  const uint64_t cfg = snap_cfg_of(h);
-  sig = snap_fnv(sig, &cfg, sizeof(cfg));
+  sig = snap_fnv(sig, &h->cfg_hash, sizeof(h->cfg_hash));
   for (int k = 0; k < nd && k < 16; k++) {
     sig = snap_fnv(sig, lay[k].name, sizeof(lay[k].name));
     sig = snap_fnv(sig, &lay[k].elem, sizeof(int32_t));
@@ -1195,7 +1109,7 @@ int bcn_episode_track(bcn_env_t h, const void* out_buf_dev, void* ep_buf_dev, co
   bcn_snapshot_seg lay[BCN_EP_NSEG];
   if (episode_build(h, lay, nullptr) < 0) return BCN_ERR_ARG;
   const size_t B = (size_t)h->batch, row = (size_t)h->n_obs * h->esz;
-  const OutOffsets o = out_offsets(h);
+  const bcn_out_layout_t o = bcn_out_layout(B, (size_t)h->n_obs, h->esz);
   const char* out = static_cast<const char*>(out_buf_dev);
   char* ep = static_cast<char*>(ep_buf_dev);
   EpisodeArgs a;
@@ -1209,7 +1123,7 @@ int bcn_episode_track(bcn_env_t h, const void* out_buf_dev, void* ep_buf_dev, co
   a.final_obs = ep + lay[8].offset;
   a.batch = (unsigned)B;
   a.nbk = (unsigned)((B + BCN_EP_NT - 1) / BCN_EP_NT);
-  a.unit = row % 16 == 0 ? 16 : row % 8 == 0 ? 8 : 4;      // rows are reals: multiples of 4 bytes
+  a.unit = copy_unit(row);      // rows are reals: multiples of 4 bytes
   a.upr = (unsigned)(row / a.unit);
   a.total = (unsigned)(B * a.upr);
   a.f64 = h->dtype == BCN_F64;

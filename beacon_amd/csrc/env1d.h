@@ -71,13 +71,16 @@ __device__ __forceinline__ real bcn_device_noise(const Env1DArgs<real>& A, int b
   return (real(2) * r - real(1)) * A.nsigma;
 }
 
-// name of the step kernel the last *_launch_step of this thread dispatched when it is not the env's general one (else nullptr)
-extern thread_local const char* bcn_env1d_launched;
-// ... and the shape of that launch: cells per thread K and threads per replica NT of the instantiation (bcn_kernel_shape)
-extern thread_local int bcn_env1d_shape_k, bcn_env1d_shape_nt;
-template <typename real> int burgers_launch_step(const Env1DArgs<real>& a, int batch, hipStream_t s);
+// What a *_launch_step dispatched, written by the launcher for its caller (host side only, as NS2DHost is for the 2D envs): the
+// kernel's name when it is not the env's general one (else nullptr), and the shape of the instantiation -- cells per thread K and
+// threads per replica NT (bcn_kernel_shape)
+struct Env1DLaunch {
+  const char* name = nullptr;
+  int k = 0, nt = 0;
+};
+template <typename real> int burgers_launch_step(const Env1DArgs<real>& a, int batch, hipStream_t s, Env1DLaunch* note);
 template <typename real> int burgers_launch_reset(const Env1DArgs<real>& a, int batch, hipStream_t s);
-template <typename real> int shkadov_launch_step(const Env1DArgs<real>& a, int batch, hipStream_t s);
+template <typename real> int shkadov_launch_step(const Env1DArgs<real>& a, int batch, hipStream_t s, Env1DLaunch* note);
 template <typename real> int shkadov_launch_reset(const Env1DArgs<real>& a, int batch, hipStream_t s);
-template <typename real> int sloshing_launch_step(const Env1DArgs<real>& a, int batch, hipStream_t s);
+template <typename real> int sloshing_launch_step(const Env1DArgs<real>& a, int batch, hipStream_t s, Env1DLaunch* note);
 template <typename real> int sloshing_launch_reset(const Env1DArgs<real>& a, int batch, hipStream_t s);

@@ -1234,23 +1234,23 @@ inline int pick_k_onewave(int n, int one_wave) {
   return n <= 64 ? 1 : (n <= 128 ? 2 : (n <= 256 ? 4 : 8));
 }
 
-// (K, NT) of the instantiation that is launched goes to bcn_env1d_shape_* (env1d.h): bcn_kernel_shape reports it
-#define BCN_LAUNCH_NT_(KERNEL, K_, NT_, A, BATCH, STREAM)                                                       \
+// (K, NT) of the instantiation that is launched goes to the caller's Env1DLaunch (env1d.h): bcn_kernel_shape reports it
+#define BCN_LAUNCH_NT_(KERNEL, K_, NT_, A, BATCH, STREAM, NOTE)                                                 \
   do {                                                                                                          \
     hipLaunchKernelGGL((KERNEL<real, K_, NT_>), dim3(BATCH), dim3(NT_), 0, STREAM, A);                          \
-    bcn_env1d_shape_k = K_; bcn_env1d_shape_nt = NT_;                                                           \
+    (NOTE)->k = K_; (NOTE)->nt = NT_;                                                                           \
   } while (0)
-#define BCN_LAUNCH_NT(KERNEL, K_, A, BATCH, STREAM)                                                             \
+#define BCN_LAUNCH_NT(KERNEL, K_, A, BATCH, STREAM, NOTE)                                                       \
   do {                                                                                                          \
     const int n__ = (A).n;                                                                                      \
-    if (n__ <= K_ * 64) BCN_LAUNCH_NT_(KERNEL, K_, 64, A, BATCH, STREAM);                                       \
-    else if (n__ <= K_ * 128) BCN_LAUNCH_NT_(KERNEL, K_, 128, A, BATCH, STREAM);                                \
-    else if (n__ <= K_ * 256) BCN_LAUNCH_NT_(KERNEL, K_, 256, A, BATCH, STREAM);                                \
-    else if (n__ <= K_ * 512) BCN_LAUNCH_NT_(KERNEL, K_, 512, A, BATCH, STREAM);                                \
-    else BCN_LAUNCH_NT_(KERNEL, K_, 1024, A, BATCH, STREAM);                                                    \
+    if (n__ <= K_ * 64) BCN_LAUNCH_NT_(KERNEL, K_, 64, A, BATCH, STREAM, NOTE);                                 \
+    else if (n__ <= K_ * 128) BCN_LAUNCH_NT_(KERNEL, K_, 128, A, BATCH, STREAM, NOTE);                          \
+    else if (n__ <= K_ * 256) BCN_LAUNCH_NT_(KERNEL, K_, 256, A, BATCH, STREAM, NOTE);                          \
+    else if (n__ <= K_ * 512) BCN_LAUNCH_NT_(KERNEL, K_, 512, A, BATCH, STREAM, NOTE);                          \
+    else BCN_LAUNCH_NT_(KERNEL, K_, 1024, A, BATCH, STREAM, NOTE);                                              \
   } while (0)
 
-#define BCN_DISPATCH_1D(KERNEL, A, BATCH, STREAM, ONEWAVE_OK)                                  \
+#define BCN_DISPATCH_1D(KERNEL, A, BATCH, STREAM, ONEWAVE_OK, NOTE)                            \
   do {                                                                                         \
     if ((A).n > 8 * 1024) {                                                                    \
       bcn_set_error("1D grid of %d cells exceeds the 8192-cell kernel limit", (A).n);          \
@@ -1260,24 +1260,23 @@ inline int pick_k_onewave(int n, int one_wave) {
     if (k__ == 0) k__ = pick_k((A).n, BATCH, (A).force_k);                                     \
     while ((A).n > k__ * 1024) k__ *= 2;                                                       \
     switch (k__) {                                                                             \
-      case 1: BCN_LAUNCH_NT(KERNEL, 1, A, BATCH, STREAM); break;                               \
-      case 2: BCN_LAUNCH_NT(KERNEL, 2, A, BATCH, STREAM); break;                               \
-      case 4: BCN_LAUNCH_NT(KERNEL, 4, A, BATCH, STREAM); break;                               \
-      default: BCN_LAUNCH_NT(KERNEL, 8, A, BATCH, STREAM); break;                              \
+      case 1: BCN_LAUNCH_NT(KERNEL, 1, A, BATCH, STREAM, NOTE); break;                         \
+      case 2: BCN_LAUNCH_NT(KERNEL, 2, A, BATCH, STREAM, NOTE); break;                         \
+      case 4: BCN_LAUNCH_NT(KERNEL, 4, A, BATCH, STREAM, NOTE); break;                         \
+      default: BCN_LAUNCH_NT(KERNEL, 8, A, BATCH, STREAM, NOTE); break;                        \
     }                                                                                          \
     BCN_HIP(hipGetLastError());                                                                \
   } while (0)
 
 }  // namespace
 
-template <typename real> int burgers_launch_step(const Env1DArgs<real>& a, int batch, hipStream_t s) {
+template <typename real> int burgers_launch_step(const Env1DArgs<real>& a, int batch, hipStream_t s, Env1DLaunch* note) {
 #ifdef BCN_ENV1D_FLOAT
   if constexpr (std::is_same<real, float>::value) {   // float32, 129 .. 511 cells that do not fill the wave (the reference's nx = 500): packed, with masks
     if (a.one_wave == 1 && a.force_k == 0 && a.n > 128 && a.n < 512 && a.n != 256 && a.ctrl_pos >= a.n_obs_pts && a.ctrl_pos <= a.n) {
       if (a.n > 256) hipLaunchKernelGGL((burgers_step_pk_k<8, false>), dim3(batch), dim3(64), 0, s, a);
       else hipLaunchKernelGGL((burgers_step_pk_k<4, false>), dim3(batch), dim3(64), 0, s, a);
-      bcn_env1d_launched = "burgers_step_pk_k";
-      bcn_env1d_shape_k = a.n > 256 ? 8 : 4; bcn_env1d_shape_nt = 64;
+      *note = {"burgers_step_pk_k", a.n > 256 ? 8 : 4, 64};
       BCN_HIP(hipGetLastError());
       return BCN_OK;
     }
@@ -1290,8 +1289,7 @@ template <typename real> int burgers_launch_step(const Env1DArgs<real>& a, int b
       if (a.one_wave == 1 && (a.n == 512 || a.n == 256) && a.ctrl_pos >= a.n_obs_pts && a.ctrl_pos <= a.n) {
         if (a.n == 512) hipLaunchKernelGGL((burgers_step_pk_k<8, true>), dim3(batch), dim3(64), 0, s, a);
         else hipLaunchKernelGGL((burgers_step_pk_k<4, true>), dim3(batch), dim3(64), 0, s, a);
-        bcn_env1d_launched = "burgers_step_pk_k";
-        bcn_env1d_shape_k = a.n / 64; bcn_env1d_shape_nt = 64;
+        *note = {"burgers_step_pk_k", a.n / 64, 64};
         BCN_HIP(hipGetLastError());
         return BCN_OK;
       }
@@ -1300,11 +1298,11 @@ template <typename real> int burgers_launch_step(const Env1DArgs<real>& a, int b
     if (a.n == 512) hipLaunchKernelGGL((burgers_step_k<real, 8, 64, true>), dim3(batch), dim3(64), 0, s, a);
     else if (a.n == 256) hipLaunchKernelGGL((burgers_step_k<real, 4, 64, true>), dim3(batch), dim3(64), 0, s, a);
     else hipLaunchKernelGGL((burgers_step_k<real, 2, 64, true>), dim3(batch), dim3(64), 0, s, a);
-    bcn_env1d_shape_k = a.n / 64; bcn_env1d_shape_nt = 64;   // FIT: n == 64 K
+    *note = {nullptr, a.n / 64, 64};   // FIT: n == 64 K
     BCN_HIP(hipGetLastError());
     return BCN_OK;
   }
-  BCN_DISPATCH_1D(burgers_step_k, a, batch, s, true);
+  BCN_DISPATCH_1D(burgers_step_k, a, batch, s, true, note);
   return BCN_OK;
 }
 template <typename real> int burgers_launch_reset(const Env1DArgs<real>& a, int batch, hipStream_t s) {
@@ -1312,9 +1310,9 @@ template <typename real> int burgers_launch_reset(const Env1DArgs<real>& a, int 
   BCN_HIP(hipGetLastError());
   return BCN_OK;
 }
-template <typename real> int shkadov_launch_step(const Env1DArgs<real>& a, int batch, hipStream_t s) {
+template <typename real> int shkadov_launch_step(const Env1DArgs<real>& a, int batch, hipStream_t s, Env1DLaunch* note) {
   if (a.n_jets > 64) { bcn_set_error("n_jets > 64 unsupported"); return BCN_ERR_UNSUPPORTED; }
-  BCN_DISPATCH_1D(shkadov_step_k, a, batch, s, false);
+  BCN_DISPATCH_1D(shkadov_step_k, a, batch, s, false, note);
   return BCN_OK;
 }
 template <typename real> int shkadov_launch_reset(const Env1DArgs<real>& a, int batch, hipStream_t s) {
@@ -1322,19 +1320,18 @@ template <typename real> int shkadov_launch_reset(const Env1DArgs<real>& a, int 
   BCN_HIP(hipGetLastError());
   return BCN_OK;
 }
-template <typename real> int sloshing_launch_step(const Env1DArgs<real>& a, int batch, hipStream_t s) {
+template <typename real> int sloshing_launch_step(const Env1DArgs<real>& a, int batch, hipStream_t s, Env1DLaunch* note) {
 #ifdef BCN_ENV1D_FLOAT
   if constexpr (std::is_same<real, float>::value) {   // float32, up to 256 cells, the far wall not a lane's first cell: the packed kernel
     if (a.one_wave == 1 && a.force_k == 0 && a.n > 128 && a.n <= 256 && ((a.n - 1) & 3) != 0 && a.ndt_act <= 64 && a.nx == a.n - 2) {
       hipLaunchKernelGGL((sloshing_step_pk_k<4>), dim3(batch), dim3(64), 0, s, a);
-      bcn_env1d_launched = "sloshing_step_pk_k";
-      bcn_env1d_shape_k = 4; bcn_env1d_shape_nt = 64;
+      *note = {"sloshing_step_pk_k", 4, 64};
       BCN_HIP(hipGetLastError());
       return BCN_OK;
     }
   }
 #endif
-  BCN_DISPATCH_1D(sloshing_step_k, a, batch, s, true);
+  BCN_DISPATCH_1D(sloshing_step_k, a, batch, s, true, note);
   return BCN_OK;
 }
 template <typename real> int sloshing_launch_reset(const Env1DArgs<real>& a, int batch, hipStream_t s) {
@@ -1344,11 +1341,11 @@ template <typename real> int sloshing_launch_reset(const Env1DArgs<real>& a, int
 }
 
 #define BCN_INST(T)                                                                   \
-  template int burgers_launch_step<T>(const Env1DArgs<T>&, int, hipStream_t);         \
+  template int burgers_launch_step<T>(const Env1DArgs<T>&, int, hipStream_t, Env1DLaunch*);   \
   template int burgers_launch_reset<T>(const Env1DArgs<T>&, int, hipStream_t);        \
-  template int shkadov_launch_step<T>(const Env1DArgs<T>&, int, hipStream_t);         \
+  template int shkadov_launch_step<T>(const Env1DArgs<T>&, int, hipStream_t, Env1DLaunch*);   \
   template int shkadov_launch_reset<T>(const Env1DArgs<T>&, int, hipStream_t);        \
-  template int sloshing_launch_step<T>(const Env1DArgs<T>&, int, hipStream_t);        \
+  template int sloshing_launch_step<T>(const Env1DArgs<T>&, int, hipStream_t, Env1DLaunch*);  \
   template int sloshing_launch_reset<T>(const Env1DArgs<T>&, int, hipStream_t);
 #ifdef BCN_ENV1D_FLOAT
 BCN_INST(float)

@@ -69,126 +69,115 @@ inline void* dpr(OptT t, bcn_env_t h, int64_t per, const char* name) {
   return dp(*t, h, true, name);
 }
 
+// The outputs of an env op, checked -- size, dtype, device and contiguity of each -- with what every op needs next to them: the
+// handle and torch's current stream on the outputs' device.  reset ops have obs alone, step ops all five.
+struct Outs {
+  bcn_env_t h;
+  void *obs, *rwd = nullptr, *stream;
+  uint8_t *done = nullptr, *trunc = nullptr;
+  int32_t* status = nullptr;
+  Outs(int64_t h_, const Tensor& obs_) : h(H(h_)) {
+    rows(obs_, h, bcn_n_obs(h), "obs");
+    obs = dp(obs_, h, true, "obs");
+    stream = stream_of(obs_);
+  }
+  Outs(int64_t h_, const Tensor& obs_, const Tensor& rwd_, const Tensor& done_, const Tensor& trunc_, const Tensor& status_) : Outs(h_, obs_) {
+    rows(rwd_, h, 1, "rwd");
+    rwd = dp(rwd_, h, true, "rwd");
+    done = u8(done_, h, 1, "done");
+    trunc = u8(trunc_, h, 1, "trunc");
+    status = i32(status_, h, 1, "status");
+  }
+};
+inline const int32_t* int_actions(OptT actions, bcn_env_t h) { return actions.has_value() ? i32(*actions, h, 1, "actions") : nullptr; }
+
 // ---- rayleigh (rayleigh.py:89-157) -------------------------------------------------------------------------------------
 void rayleigh_reset(int64_t h_, OptT init_fields, const Tensor& obs) {
-  bcn_env_t h = H(h_);
-  rows(obs, h, bcn_n_obs(h), "obs");
-  check(bcn_rayleigh_reset(h, dpo(init_fields, h, true, "init_fields"), dp(obs, h, true, "obs"), stream_of(obs)), "bcn_rayleigh_reset");
+  const Outs o(h_, obs);
+  check(bcn_rayleigh_reset(o.h, dpo(init_fields, o.h, true, "init_fields"), o.obs, o.stream), "bcn_rayleigh_reset");
 }
 void rayleigh_step(int64_t h_, OptT actions, const Tensor& actions_norm, const Tensor& obs, const Tensor& rwd, const Tensor& done,
                    const Tensor& trunc, const Tensor& status, const Tensor& sweeps) {
-  bcn_env_t h = H(h_);
-  rows(obs, h, bcn_n_obs(h), "obs");
-  rows(rwd, h, 1, "rwd");
-  rows(actions_norm, h, bcn_n_act(h), "actions_norm");
-  check(bcn_rayleigh_step(h, dpr(actions, h, bcn_n_act(h), "actions"), dp(actions_norm, h, true, "actions_norm"), dp(obs, h, true, "obs"),
-                          dp(rwd, h, true, "rwd"), u8(done, h, 1, "done"), u8(trunc, h, 1, "trunc"), i32(status, h, 1, "status"), i32(sweeps, h, bcn_ndt_act(h), "sweeps"),
-                          stream_of(obs)),
+  const Outs o(h_, obs, rwd, done, trunc, status);
+  rows(actions_norm, o.h, bcn_n_act(o.h), "actions_norm");
+  check(bcn_rayleigh_step(o.h, dpr(actions, o.h, bcn_n_act(o.h), "actions"), dp(actions_norm, o.h, true, "actions_norm"), o.obs, o.rwd, o.done,
+                          o.trunc, o.status, i32(sweeps, o.h, bcn_ndt_act(o.h), "sweeps"), o.stream),
         "bcn_rayleigh_step");
 }
 
 // ---- mixing (mixing.py:73-135) -----------------------------------------------------------------------------------------
 void mixing_reset(int64_t h_, const Tensor& obs) {
-  bcn_env_t h = H(h_);
-  rows(obs, h, bcn_n_obs(h), "obs");
-  check(bcn_mixing_reset(h, dp(obs, h, true, "obs"), stream_of(obs)), "bcn_mixing_reset");
+  const Outs o(h_, obs);
+  check(bcn_mixing_reset(o.h, o.obs, o.stream), "bcn_mixing_reset");
 }
 void mixing_step(int64_t h_, OptT actions, const Tensor& obs, const Tensor& rwd, const Tensor& done, const Tensor& trunc,
                  const Tensor& status, const Tensor& sweeps) {
-  bcn_env_t h = H(h_);
-  rows(obs, h, bcn_n_obs(h), "obs");
-  rows(rwd, h, 1, "rwd");
-  const int32_t* a = actions.has_value() ? i32(*actions, h, 1, "actions") : nullptr;
-  check(bcn_mixing_step(h, a, dp(obs, h, true, "obs"), dp(rwd, h, true, "rwd"), u8(done, h, 1, "done"), u8(trunc, h, 1, "trunc"),
-                        i32(status, h, 1, "status"), i32(sweeps, h, bcn_ndt_act(h), "sweeps"), stream_of(obs)),
+  const Outs o(h_, obs, rwd, done, trunc, status);
+  check(bcn_mixing_step(o.h, int_actions(actions, o.h), o.obs, o.rwd, o.done, o.trunc, o.status, i32(sweeps, o.h, bcn_ndt_act(o.h), "sweeps"),
+                        o.stream),
         "bcn_mixing_step");
 }
 
 // ---- burgers (burgers.py:68-117) ---------------------------------------------------------------------------------------
 void burgers_reset(int64_t h_, const Tensor& obs) {
-  bcn_env_t h = H(h_);
-  rows(obs, h, bcn_n_obs(h), "obs");
-  check(bcn_burgers_reset(h, dp(obs, h, true, "obs"), stream_of(obs)), "bcn_burgers_reset");
+  const Outs o(h_, obs);
+  check(bcn_burgers_reset(o.h, o.obs, o.stream), "bcn_burgers_reset");
 }
 void burgers_step(int64_t h_, OptT actions, OptT noise, const Tensor& obs, const Tensor& rwd, const Tensor& done, const Tensor& trunc,
                   const Tensor& status) {
-  bcn_env_t h = H(h_);
-  rows(obs, h, bcn_n_obs(h), "obs");
-  rows(rwd, h, 1, "rwd");
-  check(bcn_burgers_step(h, dpr(actions, h, 1, "actions"), dpr(noise, h, 1, "noise"), dp(obs, h, true, "obs"),
-                         dp(rwd, h, true, "rwd"), u8(done, h, 1, "done"), u8(trunc, h, 1, "trunc"), i32(status, h, 1, "status"), stream_of(obs)),
+  const Outs o(h_, obs, rwd, done, trunc, status);
+  check(bcn_burgers_step(o.h, dpr(actions, o.h, 1, "actions"), dpr(noise, o.h, 1, "noise"), o.obs, o.rwd, o.done, o.trunc, o.status, o.stream),
         "bcn_burgers_step");
 }
 
 // ---- shkadov (shkadov.py:113-185) --------------------------------------------------------------------------------------
 void shkadov_reset(int64_t h_, OptT init_fields, const Tensor& obs) {
-  bcn_env_t h = H(h_);
-  rows(obs, h, bcn_n_obs(h), "obs");
-  check(bcn_shkadov_reset(h, dpo(init_fields, h, true, "init_fields"), dp(obs, h, true, "obs"), stream_of(obs)), "bcn_shkadov_reset");
+  const Outs o(h_, obs);
+  check(bcn_shkadov_reset(o.h, dpo(init_fields, o.h, true, "init_fields"), o.obs, o.stream), "bcn_shkadov_reset");
 }
 void shkadov_step(int64_t h_, OptT actions, OptT noise, const Tensor& obs, const Tensor& rwd, const Tensor& done, const Tensor& trunc,
                   const Tensor& status) {
-  bcn_env_t h = H(h_);
-  rows(obs, h, bcn_n_obs(h), "obs");
-  rows(rwd, h, 1, "rwd");
-  check(bcn_shkadov_step(h, dpr(actions, h, bcn_n_act(h), "actions"), dpr(noise, h, bcn_ndt_act(h), "noise"), dp(obs, h, true, "obs"),
-                         dp(rwd, h, true, "rwd"), u8(done, h, 1, "done"), u8(trunc, h, 1, "trunc"), i32(status, h, 1, "status"), stream_of(obs)),
+  const Outs o(h_, obs, rwd, done, trunc, status);
+  check(bcn_shkadov_step(o.h, dpr(actions, o.h, bcn_n_act(o.h), "actions"), dpr(noise, o.h, bcn_ndt_act(o.h), "noise"), o.obs, o.rwd, o.done,
+                         o.trunc, o.status, o.stream),
         "bcn_shkadov_step");
 }
 
 // ---- sloshing (sloshing.py:92-166) -------------------------------------------------------------------------------------
 void sloshing_reset(int64_t h_, OptT init_fields, const Tensor& obs) {
-  bcn_env_t h = H(h_);
-  rows(obs, h, bcn_n_obs(h), "obs");
-  check(bcn_sloshing_reset(h, dpo(init_fields, h, true, "init_fields"), dp(obs, h, true, "obs"), stream_of(obs)), "bcn_sloshing_reset");
+  const Outs o(h_, obs);
+  check(bcn_sloshing_reset(o.h, dpo(init_fields, o.h, true, "init_fields"), o.obs, o.stream), "bcn_sloshing_reset");
 }
 void sloshing_step(int64_t h_, OptT actions, const Tensor& obs, const Tensor& rwd, const Tensor& done, const Tensor& trunc,
                    const Tensor& status) {
-  bcn_env_t h = H(h_);
-  rows(obs, h, bcn_n_obs(h), "obs");
-  rows(rwd, h, 1, "rwd");
-  check(bcn_sloshing_step(h, dpr(actions, h, 1, "actions"), dp(obs, h, true, "obs"), dp(rwd, h, true, "rwd"), u8(done, h, 1, "done"),
-                          u8(trunc, h, 1, "trunc"), i32(status, h, 1, "status"), stream_of(obs)),
-        "bcn_sloshing_step");
+  const Outs o(h_, obs, rwd, done, trunc, status);
+  check(bcn_sloshing_step(o.h, dpr(actions, o.h, 1, "actions"), o.obs, o.rwd, o.done, o.trunc, o.status, o.stream), "bcn_sloshing_step");
 }
 
 // ---- lorenz (lorenz.py:60-117), vortex (vortex.py:82-146) --------------------------------------------------------------
 void lorenz_reset(int64_t h_, const Tensor& obs) {
-  bcn_env_t h = H(h_);
-  rows(obs, h, bcn_n_obs(h), "obs");
-  check(bcn_lorenz_reset(h, dp(obs, h, true, "obs"), stream_of(obs)), "bcn_lorenz_reset");
+  const Outs o(h_, obs);
+  check(bcn_lorenz_reset(o.h, o.obs, o.stream), "bcn_lorenz_reset");
 }
 void lorenz_step(int64_t h_, OptT actions, const Tensor& obs, const Tensor& rwd, const Tensor& done, const Tensor& trunc,
                  const Tensor& status) {
-  bcn_env_t h = H(h_);
-  rows(obs, h, bcn_n_obs(h), "obs");
-  rows(rwd, h, 1, "rwd");
-  const int32_t* a = actions.has_value() ? i32(*actions, h, 1, "actions") : nullptr;
-  check(bcn_lorenz_step(h, a, dp(obs, h, true, "obs"), dp(rwd, h, true, "rwd"), u8(done, h, 1, "done"), u8(trunc, h, 1, "trunc"),
-                        i32(status, h, 1, "status"), stream_of(obs)),
-        "bcn_lorenz_step");
+  const Outs o(h_, obs, rwd, done, trunc, status);
+  check(bcn_lorenz_step(o.h, int_actions(actions, o.h), o.obs, o.rwd, o.done, o.trunc, o.status, o.stream), "bcn_lorenz_step");
 }
 void vortex_reset(int64_t h_, const Tensor& obs) {
-  bcn_env_t h = H(h_);
-  rows(obs, h, bcn_n_obs(h), "obs");
-  check(bcn_vortex_reset(h, dp(obs, h, true, "obs"), stream_of(obs)), "bcn_vortex_reset");
+  const Outs o(h_, obs);
+  check(bcn_vortex_reset(o.h, o.obs, o.stream), "bcn_vortex_reset");
 }
 void vortex_step(int64_t h_, OptT actions, const Tensor& obs, const Tensor& rwd, const Tensor& done, const Tensor& trunc,
                  const Tensor& status) {
-  bcn_env_t h = H(h_);
-  rows(obs, h, bcn_n_obs(h), "obs");
-  rows(rwd, h, 1, "rwd");
-  check(bcn_vortex_step(h, dpr(actions, h, bcn_n_act(h), "actions"), dp(obs, h, true, "obs"), dp(rwd, h, true, "rwd"),
-                        u8(done, h, 1, "done"), u8(trunc, h, 1, "trunc"), i32(status, h, 1, "status"), stream_of(obs)),
-        "bcn_vortex_step");
+  const Outs o(h_, obs, rwd, done, trunc, status);
+  check(bcn_vortex_step(o.h, dpr(actions, o.h, bcn_n_act(o.h), "actions"), o.obs, o.rwd, o.done, o.trunc, o.status, o.stream), "bcn_vortex_step");
 }
 
 // ---- snapshots (include/beacon_hip.h: bcn_snapshot_save / bcn_snapshot_load) --------------------------------------------
-// bytes of the packed output buffer [obs | rwd | status | done | trunc] of the handle's batch, every part 16-byte aligned
+// bytes of the packed output buffer of the handle's batch (include/beacon_hip.h: bcn_out_layout)
 inline int64_t out_buf_bytes(bcn_env_t h) {
-  auto up = [](int64_t x) { return (x + 15) / 16 * 16; };
-  const int64_t B = bcn_batch(h), esz = bcn_dtype(h) == BCN_F64 ? 8 : 4;
-  return up(up(up(up(up(B * bcn_n_obs(h) * esz) + B * esz) + B * 4) + B) + B);
+  return (int64_t)bcn_out_layout((size_t)bcn_batch(h), (size_t)bcn_n_obs(h), bcn_dtype(h) == BCN_F64 ? 8 : 4).bytes;
 }
 inline uint8_t* bytes_of(const Tensor& t, bcn_env_t h, int64_t n, const char* name) {
   on_device(t, h, name);

@@ -50,6 +50,44 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def dtype_name(tdtype):
+    return "f64" if tdtype == torch.float64 else "f32"
+
+
+def _mask_u8(mask, batch, device, what=None):
+    """A replica mask ([B] bool / uint8 tensor or array) as a contiguous uint8 [B] tensor on `device` (the same memory when it is
+    one already).  `what`: raise ValueError under that name for a mask of another length."""
+    if not torch.is_tensor(mask):
+        mask = torch.as_tensor(np.asarray(mask))
+    if what is not None and mask.numel() != batch:
+        raise ValueError("%s: mask must hold %d values" % (what, batch))
+    return mask.to(device=device, dtype=torch.uint8).reshape(batch).contiguous()
+
+
+# element types of a segment other than the env's own (BCN_SNAP_REAL)
+_SEG_ELEM = {_lib.SNAP_I32: torch.int32, _lib.SNAP_U32: torch.int32, _lib.SNAP_U8: torch.uint8, _lib.SNAP_F64: torch.float64,
+             _lib.SNAP_I64: torch.int64}
+
+
+def _segments(segs, k):
+    """The first k bcn_snapshot_seg structs (bcn_snapshot_layout, bcn_episode_layout) as plain dicts."""
+    return [dict(name=g.name.decode(), offset=int(g.offset), elem=int(g.elem), planes=int(g.planes), row_elems=int(g.row_elems))
+            for g in segs[:k]]
+
+
+def _seg_view(buf, layout, name, n, real):
+    """(segment dict, flat typed no-copy view of its planes x n x row_elems elements) of the segment `name` of `buf`, laid out
+    for n replicas of an env computing in `real`; KeyError for an unknown name."""
+    for seg in layout:
+        if seg["name"] == name:
+            break
+    else:
+        raise KeyError(name)
+    dt = _SEG_ELEM.get(seg["elem"], real)
+    nbytes = int(seg["planes"]) * n * int(seg["row_elems"]) * torch.empty((), dtype=dt).element_size()
+    return seg, buf[seg["offset"]:seg["offset"] + nbytes].view(dt)
+
+
 _POSITIVE_PARAMS = ("ra", "re", "pe", "delta", "g")       # divisors / arguments of roots (include/beacon_hip.h: bcn_set_params)
 
 _OPS = ("rayleigh_reset", "rayleigh_step", "mixing_reset", "mixing_step", "burgers_reset", "burgers_step", "shkadov_reset",
@@ -66,6 +104,11 @@ def _op_table():
     return None if ops is None else {n: getattr(ops, n).default for n in _OPS + _ODE_OPS + _STATE_OPS + _EPISODE_OPS}
 
 
+def _c_table(lib):
+    """{name: bcn_<name> of libbeacon_hip.so}: the same entry points through ctypes, resolved once per env."""
+    return {n: getattr(lib, "bcn_" + n) for n in _OPS + _ODE_OPS + _STATE_OPS + _EPISODE_OPS}
+
+
 class Snapshot(object):
     """Everything one VecEnv needs to continue its episodes bit for bit (VecEnv.snapshot / restore / fork), for `batch` replicas:
     `buf`, one uint8 tensor in the layout of include/beacon_hip.h (bcn_snapshot_*), and `meta`, a dict of plain values:
@@ -73,8 +116,6 @@ class Snapshot(object):
     values, segment shapes), layout (the segments: name, offset, elem, planes, row_elems), field_shape, ctor (the env's
     constructor kwargs), version (of the library that wrote it), noise (sigma, seed, replica_offset: kernel arguments, recorded
     only) and gen_state (the env's torch generator, or None)."""
-
-    _ELEM = {_lib.SNAP_I32: torch.int32, _lib.SNAP_U32: torch.int32, _lib.SNAP_U8: torch.uint8}
 
     def __init__(self, buf, meta):
         if not torch.is_tensor(buf) or buf.dtype != torch.uint8 or buf.dim() != 1:
@@ -92,15 +133,8 @@ class Snapshot(object):
         """Typed view (no copy) of one segment: "fields" [planes, batch, ...] (the planes of get_state() in front of the batch
         axis), "obs_hist", "a_last" / "ia_last" / "iu", "a_prev", "stp", "nctr" (the uint32 counters as int32 bits), "obs", "rwd",
         "status", "done", "trunc" -- whichever the env has (names()).  KeyError for any other name."""
-        for seg in self.meta["layout"]:
-            if seg["name"] == name:
-                break
-        else:
-            raise KeyError(name)
-        dt = self._ELEM.get(seg["elem"], _DT[self.meta["dtype"]][0])
-        esz = torch.empty((), dtype=dt).element_size()
+        seg, v = _seg_view(self.buf, self.meta["layout"], name, self.batch, _DT[self.meta["dtype"]][0])
         n, planes, row = self.batch, int(seg["planes"]), int(seg["row_elems"])
-        v = self.buf[seg["offset"]:seg["offset"] + planes * n * row * esz].view(dt)
         if name == "fields":
             shape = tuple(self.meta.get("field_shape") or ())
             return v.view((planes, n) + shape) if shape else v.view(planes, n)
@@ -137,7 +171,6 @@ class EpisodeStats(object):
     these statistics where they are -- clear(mask) is the tool after a fork."""
 
     NAMES = ("ret", "len", "last_ret", "last_len", "count", "sum_ret", "sum_len", "finished", "final_obs")
-    _ELEM = {_lib.SNAP_I32: torch.int32, _lib.SNAP_U8: torch.uint8, _lib.SNAP_F64: torch.float64, _lib.SNAP_I64: torch.int64}
 
     def __init__(self, env):
         segs = (_lib.SnapshotSeg * 16)()
@@ -147,22 +180,14 @@ class EpisodeStats(object):
             raise _lib.BeaconHipError("libbeacon_hip: %s" % env.lib.bcn_last_error().decode())
         self.batch, self.obs_dim, self.tdtype = env.batch, env.obs_dim, env.tdtype
         self.buf = torch.zeros((nbytes,), dtype=torch.uint8, device=env.device)
-        self.layout = [dict(name=segs[i].name.decode(), offset=int(segs[i].offset), elem=int(segs[i].elem),
-                            row_elems=int(segs[i].row_elems)) for i in range(k)]
+        self.layout = _segments(segs, k)
         assert tuple(seg["name"] for seg in self.layout) == self.NAMES
         for seg in self.layout:
             setattr(self, seg["name"], self.view(seg["name"]))
 
     def view(self, name):
         """Typed view (no copy) of one segment; KeyError for an unknown name."""
-        for seg in self.layout:
-            if seg["name"] == name:
-                break
-        else:
-            raise KeyError(name)
-        dt = self._ELEM.get(seg["elem"], self.tdtype)
-        esz = torch.empty((), dtype=dt).element_size()
-        v = self.buf[seg["offset"]:seg["offset"] + self.batch * seg["row_elems"] * esz].view(dt)
+        seg, v = _seg_view(self.buf, self.layout, name, self.batch, self.tdtype)
         return v.view(self.batch, seg["row_elems"]) if name == "final_obs" else v
 
     def clear(self, mask=None):
@@ -171,9 +196,7 @@ class EpisodeStats(object):
         if mask is None:
             self.buf.zero_()
             return self
-        if not torch.is_tensor(mask):
-            mask = torch.as_tensor(np.asarray(mask))
-        m = mask.to(device=self.buf.device).reshape(self.batch) != 0
+        m = _mask_u8(mask, self.batch, self.buf.device) != 0
         for name in self.NAMES:
             v = getattr(self, name)
             v.masked_fill_(m[:, None] if v.dim() == 2 else m, 0)
@@ -190,7 +213,7 @@ class EpisodeStats(object):
     def state_dict(self):
         """For checkpoints: the buffer on the CPU and what it was laid out for."""
         return {"buf": self.buf.cpu(), "batch": self.batch, "obs_dim": self.obs_dim,
-                "dtype": "f64" if self.tdtype == torch.float64 else "f32"}
+                "dtype": dtype_name(self.tdtype)}
 
     def load_state_dict(self, d):
         if (int(d["batch"]), int(d["obs_dim"]), _DT[d["dtype"]][0]) != (self.batch, self.obs_dim, self.tdtype) or \
@@ -221,6 +244,7 @@ class VecEnv(object):
         # the torch.library ops over the same C ABI (beacon_amd/torch_ext.py): one dispatcher call per reset() / step();
         # None (no compiler and no prebuilt extension, or BEACON_TORCH_EXT=0): the ctypes binding below
         self._ops = _op_table()
+        self._cfn = _c_table(self.lib)
         self.batch = int(batch)
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -285,6 +309,30 @@ class VecEnv(object):
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
+    def _call(self, name, *args):
+        """The entry point `name` (one of _OPS, _ODE_OPS, _STATE_OPS, _EPISODE_OPS) through the binding in force: the torch op, or
+        bcn_<name> through ctypes.  `args`: what both take between the handle and the stream, in their common order -- tensors
+        (None: a null pointer) and ints; the op reads torch's current stream itself, ctypes gets it appended."""
+        if self._ops is not None:
+            return self._ops[name](self.h.value, *args)
+        _lib.check(self._cfn[name](self.h, *[a if a is None or isinstance(a, int) else C.c_void_p(a.data_ptr()) for a in args],
+                                   self._stream()))
+
+    def _int_actions(self, actions):
+        """Discrete actions -> contiguous int32 [B] device tensor; None (the kernel repeats the stored action) stays None."""
+        if actions is None:
+            return None
+        if not torch.is_tensor(actions):
+            actions = torch.as_tensor(np.asarray(actions, dtype=np.int64))
+        return actions.to(device=self.device, dtype=torch.int32).reshape(self.batch).contiguous()
+
+    def _noise_setup(self, seed):
+        """The envs with inlet noise (burgers, shkadov), once their handle exists: the kernel's own draws (set_noise_seed) and the
+        torch generator `gen` of draw_noise() / reset_random() both start from the constructor's seed."""
+        self.set_noise_seed(seed, 0)
+        self.gen = torch.Generator(device=self.device)
+        self.gen.manual_seed(self.seed)
+
     def _real(self, x, shape):
         """actions / noise / init fields -> contiguous device tensor of the env dtype."""
         if x is None:
@@ -335,11 +383,9 @@ class VecEnv(object):
         k = self.lib.bcn_snapshot_layout(self.h, self.batch, segs, 16)
         if k <= 0:
             raise _lib.BeaconHipError("libbeacon_hip: %s" % self.lib.bcn_last_error().decode())
-        lay = [dict(name=segs[i].name.decode(), offset=int(segs[i].offset), elem=int(segs[i].elem), planes=int(segs[i].planes),
-                    row_elems=int(segs[i].row_elems)) for i in range(k)]
         shape = self.state_shape()
-        return dict(env=type(self).__name__, kind=int(self.lib.bcn_env_kind(self.h)), dtype="f64" if self.tdtype == torch.float64 else "f32",
-                    batch=self.batch, signature=self.snapshot_signature(), layout=lay,
+        return dict(env=type(self).__name__, kind=int(self.lib.bcn_env_kind(self.h)), dtype=dtype_name(self.tdtype),
+                    batch=self.batch, signature=self.snapshot_signature(), layout=_segments(segs, k),
                     field_shape=list(shape[1:]) if len(shape) > 1 else [], ctor=dict(getattr(self, "_ctor", {})),
                     version=self.lib.bcn_version().decode(), noise=None, gen_state=None)
 
@@ -376,10 +422,7 @@ class VecEnv(object):
             if out.batch != self.batch:
                 raise ValueError("snapshot(out=): out holds %d replicas, this env %d" % (out.batch, self.batch))
         self._snap_volatile(out.meta)
-        if self._ops is not None:
-            self._ops["snapshot_save"](self.h.value, out.buf, self.out_buf)
-        else:
-            _lib.check(self.lib.bcn_snapshot_save(self.h, _ptr(out.buf), _ptr(self.out_buf), self._stream()))
+        self._call("snapshot_save", out.buf, self.out_buf)
         return out
 
     def restore(self, snap, src=None, mask=None):
@@ -409,18 +452,9 @@ class VecEnv(object):
             if src.device != self.device or src.dtype != torch.int32 or not src.is_contiguous():
                 src = src.to(device=self.device, dtype=torch.int32).reshape(self.batch).contiguous()
         if mask is not None:
-            if not torch.is_tensor(mask):
-                mask = torch.as_tensor(np.asarray(mask))
-            if mask.numel() != self.batch:
-                raise ValueError("restore: mask must hold %d values" % self.batch)
-            if mask.device != self.device or mask.dtype != torch.uint8 or not mask.is_contiguous():
-                mask = mask.to(device=self.device, dtype=torch.uint8).reshape(self.batch).contiguous()
+            mask = _mask_u8(mask, self.batch, self.device, "restore")
         self._keep_restore = (src, mask)
-        if self._ops is not None:
-            self._ops["snapshot_load"](self.h.value, snap.buf, snap.batch, src, mask, self.out_buf)
-        else:
-            _lib.check(self.lib.bcn_snapshot_load(self.h, _ptr(snap.buf), snap.batch, _ptr(src), _ptr(mask), _ptr(self.out_buf),
-                                                  self._stream()))
+        self._call("snapshot_load", snap.buf, snap.batch, src, mask, self.out_buf)
         gen = getattr(self, "gen", None)
         if (gen is not None and src is None and mask is None and snap.meta.get("gen_state") is not None
                 and not torch.cuda.is_current_stream_capturing()):
@@ -470,7 +504,7 @@ class VecEnv(object):
             return
         if p.verified is None and not jit.CHECKING:
             # first use of this shared object: compared with the generic kernel before any env runs on it (jit.verify)
-            ctor, cls, dev, dt = dict(self._ctor), type(self), self.device, ("f64" if f64 else "f32")
+            ctor, cls, dev, dt = dict(self._ctor), type(self), self.device, dtype_name(self.tdtype)
             jit.verify(p, lambda batch: cls(batch, dev, dt, **ctor), kind, f64)
         if p.verified or jit.CHECKING:
             _lib.check(self.lib.bcn_set_fast_plugin(self.h, p.fn, p.scratch))
@@ -635,9 +669,7 @@ class VecEnv(object):
             self._mask = None
             _lib.check(self.lib.bcn_set_mask(self.h, None))
             return
-        if not torch.is_tensor(mask):
-            mask = torch.as_tensor(np.asarray(mask))
-        self._mask = mask.to(device=self.device, dtype=torch.uint8).reshape(self.batch).contiguous()
+        self._mask = _mask_u8(mask, self.batch, self.device)
         _lib.check(self.lib.bcn_set_mask(self.h, _ptr(self._mask)))
 
     # -- Gym surface ------------------------------------------------------------------------
@@ -676,9 +708,7 @@ class VecEnv(object):
         return ep
 
     def _track(self, ep, mask):
-        if self._ops is not None:
-            return self._ops["episode_track"](self.h.value, self.out_buf, ep.buf, mask)
-        _lib.check(self.lib.bcn_episode_track(self.h, _ptr(self.out_buf), _ptr(ep.buf), _ptr(mask), self._stream()))
+        self._call("episode_track", self.out_buf, ep.buf, mask)
 
     def _reset_finished(self, ep):
         """the env's own masked reset with ep.finished as the device mask (what reset_done() launches with done.clone()); the
@@ -692,9 +722,7 @@ class VecEnv(object):
         step() (call it once per step, before reset_done(), which overwrites the terminal rows of `obs`).  `mask`: the mask that
         step was given.  Returns the EpisodeStats."""
         if mask is not None:
-            if not torch.is_tensor(mask):
-                mask = torch.as_tensor(np.asarray(mask))
-            mask = mask.to(device=self.device, dtype=torch.uint8).reshape(self.batch).contiguous()
+            mask = _mask_u8(mask, self.batch, self.device)
         ep = self.episodes
         self._keep_track = mask           # keeps the converted mask alive behind the asynchronous launch (as _keep, _done_mask do)
         self._track(ep, mask)
@@ -809,7 +837,23 @@ class StepGraph(object):
 
 
 # ---------------------------------------------------------------------------------------------
-class VecRayleigh(VecEnv):
+class _VecNS2D(VecEnv):
+    """What the two 2D envs (rayleigh, mixing) share on the host."""
+
+    def set_ndt_act(self, n):
+        """Test hook: shorten the action step (the goldens for big grids use ndt_act=5).  The handle is built anew."""
+        self.close()
+        self.ndt_act = int(n)
+        self.h = C.c_void_p()
+        self._create()
+        self._reapply_params()
+        self.sweeps = torch.zeros((self.batch, self.ndt_act), dtype=torch.int32, device=self.device)
+
+    def state_shape(self):
+        return (4, self.ny + 2, self.nx + 2)
+
+
+class VecRayleigh(_VecNS2D):
     """rayleigh/rayleigh.py:16-366.  `init_fields`: [4, nx+2, ny+2] in the reference's [i, j]
     layout (u, v, p, T) -- what load() parses from init_field.dat (:356-362) -- or None
     (init=False: all-zero fields)."""
@@ -870,18 +914,6 @@ class VecRayleigh(VecEnv):
         self._attach_plugin(0)
         self._slow_mode_bound(0)
 
-    def set_ndt_act(self, n):
-        """Test hook: shorten the action step (the goldens for big grids use ndt_act=5)."""
-        self.close()
-        self.ndt_act = int(n)
-        self.h = C.c_void_p()
-        self._create()
-        self._reapply_params()
-        self.sweeps = torch.zeros((self.batch, self.ndt_act), dtype=torch.int32, device=self.device)
-
-    def state_shape(self):
-        return (4, self.ny + 2, self.nx + 2)
-
     def perturbed_conduction_state(self, seed=2024):
         """Start state of a warm-up on a grid without an init file, [4, nx+2, ny+2] in the reference's [i, j] layout:
         u = v = p = 0, T = the conduction profile plus five seeded long-wave perturbations of amplitude <= 0.02 (from
@@ -912,22 +944,15 @@ class VecRayleigh(VecEnv):
         return np.ascontiguousarray(st[0].double().cpu().numpy().transpose(0, 2, 1))
 
     def _reset(self):
-        if self._ops is not None:
-            return self._ops["rayleigh_reset"](self.h.value, self._init_dev, self.obs)
-        _lib.check(self.lib.bcn_rayleigh_reset(self.h, _ptr(self._init_dev), _ptr(self.obs), self._stream()))
+        self._call("rayleigh_reset", self._init_dev, self.obs)
 
     def _step(self, actions, noise=None):
         a = self._real(actions, (self.batch, self.n_sgts))
         self._keep = a
-        if self._ops is not None:
-            return self._ops["rayleigh_step"](self.h.value, a, self.actions_norm, self.obs, self.rwd, self.done, self.trunc,
-                                              self.status, self.sweeps)
-        _lib.check(self.lib.bcn_rayleigh_step(self.h, _ptr(a), _ptr(self.actions_norm), _ptr(self.obs),
-                                              _ptr(self.rwd), _ptr(self.done), _ptr(self.trunc),
-                                              _ptr(self.status), _ptr(self.sweeps), self._stream()))
+        self._call("rayleigh_step", a, self.actions_norm, self.obs, self.rwd, self.done, self.trunc, self.status, self.sweeps)
 
 
-class VecMixing(VecEnv):
+class VecMixing(_VecNS2D):
     """mixing/mixing.py:16-378"""
 
     PARAMS = ("re", "pe")
@@ -980,34 +1005,13 @@ class VecMixing(VecEnv):
         self._attach_plugin(1)
         self._slow_mode_bound(1)
 
-    def set_ndt_act(self, n):
-        self.close()
-        self.ndt_act = int(n)
-        self.h = C.c_void_p()
-        self._create()
-        self._reapply_params()
-        self.sweeps = torch.zeros((self.batch, self.ndt_act), dtype=torch.int32, device=self.device)
-
-    def state_shape(self):
-        return (4, self.ny + 2, self.nx + 2)
-
     def _reset(self):
-        if self._ops is not None:
-            return self._ops["mixing_reset"](self.h.value, self.obs)
-        _lib.check(self.lib.bcn_mixing_reset(self.h, _ptr(self.obs), self._stream()))
+        self._call("mixing_reset", self.obs)
 
     def _step(self, actions, noise=None):
-        a = None
-        if actions is not None:
-            if not torch.is_tensor(actions):
-                actions = torch.as_tensor(np.asarray(actions, dtype=np.int64))
-            a = actions.to(device=self.device, dtype=torch.int32).reshape(self.batch).contiguous()
+        a = self._int_actions(actions)
         self._keep = a
-        if self._ops is not None:
-            return self._ops["mixing_step"](self.h.value, a, self.obs, self.rwd, self.done, self.trunc, self.status, self.sweeps)
-        _lib.check(self.lib.bcn_mixing_step(self.h, _ptr(a), _ptr(self.obs), _ptr(self.rwd), _ptr(self.done),
-                                            _ptr(self.trunc), _ptr(self.status), _ptr(self.sweeps),
-                                            self._stream()))
+        self._call("mixing_step", a, self.obs, self.rwd, self.done, self.trunc, self.status, self.sweeps)
 
 
 class VecBurgers(VecEnv):
@@ -1021,11 +1025,9 @@ class VecBurgers(VecEnv):
                  ctrl_pos=1.0, L=2.0, nx=500, seed=0):
         self._derive(u_target, amp, sigma, ctrl_pos, L, nx)
         self._ctor = dict(u_target=u_target, amp=amp, sigma=sigma, ctrl_pos=ctrl_pos, L=L, nx=nx, seed=seed)
-        self.seed, self.replica_offset = int(seed), 0
         super().__init__(batch, device, dtype)
         self._make_spaces()
-        self.gen = torch.Generator(device=self.device)
-        self.gen.manual_seed(self.seed)
+        self._noise_setup(seed)
 
     def _make_spaces(self):
         self.action_space = spaces.box(-1.0, 1.0, (1,))                         # burgers.py:54-57
@@ -1049,7 +1051,6 @@ class VecBurgers(VecEnv):
         self.cfg = c
         _lib.check(self.lib.bcn_burgers_create(C.byref(c), self.batch, self.cdtype, self.dev_index,
                                                C.byref(self.h)))
-        self.set_noise_seed(self.seed, self.replica_offset)
 
     def state_shape(self):
         return (3, self.nx)
@@ -1062,19 +1063,13 @@ class VecBurgers(VecEnv):
         return (2.0 * r - 1.0) * self.sigma
 
     def _reset(self):
-        if self._ops is not None:
-            return self._ops["burgers_reset"](self.h.value, self.obs)
-        _lib.check(self.lib.bcn_burgers_reset(self.h, _ptr(self.obs), self._stream()))
+        self._call("burgers_reset", self.obs)
 
     def _step(self, actions, noise=None):
         a = self._real(actions, (self.batch,))
         nz = None if noise is None else self._real(noise, (self.batch,))     # None: drawn inside the kernel
         self._keep = (a, nz)
-        if self._ops is not None:
-            return self._ops["burgers_step"](self.h.value, a, nz, self.obs, self.rwd, self.done, self.trunc, self.status)
-        _lib.check(self.lib.bcn_burgers_step(self.h, _ptr(a), _ptr(nz), _ptr(self.obs), _ptr(self.rwd),
-                                             _ptr(self.done), _ptr(self.trunc), _ptr(self.status),
-                                             self._stream()))
+        self._call("burgers_step", a, nz, self.obs, self.rwd, self.done, self.trunc, self.status)
 
 
 class VecShkadov(VecEnv):
@@ -1090,11 +1085,9 @@ class VecShkadov(VecEnv):
         self._derive(L0, n_jets, jet_pos, jet_space, delta, t_act)
         self._ctor = dict(L0=L0, n_jets=n_jets, jet_pos=jet_pos, jet_space=jet_space, delta=delta, t_act=t_act, seed=seed)
         self._init_np = None if init_fields is None else np.asarray(init_fields, dtype=np.float64)
-        self.seed, self.replica_offset = int(seed), 0
         super().__init__(batch, device, dtype)
         self._make_spaces()
-        self.gen = torch.Generator(device=self.device)
-        self.gen.manual_seed(self.seed)
+        self._noise_setup(seed)
         self._init_dev = None
         if self._init_np is not None:
             self._init_dev = self._real(np.ascontiguousarray(self._init_np[:, :self.nx]), (2, self.nx))
@@ -1134,7 +1127,6 @@ class VecShkadov(VecEnv):
         self.cfg = c
         _lib.check(self.lib.bcn_shkadov_create(C.byref(c), self.batch, self.cdtype, self.dev_index,
                                                C.byref(self.h)))
-        self.set_noise_seed(self.seed, self.replica_offset)
 
     def state_shape(self):
         return (4, self.nx)
@@ -1158,19 +1150,13 @@ class VecShkadov(VecEnv):
         return self.obs, None
 
     def _reset(self):
-        if self._ops is not None:
-            return self._ops["shkadov_reset"](self.h.value, self._init_dev, self.obs)
-        _lib.check(self.lib.bcn_shkadov_reset(self.h, _ptr(self._init_dev), _ptr(self.obs), self._stream()))
+        self._call("shkadov_reset", self._init_dev, self.obs)
 
     def _step(self, actions, noise=None):
         a = self._real(actions, (self.batch, self.n_jets))
         nz = None if noise is None else self._real(noise, (self.batch, self.ndt_act))   # None: drawn inside the kernel
         self._keep = (a, nz)
-        if self._ops is not None:
-            return self._ops["shkadov_step"](self.h.value, a, nz, self.obs, self.rwd, self.done, self.trunc, self.status)
-        _lib.check(self.lib.bcn_shkadov_step(self.h, _ptr(a), _ptr(nz), _ptr(self.obs), _ptr(self.rwd),
-                                             _ptr(self.done), _ptr(self.trunc), _ptr(self.status),
-                                             self._stream()))
+        self._call("shkadov_step", a, nz, self.obs, self.rwd, self.done, self.trunc, self.status)
 
 
 class VecSloshing(VecEnv):
@@ -1222,17 +1208,12 @@ class VecSloshing(VecEnv):
         return 0.5 * (np.cos(np.pi * t) + 3.0 * np.cos(4.0 * np.pi * t))
 
     def _reset(self):
-        if self._ops is not None:
-            return self._ops["sloshing_reset"](self.h.value, self._init_dev, self.obs)
-        _lib.check(self.lib.bcn_sloshing_reset(self.h, _ptr(self._init_dev), _ptr(self.obs), self._stream()))
+        self._call("sloshing_reset", self._init_dev, self.obs)
 
     def _step(self, actions, noise=None):
         a = self._real(actions, (self.batch,))
         self._keep = a
-        if self._ops is not None:
-            return self._ops["sloshing_step"](self.h.value, a, self.obs, self.rwd, self.done, self.trunc, self.status)
-        _lib.check(self.lib.bcn_sloshing_step(self.h, _ptr(a), _ptr(self.obs), _ptr(self.rwd), _ptr(self.done),
-                                              _ptr(self.trunc), _ptr(self.status), self._stream()))
+        self._call("sloshing_step", a, self.obs, self.rwd, self.done, self.trunc, self.status)
 
 
 class VecLorenz(VecEnv):
@@ -1272,21 +1253,12 @@ class VecLorenz(VecEnv):
         return (8,)
 
     def _reset(self):
-        if self._ops is not None:
-            return self._ops["lorenz_reset"](self.h.value, self.obs)
-        _lib.check(self.lib.bcn_lorenz_reset(self.h, _ptr(self.obs), self._stream()))
+        self._call("lorenz_reset", self.obs)
 
     def _step(self, actions, noise=None):
-        a = None
-        if actions is not None:
-            if not torch.is_tensor(actions):
-                actions = torch.as_tensor(np.asarray(actions, dtype=np.int64))
-            a = actions.to(device=self.device, dtype=torch.int32).reshape(self.batch).contiguous()
+        a = self._int_actions(actions)
         self._keep = a
-        if self._ops is not None:
-            return self._ops["lorenz_step"](self.h.value, a, self.obs, self.rwd, self.done, self.trunc, self.status)
-        _lib.check(self.lib.bcn_lorenz_step(self.h, _ptr(a), _ptr(self.obs), _ptr(self.rwd), _ptr(self.done),
-                                            _ptr(self.trunc), _ptr(self.status), self._stream()))
+        self._call("lorenz_step", a, self.obs, self.rwd, self.done, self.trunc, self.status)
 
 
 class VecVortex(VecEnv):
@@ -1335,14 +1307,9 @@ class VecVortex(VecEnv):
         return (14,)
 
     def _reset(self):
-        if self._ops is not None:
-            return self._ops["vortex_reset"](self.h.value, self.obs)
-        _lib.check(self.lib.bcn_vortex_reset(self.h, _ptr(self.obs), self._stream()))
+        self._call("vortex_reset", self.obs)
 
     def _step(self, actions, noise=None):
         a = self._real(actions, (self.batch, 2))
         self._keep = a
-        if self._ops is not None:
-            return self._ops["vortex_step"](self.h.value, a, self.obs, self.rwd, self.done, self.trunc, self.status)
-        _lib.check(self.lib.bcn_vortex_step(self.h, _ptr(a), _ptr(self.obs), _ptr(self.rwd), _ptr(self.done),
-                                            _ptr(self.trunc), _ptr(self.status), self._stream()))
+        self._call("vortex_step", a, self.obs, self.rwd, self.done, self.trunc, self.status)

@@ -395,6 +395,18 @@ BCN_API uint64_t bcn_snapshot_signature(bcn_env_t h);
 BCN_API int bcn_snapshot_save(bcn_env_t h, void* snap_dev, const void* out_buf_dev, void* stream);
 BCN_API int bcn_snapshot_load(bcn_env_t h, const void* snap_dev, int n_src, const int32_t* src_dev, const uint8_t* mask_dev,
                               void* out_buf_dev, void* stream);
+/* The packed output buffer (out_buf_dev above) of `batch` replicas with n_obs observations of esz bytes (4 or 8) each: byte offset
+ * of every part and the size of the whole.  The one definition of that layout: the library, the torch extension and -- through a
+ * test -- the Python side's allocation all follow it.  Header-only, not an exported symbol. */
+typedef struct { size_t obs, rwd, status, done, trunc, bytes; } bcn_out_layout_t;
+static inline bcn_out_layout_t bcn_out_layout(size_t batch, size_t n_obs, size_t esz) {
+  const size_t len[5] = {batch * n_obs * esz, batch * esz, batch * 4, batch, batch};
+  size_t off[6] = {0, 0, 0, 0, 0, 0};
+  bcn_out_layout_t o;
+  for (int k = 0; k < 5; k++) off[k + 1] = (off[k] + len[k] + 15) / 16 * 16;
+  o.obs = off[0]; o.rwd = off[1]; o.status = off[2]; o.done = off[3]; o.trunc = off[4]; o.bytes = off[5];
+  return o;
+}
 /* Per-replica physical parameters.  Every handle is created from ONE cfg; these calls give each replica of the batch its own values
  * of the reference's constructor arguments (everything else in a cfg -- grids, counts, segment and jet layout, dt, tolerances -- is
  * structural and stays per handle).  Parameters, in the order of bcn_param_name and of the value rows:
