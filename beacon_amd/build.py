@@ -39,6 +39,11 @@ FILE_FLAGS = {"ns2d_fast.hip": ["-fno-slp-vectorize", "-ffp-contract=on", "-O2"]
               "ns2d_fast_f64.hip": ["-fno-slp-vectorize", "-ffp-contract=on"],
               "ns2d_fast2.hip": ["-fno-slp-vectorize", "-ffp-contract=on", "-mllvm", "-amdgpu-disable-unclustered-high-rp-reschedule",
                                  "-mllvm", "-amdgpu-sdwa-peephole=0"],
+              # the same kernels reading the per-replica parameter table (csrc/ns2d_prm.h): each with the flags of its sibling
+              "ns2d_fast_prm.hip": ["-fno-slp-vectorize", "-ffp-contract=on", "-O2"],
+              "ns2d_fast_prm_f64.hip": ["-fno-slp-vectorize", "-ffp-contract=on"],
+              "ns2d_fast2_prm.hip": ["-fno-slp-vectorize", "-ffp-contract=on", "-mllvm", "-amdgpu-disable-unclustered-high-rp-reschedule",
+                                     "-mllvm", "-amdgpu-sdwa-peephole=0"],
               # float64 1D kernels: the reference's operation order without FMA contraction -> bit-identical fields
               "env1d_f64.hip": ["-ffp-contract=off"],
               # float64 ODE envs (lorenz, vortex): the host ports' operation order without FMA contraction -> bit-identical episodes

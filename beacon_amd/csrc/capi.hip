@@ -224,6 +224,7 @@ struct NS2DEnv : bcn_env_s {
     if (!strcmp(name, "transport_iter") && value >= 0 && value <= 64) { a.transport_iter = value; return BCN_OK; }
     if (!strcmp(name, "sched_tail") && value >= 0 && value <= 1024) { host.sched_tail = value; return BCN_OK; }
     if (!strcmp(name, "generic_threads") && (value == 0 || value == 256 || value == 1024)) { host.generic_nt = value; return BCN_OK; }
+    if (!strcmp(name, "params_kernel") && (value == 0 || value == 1)) { params_kernel = value; host.launched = nullptr; return BCN_OK; }
     return bcn_env_s::set_option(name, value);
   }
   int get_counters(uint64_t* host, hipStream_t s) override {
@@ -234,6 +235,7 @@ struct NS2DEnv : bcn_env_s {
   typedef int (*plugin_fn)(const void*, int, void*);
   plugin_fn plugin = nullptr;        // register-resident kernel of a grid that is not built in (bcn_set_fast_plugin)
   int set_fast_plugin(void* fn, size_t scratch_elems) override {
+    plugin_prm = nullptr;   // (the table-reading launcher belongs to the plugin it was set behind)
     if (!fn) { plugin = nullptr; fast_ok = ns2d_fast_supported<real>(a); variant = fast_ok ? 1 : 0; return BCN_OK; }
     if (scratch_elems > 0) {
       DeviceGuard g(device);
@@ -248,18 +250,40 @@ struct NS2DEnv : bcn_env_s {
     fast_ok = true; variant = 1; host.launched = nullptr;
     return BCN_OK;
   }
+  // the plugin's launcher of its table-reading kernels (bcn_set_fast_plugin_params; a plugin built with -DBCN_JIT_PRM=1)
+  typedef int (*plugin_prm_fn)(const void*, int, void*, const void*);
+  plugin_prm_fn plugin_prm = nullptr;
+  int set_fast_plugin_params(void* fn) override {
+    if (fn && !plugin) { bcn_set_error("bcn_set_fast_plugin_params: the handle has no kernel plugin (bcn_set_fast_plugin comes first)"); return BCN_ERR_ARG; }
+    plugin_prm = reinterpret_cast<plugin_prm_fn>(fn);
+    host.launched = nullptr;
+    return BCN_OK;
+  }
   NS2DHost host;   // launcher-side state: kernel name of the last step, options that no kernel reads
-  // per-replica parameters (bcn_set_params): the table is an argument of the generic kernel alone, so a handle that has one steps
-  // through it whatever its variant; clearing the table restores the previous dispatch
+  // per-replica parameters (bcn_set_params): the table is a kernel argument of its own.  The generic kernel takes it, and a handle
+  // that has one steps through that kernel whatever its variant -- unless the option "params_kernel" is 1, the variant is 1 and
+  // the handle has a register-resident kernel that takes the table too (built in: params.h; a plugin: plugin_prm).  Clearing
+  // the table restores the previous dispatch.  A register-resident kernel that ignores the table is never launched while one is set.
   const real* prm = nullptr;
+  int params_kernel = 0;
   void use_params(const void* table) override { prm = static_cast<const real*>(table); host.launched = nullptr; }
+  bool prm_fast() const {
+    return prm && params_kernel == 1 && variant == 1 && (plugin ? plugin_prm != nullptr : ns2d_fast_supported_prm<real>(a));
+  }
   const char* kernel_name() const override {
-    if (prm) return "ns2d_generic_step";
+    if (prm && !prm_fast()) return "ns2d_generic_step";
     return host.launched ? host.launched : (variant == 1 ? "ns2d_fast_step" : "ns2d_generic_step");
   }
   int launch(hipStream_t s) {
     a.host = &host;
-    if (prm) return ns2d_launch_generic_prm<real>(a, batch, s, prm);
+    if (prm) {
+      if (prm_fast()) {
+        // BCN_ERR_UNSUPPORTED (as below: the hybrid's 32-bit addressing): the generic kernel takes the step, with the table
+        const int rc = plugin ? plugin_prm(&a, batch, s, prm) : ns2d_launch_fast_prm<real>(a, batch, s, prm);
+        if (rc != BCN_ERR_UNSUPPORTED) return rc;
+      }
+      return ns2d_launch_generic_prm<real>(a, batch, s, prm);
+    }
     if (variant == 1 && plugin) {
       // BCN_ERR_UNSUPPORTED: the batch does not fit the plugin's addressing (ns2d_fast4_impl.h: 32-bit offsets from a
       // replica's u): the generic kernel takes the step
@@ -958,6 +982,10 @@ int bcn_api_version(void) { return BCN_API_VERSION; }
 int bcn_set_fast_plugin(bcn_env_t h, void* launch_fn, size_t scratch_elems) {
   if (!h) { bcn_set_error("null handle"); return BCN_ERR_ARG; }
   return h->set_fast_plugin(launch_fn, scratch_elems);
+}
+int bcn_set_fast_plugin_params(bcn_env_t h, void* launch_fn) {
+  if (!h) { bcn_set_error("null handle"); return BCN_ERR_ARG; }
+  return h->set_fast_plugin_params(launch_fn);
 }
 int bcn_set_noise(bcn_env_t h, double sigma, uint64_t seed, int64_t replica_offset) {
   if (!h) { bcn_set_error("null handle"); return BCN_ERR_ARG; }

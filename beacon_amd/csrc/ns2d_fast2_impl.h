@@ -34,6 +34,7 @@
 #include "bcn_dpp.h"
 #include "ns2d.h"
 #include "ns2d_device.h"
+#include "ns2d_prm.h"
 #include "ns2d_sched.h"
 
 namespace {
@@ -958,8 +959,9 @@ __device__ __forceinline__ void fast2_body(const NS2DArgs<real>& A, char* smem, 
 }
 
 template <typename real, int NX, int NY, int R, int KIND, bool EQ, int GF>
-__device__ __forceinline__ void fast2_unit(const NS2DArgs<real>& A, const int b, const int it_begin, const int it_end,
-                                           const bool first_chunk, const bool last_chunk, char* smem) {
+__device__ __forceinline__ void fast2_unit(const NS2DArgs<real>& BCN_PRM_A, const int b, const int it_begin, const int it_end,
+                                           const bool first_chunk, const bool last_chunk, char* smem BCN_PRM_KPARAM) {
+  BCN_PRM_LOCAL(KIND)   // ns2d_prm.h: nothing, or A = this replica's copy of the argument block
   using G = Fast2Geom<NX, NY, R, GF>;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (G::RL != R && w == G::NW - 1)
@@ -970,28 +972,28 @@ __device__ __forceinline__ void fast2_unit(const NS2DArgs<real>& A, const int b,
 
 // plain launch: one workgroup per replica, the whole action step
 template <typename real, int NX, int NY, int R, int KIND, bool EQ, int GF>
-__global__ __launch_bounds__(((NX + R - 1) / R) * 64) void ns2d_fast2_step(NS2DArgs<real> A) {
+__global__ __launch_bounds__(((NX + R - 1) / R) * 64) void ns2d_fast2_step(NS2DArgs<real> A BCN_PRM_KPARAM) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int b = blockIdx.x;
   if (A.mask && !A.mask[b]) return;
-  fast2_unit<real, NX, NY, R, KIND, EQ, GF>(A, b, 0, A.ndt_act, true, true, smem);
+  fast2_unit<real, NX, NY, R, KIND, EQ, GF>(A, b, 0, A.ndt_act, true, true, smem BCN_PRM_KARG);
 }
 
 // ticketed chunk scheduler (ns2d_sched.h): persistent workgroups draw (chunk, replica) units
 template <typename real, int NX, int NY, int R, int KIND, bool EQ, int GF>
 __global__ __launch_bounds__(((NX + R - 1) / R) * 64) void ns2d_fast2_sched(NS2DArgs<real> A, SchedCtl* ctl, int batch,
-                                                                          int nchunk) {
+                                                                          int nchunk BCN_PRM_KPARAM) {
   using G = Fast2Geom<NX, NY, R, GF>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // two words at the end of the `red` scratch row (block_sum uses red[0..NW), the transport sink red[16..17])
   unsigned int* s_words = reinterpret_cast<unsigned int*>(reinterpret_cast<real*>(smem) + G::EXCH + 128 + 24);
   ns2d_sched_loop<real>(A, ctl, batch, nchunk, s_words, [&](int b, int it0, int it1, bool first, bool last) {
-    fast2_unit<real, NX, NY, R, KIND, EQ, GF>(A, b, it0, it1, first, last, smem);
+    fast2_unit<real, NX, NY, R, KIND, EQ, GF>(A, b, it0, it1, first, last, smem BCN_PRM_KARG);
   });
 }
 
 template <typename real, int NX, int NY, int R, int KIND, bool EQ, int GF>
-int launch_fast2_eq(const NS2DArgs<real>& a, int batch, hipStream_t s) {
+int launch_fast2_eq(const NS2DArgs<real>& a, int batch, hipStream_t s BCN_PRM_PARAM) {
   using G = Fast2Geom<NX, NY, R, GF>;
   const size_t lds = G::lds_elems() * sizeof(real);
   if (GF && (!a.fscr || a.fscr_stride < G::scratch_elems())) { bcn_set_error("fast2 path: field scratch missing"); return BCN_ERR_UNSUPPORTED; }
@@ -1007,7 +1009,7 @@ int launch_fast2_eq(const NS2DArgs<real>& a, int batch, hipStream_t s) {
     c.sched_nbig = 0;
     c.sched_q = q;
     BCN_HIP(hipMemsetAsync(a.sched_ctl, 0, a.sched_bytes, s));
-    hipLaunchKernelGGL(ks, dim3(sp.grid), dim3(G::NT), lds, s, c, static_cast<SchedCtl*>(a.sched_ctl), batch, nchunk);
+    hipLaunchKernelGGL(ks, dim3(sp.grid), dim3(G::NT), lds, s, c, static_cast<SchedCtl*>(a.sched_ctl), batch, nchunk BCN_PRM_LAUNCH);
     BCN_HIP(hipGetLastError());
     if (a.host) a.host->launched = "ns2d_fast2_sched";
     return BCN_OK;
@@ -1016,17 +1018,17 @@ int launch_fast2_eq(const NS2DArgs<real>& a, int batch, hipStream_t s) {
   auto k = ns2d_fast2_step<real, NX, NY, R, KIND, EQ, GF>;
   static unsigned long long set = 0;
   if (ns2d_first_on_device(set)) BCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k, dim3(batch), dim3(G::NT), lds, s, c);
+  hipLaunchKernelGGL(k, dim3(batch), dim3(G::NT), lds, s, c BCN_PRM_LAUNCH);
   BCN_HIP(hipGetLastError());
   if (a.host) a.host->launched = "ns2d_fast2_step";
   return BCN_OK;
 }
 
 template <typename real, int NX, int NY, int R, int KIND, int GF = 0>
-int launch_fast2(const NS2DArgs<real>& a, int batch, hipStream_t s) {
+int launch_fast2(const NS2DArgs<real>& a, int batch, hipStream_t s BCN_PRM_PARAM) {
   // dx == dy (every reference configuration): one multiply per cell instead of two
-  if (a.cx == a.cy) return launch_fast2_eq<real, NX, NY, R, KIND, true, GF>(a, batch, s);
-  return launch_fast2_eq<real, NX, NY, R, KIND, false, GF>(a, batch, s);
+  if (a.cx == a.cy) return launch_fast2_eq<real, NX, NY, R, KIND, true, GF>(a, batch, s BCN_PRM_ARG);
+  return launch_fast2_eq<real, NX, NY, R, KIND, false, GF>(a, batch, s BCN_PRM_ARG);
 }
 
 }  // namespace

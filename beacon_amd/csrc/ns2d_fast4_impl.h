@@ -38,6 +38,7 @@
 #include "bcn_dpp.h"
 #include "ns2d.h"
 #include "ns2d_device.h"
+#include "ns2d_prm.h"
 #include "ns2d_sched.h"
 
 namespace {
@@ -299,8 +300,9 @@ __device__ __forceinline__ void f4_sweep(real (&Pv)[R + 1][RPL], const real (&Bv
 // timesteps [it_begin, it_end) of replica b: the whole action step (plain launch) or one chunk of it (ticket scheduler,
 // ns2d_sched.h: the replica's state lives in HBM between timesteps anyway, so a chunk needs no load / store of its own)
 template <typename real, int NX, int NY, int R, int RPL, int KIND, bool EQ>
-__device__ __forceinline__ void fast4_unit(const NS2DArgs<real>& A, const int b, const int it_begin, const int it_end,
-                                           const bool first_chunk, const bool last_chunk, char* smem) {
+__device__ __forceinline__ void fast4_unit(const NS2DArgs<real>& BCN_PRM_A, const int b, const int it_begin, const int it_end,
+                                           const bool first_chunk, const bool last_chunk, char* smem BCN_PRM_KPARAM) {
+  BCN_PRM_LOCAL(KIND)   // ns2d_prm.h: nothing, or A = this replica's copy of the argument block
   using G = Fast4Geom<NX, NY, R, RPL>;
   constexpr int NW = G::NW, NT = G::NT, SX = G::SX, P = G::P, RL = G::RL, NL = G::NL, RT = G::RT, CPL = G::CPL, HROWS = G::HROWS;
   constexpr int BR = G::br(sizeof(real)), NBLK = G::nblk(sizeof(real));
@@ -933,25 +935,25 @@ __device__ __forceinline__ void fast4_unit(const NS2DArgs<real>& A, const int b,
 }
 
 template <typename real, int NX, int NY, int R, int RPL, int KIND, bool EQ>
-__global__ __launch_bounds__((Fast4Geom<NX, NY, R, RPL>::NT)) void ns2d_fast4_step(NS2DArgs<real> A) {
+__global__ __launch_bounds__((Fast4Geom<NX, NY, R, RPL>::NT)) void ns2d_fast4_step(NS2DArgs<real> A BCN_PRM_KPARAM) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int b = blockIdx.x;
   if (A.mask && !A.mask[b]) return;
-  fast4_unit<real, NX, NY, R, RPL, KIND, EQ>(A, b, 0, A.ndt_act, true, true, smem);
+  fast4_unit<real, NX, NY, R, RPL, KIND, EQ>(A, b, 0, A.ndt_act, true, true, smem BCN_PRM_KARG);
 }
 
 // ticketed chunk scheduler (ns2d_sched.h): persistent workgroups draw (chunk, replica) units
 template <typename real, int NX, int NY, int R, int RPL, int KIND, bool EQ>
-__global__ __launch_bounds__((Fast4Geom<NX, NY, R, RPL>::NT)) void ns2d_fast4_sched(NS2DArgs<real> A, SchedCtl* ctl, int batch, int nchunk) {
+__global__ __launch_bounds__((Fast4Geom<NX, NY, R, RPL>::NT)) void ns2d_fast4_sched(NS2DArgs<real> A, SchedCtl* ctl, int batch, int nchunk BCN_PRM_KPARAM) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   unsigned int* s_words = reinterpret_cast<unsigned int*>(reinterpret_cast<real*>(smem) + 128);
   ns2d_sched_loop<real>(A, ctl, batch, nchunk, s_words, [&](int b, int it0, int it1, bool first, bool last) {
-    fast4_unit<real, NX, NY, R, RPL, KIND, EQ>(A, b, it0, it1, first, last, smem);
+    fast4_unit<real, NX, NY, R, RPL, KIND, EQ>(A, b, it0, it1, first, last, smem BCN_PRM_KARG);
   });
 }
 
 template <typename real, int NX, int NY, int R, int RPL, int KIND, bool EQ>
-int launch_fast4_eq(const NS2DArgs<real>& a, int batch, hipStream_t s) {
+int launch_fast4_eq(const NS2DArgs<real>& a, int batch, hipStream_t s BCN_PRM_PARAM) {
   using G = Fast4Geom<NX, NY, R, RPL>;
   const size_t lds = (size_t)G::lds_elems(sizeof(real)) * sizeof(real);
   if (!f4_fields_ok(a, (size_t)G::NCELL)) return BCN_ERR_UNSUPPORTED;   // (the caller falls back to the generic kernel)
@@ -968,7 +970,7 @@ int launch_fast4_eq(const NS2DArgs<real>& a, int batch, hipStream_t s) {
     c.sched_nbig = 0;
     c.sched_q = q;
     BCN_HIP(hipMemsetAsync(a.sched_ctl, 0, a.sched_bytes, s));
-    hipLaunchKernelGGL(ks, dim3(sp.grid), dim3(G::NT), lds, s, c, static_cast<SchedCtl*>(a.sched_ctl), batch, a.ndt_act / q);
+    hipLaunchKernelGGL(ks, dim3(sp.grid), dim3(G::NT), lds, s, c, static_cast<SchedCtl*>(a.sched_ctl), batch, a.ndt_act / q BCN_PRM_LAUNCH);
     BCN_HIP(hipGetLastError());
     if (a.host) a.host->launched = "ns2d_fast4_sched";
     return BCN_OK;
@@ -977,17 +979,17 @@ int launch_fast4_eq(const NS2DArgs<real>& a, int batch, hipStream_t s) {
   auto k = ns2d_fast4_step<real, NX, NY, R, RPL, KIND, EQ>;
   static unsigned long long set = 0;
   if (ns2d_first_on_device(set)) BCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k, dim3(batch), dim3(G::NT), lds, s, c);
+  hipLaunchKernelGGL(k, dim3(batch), dim3(G::NT), lds, s, c BCN_PRM_LAUNCH);
   BCN_HIP(hipGetLastError());
   if (a.host) a.host->launched = "ns2d_fast4_step";
   return BCN_OK;
 }
 
 template <typename real, int NX, int NY, int R, int RPL, int KIND>
-int launch_fast4(const NS2DArgs<real>& a, int batch, hipStream_t s) {
+int launch_fast4(const NS2DArgs<real>& a, int batch, hipStream_t s BCN_PRM_PARAM) {
   // dx == dy (every reference configuration): one multiply per cell instead of two
-  if (a.cx == a.cy) return launch_fast4_eq<real, NX, NY, R, RPL, KIND, true>(a, batch, s);
-  return launch_fast4_eq<real, NX, NY, R, RPL, KIND, false>(a, batch, s);
+  if (a.cx == a.cy) return launch_fast4_eq<real, NX, NY, R, RPL, KIND, true>(a, batch, s BCN_PRM_ARG);
+  return launch_fast4_eq<real, NX, NY, R, RPL, KIND, false>(a, batch, s BCN_PRM_ARG);
 }
 
 }  // namespace

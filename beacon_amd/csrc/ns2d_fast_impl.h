@@ -28,6 +28,7 @@
 #include "bcn_dpp.h"
 #include "ns2d.h"
 #include "ns2d_device.h"
+#include "ns2d_prm.h"
 #include "ns2d_sched.h"
 
 
@@ -1246,8 +1247,9 @@ __device__ __forceinline__ void fast_body(const NS2DArgs<real>& A, const int w, 
 
 // one unit of work, every wave with the body of its strip width (both bodies execute the same barriers)
 template <typename real, int NX, int NY, int R, int KIND, bool EQ, int GF>
-__device__ __forceinline__ void fast_unit(const NS2DArgs<real>& A, const int b, const int it_begin, const int it_end,
-                                          const bool first_chunk, const bool last_chunk, char* smem) {
+__device__ __forceinline__ void fast_unit(const NS2DArgs<real>& BCN_PRM_A, const int b, const int it_begin, const int it_end,
+                                          const bool first_chunk, const bool last_chunk, char* smem BCN_PRM_KPARAM) {
+  BCN_PRM_LOCAL(KIND)   // ns2d_prm.h: nothing, or A = this replica's copy of the argument block
   using G = FastGeom<NX, NY, R, GF>;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   // (GF == 2 -- float64, T in the global scratch --: ONE body, the narrow last strip's surplus columns dead: fast_body, DEADC)
@@ -1257,22 +1259,22 @@ __device__ __forceinline__ void fast_unit(const NS2DArgs<real>& A, const int b, 
 
 // plain launch: one workgroup per replica, timesteps [A.it_begin, A.it_end)
 template <typename real, int NX, int NY, int R, int KIND, bool EQ, int GF>
-__global__ __launch_bounds__((FastGeom<NX, NY, R, GF>::NT)) void ns2d_fast_step(NS2DArgs<real> A) {
+__global__ __launch_bounds__((FastGeom<NX, NY, R, GF>::NT)) void ns2d_fast_step(NS2DArgs<real> A BCN_PRM_KPARAM) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int b = A.order ? A.order[blockIdx.x] : (int)blockIdx.x;
   if (A.mask && !A.mask[b]) return;
-  fast_unit<real, NX, NY, R, KIND, EQ, GF>(A, b, A.it_begin, A.it_end, A.first_chunk != 0, A.last_chunk != 0, smem);
+  fast_unit<real, NX, NY, R, KIND, EQ, GF>(A, b, A.it_begin, A.it_end, A.first_chunk != 0, A.last_chunk != 0, smem BCN_PRM_KARG);
 }
 
 // ---- ticketed chunk scheduler (ns2d_sched.h) ---------------------------------------------------
 template <typename real, int NX, int NY, int R, int KIND, bool EQ, int GF>
-__global__ __launch_bounds__((FastGeom<NX, NY, R, GF>::NT)) void ns2d_fast_sched(NS2DArgs<real> A, SchedCtl* ctl, int batch, int nchunk) {
+__global__ __launch_bounds__((FastGeom<NX, NY, R, GF>::NT)) void ns2d_fast_sched(NS2DArgs<real> A, SchedCtl* ctl, int batch, int nchunk BCN_PRM_KPARAM) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // two words behind fast_body's scalars (no static __shared__ in front of the dynamic region)
   unsigned int* s_words = reinterpret_cast<unsigned int*>(reinterpret_cast<real*>(smem) +
                                                           FastGeom<NX, NY, R, GF>::EXCH + 224);
   ns2d_sched_loop<real>(A, ctl, batch, nchunk, s_words, [&](int b, int it0, int it1, bool first, bool last) {
-    fast_unit<real, NX, NY, R, KIND, EQ, GF>(A, b, it0, it1, first, last, smem);
+    fast_unit<real, NX, NY, R, KIND, EQ, GF>(A, b, it0, it1, first, last, smem BCN_PRM_KARG);
   });
 }
 
@@ -1301,7 +1303,7 @@ __global__ __launch_bounds__(1024) void ns2d_rank_by_work(const int32_t* sweeps,
 }
 
 template <typename real, int NX, int NY, int R, int KIND, bool EQ, int GF>
-int launch_fast_eq(const NS2DArgs<real>& a, int batch, hipStream_t s) {
+int launch_fast_eq(const NS2DArgs<real>& a, int batch, hipStream_t s BCN_PRM_PARAM) {
   using G = FastGeom<NX, NY, R, GF>;
   if (GF && (!a.fscr || a.fscr_stride < G::scratch_elems())) { bcn_set_error("fast path: field scratch missing"); return BCN_ERR_UNSUPPORTED; }
   const size_t lds = G::template lds_bytes<real>();
@@ -1324,7 +1326,7 @@ int launch_fast_eq(const NS2DArgs<real>& a, int batch, hipStream_t s) {
     ns2d_sched_chunks(a.ndt_act, SQ, (a.host ? a.host->sched_tail : 0), &c.sched_nbig, &nchunk);
     c.sched_q = SQ; c.order = nullptr; c.first_chunk = 1; c.last_chunk = 1; c.it_begin = 0; c.it_end = a.ndt_act;
     BCN_HIP(hipMemsetAsync(a.sched_ctl, 0, a.sched_bytes, s));
-    hipLaunchKernelGGL(ks, dim3(sched_grid), dim3(G::NT), lds, s, c, static_cast<SchedCtl*>(a.sched_ctl), batch, nchunk);
+    hipLaunchKernelGGL(ks, dim3(sched_grid), dim3(G::NT), lds, s, c, static_cast<SchedCtl*>(a.sched_ctl), batch, nchunk BCN_PRM_LAUNCH);
     BCN_HIP(hipGetLastError());
     if (a.host) a.host->launched = "ns2d_fast_sched";
     return BCN_OK;
@@ -1338,13 +1340,13 @@ int launch_fast_eq(const NS2DArgs<real>& a, int batch, hipStream_t s) {
   if (a.sched_ctl) BCN_HIP(hipMemsetAsync(a.sched_ctl, 0, a.sched_bytes, s));   // cycle counters
   if (!split) {
     c.it_end = a.ndt_act; c.last_chunk = 1;
-    hipLaunchKernelGGL(k, dim3(batch), dim3(G::NT), lds, s, c);
+    hipLaunchKernelGGL(k, dim3(batch), dim3(G::NT), lds, s, c BCN_PRM_LAUNCH);
   } else {
     c.it_end = Q; c.last_chunk = 0;
-    hipLaunchKernelGGL(k, dim3(batch), dim3(G::NT), lds, s, c);
+    hipLaunchKernelGGL(k, dim3(batch), dim3(G::NT), lds, s, c BCN_PRM_LAUNCH);
     hipLaunchKernelGGL(ns2d_rank_by_work, dim3(1), dim3(1024), 0, s, c.sweeps, a.ndt_act, Q, batch, c.order_out, c.mask);
     c.first_chunk = 0; c.last_chunk = 1; c.it_begin = Q; c.it_end = a.ndt_act; c.order = c.order_out;
-    hipLaunchKernelGGL(k, dim3(batch), dim3(G::NT), lds, s, c);
+    hipLaunchKernelGGL(k, dim3(batch), dim3(G::NT), lds, s, c BCN_PRM_LAUNCH);
   }
   BCN_HIP(hipGetLastError());
   if (a.host) a.host->launched = "ns2d_fast_step";
@@ -1352,11 +1354,11 @@ int launch_fast_eq(const NS2DArgs<real>& a, int batch, hipStream_t s) {
 }
 
 template <typename real, int NX, int NY, int R, int KIND, int GF = 0>
-int launch_fast(const NS2DArgs<real>& a, int batch, hipStream_t s) {
+int launch_fast(const NS2DArgs<real>& a, int batch, hipStream_t s BCN_PRM_PARAM) {
   static_assert(KIND == 0, "fast_body applies the rayleigh boundary conditions (no moving walls): mixing runs ns2d_fast2");
   // dx == dy (every reference configuration): one multiply per cell instead of two
-  if (a.cx == a.cy) return launch_fast_eq<real, NX, NY, R, KIND, true, GF>(a, batch, s);
-  return launch_fast_eq<real, NX, NY, R, KIND, false, GF>(a, batch, s);
+  if (a.cx == a.cy) return launch_fast_eq<real, NX, NY, R, KIND, true, GF>(a, batch, s BCN_PRM_ARG);
+  return launch_fast_eq<real, NX, NY, R, KIND, false, GF>(a, batch, s BCN_PRM_ARG);
 }
 
 

@@ -69,3 +69,11 @@ inline void bcn_derive_params(int kind, const double* p, const double* aux, doub
 // the generic 2D kernel with the table as a kernel argument of its own (ns2d_generic.hip): NS2DArgs keeps its layout, and with it
 // the register-resident kernels keep their code.  prm: [2][B] (rayleigh: kmom, ksc) / [3][B] (mixing: kmom, ksc, u_max)
 template <typename real> int ns2d_launch_generic_prm(const NS2DArgs<real>& a, int batch, hipStream_t s, const real* prm);
+
+// the register-resident kernels with the table as a kernel argument of their own (ns2d_prm.h; ns2d_fast_prm.hip, ns2d_fast_prm_f64.hip,
+// ns2d_fast2_prm.hip), selected per handle by bcn_set_option "params_kernel".  ns2d_launch_fast_prm reaches the two-rows-per-lane
+// built-ins the way ns2d_launch_fast does; ns2d_fast_supported_prm: the library has a table-reading kernel for this handle's grid.
+template <typename real> bool ns2d_fast_supported_prm(const NS2DArgs<real>& a);
+template <typename real> int ns2d_launch_fast_prm(const NS2DArgs<real>& a, int batch, hipStream_t s, const real* prm);
+template <typename real> bool ns2d_fast2_supported_prm(const NS2DArgs<real>& a);
+template <typename real> int ns2d_launch_fast2_prm(const NS2DArgs<real>& a, int batch, hipStream_t s, const real* prm);

@@ -17,7 +17,13 @@ change (the 110x64 float64 two-body kernel).  So no plugin is attache
 kernel, which is ordinary HIP without hand-scheduled code: float64 fields within 1e-9 with equal sweep counts (+-1), float32
 within the on-demand grids' tolerance.  Agreement is remembered next to the shared object (`<plugin>.ok`, tagged with the device
 and the HIP runtime, so another box checks again); a mismatch leaves `<plugin>.bad`, warns, and the env -- this one and every
-later one -- keeps the generic kernel."""
+later one -- keeps the generic kernel.
+
+Per-replica parameters (VecEnv.set_params) on a plugin grid.  The kernels that read the parameter table are a second shared
+object of the same grid, built with PRM_DEFS (-DBCN_JIT_PRM=1: csrc/ns2d_prm.h) -- the plain plugin keeps the code it has.  It is
+built, checked and attached only when an env asks for it (_VecNS2D.set_params_kernel("fast")); its verify() is the same comparison
+with a table of three distinct parameter sets on both envs (SELF_CHECK_PARAMS), so that the generic kernel reads the table and so
+does the plugin; its `.ok` / `.bad` markers are its own."""
 import ctypes as C
 import fcntl
 import hashlib
@@ -155,13 +161,20 @@ SELF_CHECK_F64 = dict(u=1e-9, v=1e-9, p=5e-8, S=1e-9)
 SELF_CHECK_F32 = dict(u=4.8e-6, v=5.4e-6, p=5.8e-4, S=7.7e-6)
 
 
-def compare_with_generic(make_env, kind, f64, ndt=6, batch=3, stats=None):
+# extra -D flags of a plugin's table-reading twin, and the table its self-check runs with (one set per replica of the batch of 3)
+PRM_DEFS = {"BCN_JIT_PRM": 1}
+SELF_CHECK_PARAMS = {0: dict(ra=(8.0e3, 5.0e4, 2.0e5)), 1: dict(re=(100.0, 200.0, 400.0), pe=(1.0e4, 1.0e5, 2.0e3))}
+
+
+def compare_with_generic(make_env, kind, f64, ndt=6, batch=3, stats=None, params=False):
     """(ok, report): `ndt` timesteps of a seeded state through the attached register-resident kernel -- plain launch and
     ticket scheduler (chunks of two timesteps on two persistent workgroups: hand-offs through HBM) -- against the generic
     kernel.  float64: fields within 1e-9 (p 5e-8), sweep counts within 1; float32: per field,
     SELF_CHECK_F32 (u 4.8e-6, v 5.4e-6, T/C 7.7e-6, p 5.8e-4: 10 x the largest plugin-vs-generic differences measured over every
     float32 case of tests/test_gpu_parity.py::test_jit_kernels_vs_oracle), counts within max(3, 2 %).  `stats`: a dict, filled
-    with the per-field differences and the sweep counts of each run."""
+    with the per-field differences and the sweep counts of each run.  `params`: every env carries the per-replica table
+    SELF_CHECK_PARAMS and the register-resident runs select the table-reading kernels (set_params_kernel("fast")): the check of a
+    parameter plugin, which also requires that those kernels, not the generic one, took the steps."""
     import numpy as np
     import torch
     runs = {}
@@ -172,6 +185,12 @@ def compare_with_generic(make_env, kind, f64, ndt=6, batch=3, stats=None):
             got = env.set_variant(variant)
             if sched is not None:
                 env.set_sched(*sched)
+            if params:
+                if variant == 1:
+                    env.set_params_kernel("fast")
+                with warnings.catch_warnings():
+                    warnings.simplefilter("ignore")      # (ParamsWarning of an env left on the generic kernel: reported as a mismatch below)
+                    env.set_params(**{k: np.resize(np.asarray(v), batch) for k, v in SELF_CHECK_PARAMS[kind].items()})
             env.reset()
             if kind == 0:
                 env.set_state(_seeded_rayleigh_state(env))
@@ -195,7 +214,7 @@ def compare_with_generic(make_env, kind, f64, ndt=6, batch=3, stats=None):
         ds = int(np.abs(sw - ref[1]).max())
         if stats is not None:
             stats[tag] = dict(dm, sweeps=ds, sweeps_max=int(ref[1].max()))
-        good = (got == 1 and not status.any() and not ref[2].any() and all(dm[F] <= tol[F] for F in "uvpS") and
+        good = (got == 1 and (not params or kname.startswith("ns2d_fast")) and not status.any() and not ref[2].any() and all(dm[F] <= tol[F] for F in "uvpS") and
                 ds <= (1 if f64 else max(3, int(0.02 * ref[1].max()))))
         ok = ok and good
         rep.append("%s (%s): u %.2e v %.2e p %.2e T/C %.2e sweeps %d of %d status %s%s"
@@ -224,8 +243,9 @@ def _verdict_on_disk(p, tag):
     return None, ""
 
 
-def verify(p, make_env, kind, f64):
-    """Sets p.verified (True / False) -- from the marker files next to the shared object, or by running compare_with_generic().
+def verify(p, make_env, kind, f64, params=False):
+    """Sets p.verified (True / False) -- from the marker files next to the shared object, or by running compare_with_generic()
+    (params: with a per-replica parameter table, for a plugin built with PRM_DEFS).
     One process per plugin runs the comparison: the N ranks of a fresh node queue on `<plugin>.vlock` and all but the first find
     the first one's verdict on disk when the lock comes to them."""
     global CHECKING
@@ -252,7 +272,7 @@ def verify(p, make_env, kind, f64):
             return settle(v, text)
         CHECKING = True
         try:
-            ok, rep = compare_with_generic(make_env, kind, f64)
+            ok, rep = compare_with_generic(make_env, kind, f64, params=params)
         except Exception as e:      # noqa: BLE001 -- could not run (out of memory, ...): no verdict, no plugin for this env
             warnings.warn("beacon_amd.jit: the self-check of %s could not run (%s: %s); the generic kernel stays selected for this env"
                           % (os.path.basename(p.path), type(e).__name__, e), JitWarning)
@@ -371,6 +391,8 @@ class Plugin(object):
         self.lib.bcn_jit_scratch_elems.restype = C.c_size_t
         self.lib.bcn_jit_lds_bytes.restype = C.c_size_t
         self.fn = C.cast(self.lib.bcn_jit_launch, C.c_void_p)
+        # a plugin built with PRM_DEFS: the launcher of its table-reading kernels (bcn_set_fast_plugin_params)
+        self.fn_prm = C.cast(self.lib.bcn_jit_launch_prm, C.c_void_p) if hasattr(self.lib, "bcn_jit_launch_prm") else None
         self.scratch = int(self.lib.bcn_jit_scratch_elems())
         self.lds = int(self.lib.bcn_jit_lds_bytes())
         self.verified = None          # True / False once verify() has compared it with the generic kernel
@@ -541,7 +563,12 @@ def fuzz_grid_keys():
 # per lane with dt x (1 + eps): a subtle error, under the old float32 bound of the self-check but over the per-field one)
 BREAK2_GRID = (60, 80, False, 0)
 BREAK2_DEFS = {"BCN_JIT_BREAK": 2, "BCN_JIT_BREAK_EPS": "3e-4"}
-EXTRA_BUILDS = [((75, 50, True, 0), {"BCN_JIT_BREAK": 1}), (BREAK2_GRID, BREAK2_DEFS)]
+# the parameter plugins (PRM_DEFS) of the grids tests/test_gpu_params_fast.py uses: one per kernel family -- rows 1; rows 2 float64
+# (global scratch); rows 2 mixing; rows 4 -- and the deliberately wrong one of the self-check's test
+PRM_TEST_GRIDS = [(75, 50, False, 0), (50, 75, True, 0), (100, 110, False, 1), (50, 150, False, 0)]
+PRM_BREAK_GRID = (75, 50, True, 0)
+EXTRA_BUILDS = ([((75, 50, True, 0), {"BCN_JIT_BREAK": 1}), (BREAK2_GRID, BREAK2_DEFS)] + [(g, dict(PRM_DEFS)) for g in PRM_TEST_GRIDS] +
+                [(PRM_BREAK_GRID, dict(PRM_DEFS, BCN_JIT_BREAK=1))])
 
 
 def _bounds_job(cell):

@@ -226,7 +226,8 @@ class EpisodeStats(object):
 
 class ParamsWarning(UserWarning):
     """A 2D env whose default kernel is a register-resident one received per-replica parameters: it steps through the generic
-    kernel until clear_params() (VecEnv.set_params)."""
+    kernel until clear_params() (VecEnv.set_params).  set_params_kernel("fast") on the env selects the register-resident kernels
+    that read the table instead, and with them in force set_params does not warn."""
 
 
 class VecEnv(object):
@@ -236,6 +237,7 @@ class VecEnv(object):
     PARAMS = ()              # names of the per-replica physical parameters (set_params), in the order of the C ABI's value rows
     needs_noise = False
     _plugin_defs = None      # extra -D flags of this class's on-demand kernels (tests: the deliberately broken plugin)
+    _plugin_prm_defs = None  # ... of their table-reading twins alone (set_params_kernel), on top of _plugin_defs
 
     def __init__(self, batch, device="cuda:0", dtype="f32"):
         if not torch.cuda.is_available():
@@ -611,9 +613,10 @@ class VecEnv(object):
         Graphs: the device table keeps its address from the first call on and later calls rewrite it in place, so a graph
         captured after a set_params replays whatever table is in force at replay time; one captured before the first call keeps
         the constructor's values.
-        2D envs: only the generic kernel reads the table.  While parameters are set the env steps through ns2d_generic_step
-        (kernel_name says so; the first call warns once with ParamsWarning when that is not the default kernel), and
-        clear_params() restores the previous dispatch."""
+        2D envs: by default only the generic kernel reads the table.  While parameters are set the env steps through
+        ns2d_generic_step (kernel_name says so; the first call warns once with ParamsWarning when that is not the default kernel),
+        and clear_params() restores the previous dispatch.  The fast path: set_params_kernel("fast") -- before or after this call --
+        selects the register-resident kernels that read the table (kernel_name then starts with ns2d_fast, and nothing warns)."""
         unknown = [k for k in cols if k not in self.PARAMS]
         if unknown:
             raise ValueError("%s.set_params: unknown parameter %s (this env has %s)" % (type(self).__name__, ", ".join(map(repr, unknown)),
@@ -642,7 +645,7 @@ class VecEnv(object):
         before = self.kernel_name
         _lib.check(self.lib.bcn_set_params(self.h, vals.ctypes.data_as(C.POINTER(C.c_double)), self._stream()))
         self._params = vals                       # re-applied when the handle is rebuilt (set_ndt_act)
-        if before != self.kernel_name and not getattr(self, "_params_warned", False):
+        if before != "ns2d_generic_step" and self.kernel_name == "ns2d_generic_step" and not getattr(self, "_params_warned", False):
             import warnings
             self._params_warned = True
             warnings.warn("%s: per-replica parameters are read by the generic kernel only: this env now steps through %s instead of "
@@ -840,17 +843,59 @@ class StepGraph(object):
 class _VecNS2D(VecEnv):
     """What the two 2D envs (rayleigh, mixing) share on the host."""
 
+    _kind = 0                # BCN_RAYLEIGH / BCN_MIXING
+    _params_kernel = "generic"
+
     def set_ndt_act(self, n):
         """Test hook: shorten the action step (the goldens for big grids use ndt_act=5).  The handle is built anew."""
         self.close()
         self.ndt_act = int(n)
         self.h = C.c_void_p()
         self._create()
+        self._apply_params_kernel()
         self._reapply_params()
         self.sweeps = torch.zeros((self.batch, self.ndt_act), dtype=torch.int32, device=self.device)
 
     def state_shape(self):
         return (4, self.ny + 2, self.nx + 2)
+
+    def set_params_kernel(self, which):
+        """Which kernel steps this env while per-replica parameters are set (set_params): "generic" (the default) -- the generic
+        kernel -- or "fast" -- the env's register-resident kernel in its table-reading form (include/beacon_hip.h: option
+        "params_kernel"; built into the library for the built-in grids).  On a grid with an on-demand kernel, "fast" builds that
+        kernel's table-reading twin (beacon_amd/jit.py: PRM_DEFS, a shared object of its own), compares it with the generic kernel
+        under a per-replica table before its first use, and attaches it; a twin that cannot be built or fails the comparison
+        warns with JitWarning and leaves the generic kernel in charge of steps with a table.  The choice survives set_ndt_act.
+        With "fast" a replica computes, bit for bit, what an env constructed with its parameters computes.  Returns self."""
+        if which not in ("fast", "generic"):
+            raise ValueError("%s.set_params_kernel: %r; \"fast\" or \"generic\"" % (type(self).__name__, which))
+        self._params_kernel = which
+        self._apply_params_kernel()
+        return self
+
+    def _apply_params_kernel(self):
+        fast = self._params_kernel == "fast"
+        _lib.check(self.lib.bcn_set_option(self.h, b"params_kernel", 1 if fast else 0))
+        if fast and getattr(self, "_plugin", None) is not None:
+            self._attach_plugin_params()
+
+    def _attach_plugin_params(self):
+        """The table-reading twin of this env's on-demand kernel: built, verified at its first use (jit.verify with a per-replica
+        table) and handed to the library (bcn_set_fast_plugin_params)."""
+        from . import jit
+        f64 = self.tdtype == torch.float64
+        defs = dict(self._plugin_defs or {})
+        defs.update(self._plugin_prm_defs or {})
+        defs.update(jit.PRM_DEFS)
+        p = jit.plugin_for(self.nx, self.ny, f64, self._kind, defs)
+        if p is None or p.fn_prm is None:
+            return
+        if p.verified is None and not jit.CHECKING:
+            ctor, cls, dev, dt = dict(self._ctor), type(self), self.device, dtype_name(self.tdtype)
+            jit.verify(p, lambda batch: cls(batch, dev, dt, **ctor), self._kind, f64, params=True)
+        if p.verified or jit.CHECKING:
+            _lib.check(self.lib.bcn_set_fast_plugin_params(self.h, p.fn_prm))
+            self._plugin_prm = p
 
 
 class VecRayleigh(_VecNS2D):
@@ -956,6 +1001,7 @@ class VecMixing(_VecNS2D):
     """mixing/mixing.py:16-378"""
 
     PARAMS = ("re", "pe")
+    _kind = 1
 
     action_is_int = True
 

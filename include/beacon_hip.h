@@ -266,6 +266,13 @@ BCN_API int bcn_api_version(void);
  * is passed here together with bcn_jit_scratch_elems().  Selects variant 1; launch_fn = NULL restores the built-in
  * choice.  The plugin must outlive the handle. */
 BCN_API int bcn_set_fast_plugin(bcn_env_t h, void* launch_fn, size_t scratch_elems);
+/* The same plugin's kernels that read the per-replica parameter table (bcn_set_params; option "params_kernel").  A plugin compiled
+ * with -DBCN_JIT_PRM=1 is a shared object of its own that exports, next to the symbols above,
+ *   int bcn_jit_launch_prm(const void* step_args, int batch, void* stream, const void* params_table_dev)
+ * Passed here AFTER bcn_set_fast_plugin (which clears it); launch_fn = NULL clears it.  Without it a plugin handle that has a
+ * table steps through the generic kernel whatever "params_kernel" says.  BCN_ERR_ARG for a handle without a plugin and for envs
+ * that take none. */
+BCN_API int bcn_set_fast_plugin_params(bcn_env_t h, void* launch_fn);
 /* Inlet noise on the device (burgers, shkadov).  The reference draws np.random.uniform(-sigma, sigma, 1) from numpy's global
  * stream -- once per action step (burgers.py:127), once per timestep (shkadov.py:204) -- and the *_step entry points take those
  * draws as noise_dev, so that a caller can reproduce the reference's stream.  A trainer that only needs noise of that law leaves
@@ -318,6 +325,12 @@ BCN_API int bcn_set_noise(bcn_env_t h, double sigma, uint64_t seed, int64_t repl
  *                 BCN_F64 always runs the ordered sweep
  *   "sched_tail"  short chunks that end a step of the ticket scheduler (0 = default 6; see bcn_set_sched)
  *   "generic_threads" 256 / 1024: workgroup size of the generic 2D kernel (0 = chosen by grid size)
+ *   "params_kernel" 0 / 1: which kernel steps a handle that has a per-replica parameter table (bcn_set_params).  0 (default): the
+ *                 generic kernel, whatever the variant.  1: with variant 1, the register-resident kernel of the grid in its
+ *                 table-reading form (built in for every built-in grid; a plugin: bcn_set_fast_plugin_params) -- a replica computes,
+ *                 bit for bit, what a handle created with its parameters computes on the plain register-resident kernel.  Where
+ *                 there is no such kernel (a plugin without the second launcher, a batch beyond the hybrid's 32-bit addressing) and
+ *                 with variant 0 the generic kernel takes the step; bcn_kernel_name says which one did.  Without a table: no effect
  *   "cells_per_thread" (1D envs) 1, 2, 4, 8 cells per thread (0 = chosen from grid and batch); "one_wave" (1D envs) 0 / 1:
  *                 grids up to 512 cells as one wave per replica with DPP halos (default 1)
  *   "obs_stage"   (lorenz, vortex) 1 = the observation rows [B][n_obs] go through LDS so that every store of a workgroup writes

@@ -3,7 +3,8 @@
 (SURVEY 8d algorithmic bytes / launch time) of the other solver kernels on one GPU, with the float64 C
 oracle timed on a bounded sample next to each.  Not the headline metric (that is bench.py).
 usage: python scripts/bench_envs.py [--steps K] [--no-cpu] [--only burgers,lorenz,...] [--params] [--variant 0]
---params gives every replica its own physical parameters (VecEnv.set_params: a full table; the 2D envs then run the generic kernel);
+--params gives every replica its own physical parameters (VecEnv.set_params: a full table; the 2D envs then run the generic kernel,
+or with --opt params_kernel=1 their register-resident kernels that read the table: _VecNS2D.set_params_kernel);
 "rayleigh" (the headline grid at B = 512) and "tall" run only when named in --only."""
 import argparse, ctypes as C, json, os, sys, time
 import numpy as np, torch
@@ -31,6 +32,17 @@ def spread_params(env):
     B = env.batch
     f = 1.0 + 0.1 * np.cos(np.arange(B) * 0.7)
     env.set_params(**{k: v * np.roll(f, 3 * i) for i, (k, v) in enumerate(env.params.items())})
+
+
+def apply_opts(env, opts):
+    """--opt name=value: bcn_set_option; params_kernel goes through set_params_kernel, which also attaches an on-demand grid's
+    table-reading kernel"""
+    for o in opts:
+        name, value = o.split("=")[0], int(o.split("=")[1])
+        if name == "params_kernel" and hasattr(env, "set_params_kernel"):
+            env.set_params_kernel("fast" if value else "generic")
+        else:
+            env.set_option(name, value)
 
 
 def main():
@@ -79,8 +91,7 @@ def main():
     if not args.only or "burgers" in args.only:
         B = 1024
         env = V.VecBurgers(B, dev, "f32", nx=512)
-        for o in args.opt:
-            env.set_option(o.split("=")[0], int(o.split("=")[1]))
+        apply_opts(env, args.opt)
         if args.params:
             spread_params(env)
         env.reset()
@@ -98,8 +109,7 @@ def main():
     if not args.only or "shkadov" in args.only:
         B = 1024
         env = V.VecShkadov(B, dev, "f32", None, L0=699.2, n_jets=10)
-        for o in args.opt:
-            env.set_option(o.split("=")[0], int(o.split("=")[1]))
+        apply_opts(env, args.opt)
         if args.params:
             spread_params(env)
         env.reset()
@@ -120,8 +130,7 @@ def main():
     if not args.only or "sloshing" in args.only:
         B = 1024
         env = V.VecSloshing(B, dev, "f32", packaged_init("sloshing"))
-        for o in args.opt:
-            env.set_option(o.split("=")[0], int(o.split("=")[1]))
+        apply_opts(env, args.opt)
         if args.params:
             spread_params(env)
         env.reset()
@@ -141,6 +150,7 @@ def main():
         env = V.VecMixing(B, dev, "f32")
         if args.variant >= 0:
             env.set_variant(args.variant)
+        apply_opts(env, args.opt)
         if args.params:
             spread_params(env)
         env.reset()
@@ -159,6 +169,7 @@ def main():
         env = V.VecRayleigh(B, dev, "f32", None, L=2.56, H=1.28)
         if args.variant >= 0:
             env.set_variant(args.variant)
+        apply_opts(env, args.opt)
         if args.params:
             spread_params(env)
         env.reset()
@@ -174,6 +185,9 @@ def main():
     if "tall" in args.only:      # a grid above ny = 128 (ns2d_fast4_impl.h): mixing(L=1, H=2) = 100x200, one replica per CU
         B = 256
         env = V.VecMixing(B, dev, "f32", L=1.0, H=2.0)
+        apply_opts(env, args.opt)
+        if args.params:
+            spread_params(env)
         env.reset()
         a = torch.as_tensor(rng.integers(0, 4, (K + 3, B)), dtype=torch.int32, device=dev)
         Km, Wm = min(K, 3), 3
@@ -193,8 +207,7 @@ def main():
         for B in (args.ode_batch or (1024, 65536, 1 << 20)):
             for dt in ("f32", "f64"):
                 env = cls(B, dev, dt)
-                for o in args.opt:
-                    env.set_option(o.split("=")[0], int(o.split("=")[1]))
+                apply_opts(env, args.opt)
                 env.reset()
                 gen = torch.Generator(device=dev)
                 gen.manual_seed(7)
