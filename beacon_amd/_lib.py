@@ -93,6 +93,7 @@ SIGNATURES = {
     "bcn_burgers_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "bcn_shkadov_create": (C.c_int, [C.POINTER(ShkadovCfg), C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
     "bcn_shkadov_reset": (C.c_int, [vp, vp, vp, vp]),
+    "bcn_shkadov_reset_random": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, vp]),
     "bcn_shkadov_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "bcn_sloshing_create": (C.c_int, [C.POINTER(SloshingCfg), C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
     "bcn_sloshing_reset": (C.c_int, [vp, vp, vp, vp]),

@@ -46,6 +46,8 @@ FILE_FLAGS = {"ns2d_fast.hip": ["-fno-slp-vectorize", "-ffp-contract=on", "-O2"]
                                      "-mllvm", "-amdgpu-sdwa-peephole=0"],
               # float64 1D kernels: the reference's operation order without FMA contraction -> bit-identical fields
               "env1d_f64.hip": ["-ffp-contract=off"],
+              # shkadov's random-start reset loops the float64 step body: the same flag, the same bits
+              "shkadov_warm_f64.hip": ["-ffp-contract=off"],
               # float64 ODE envs (lorenz, vortex): the host ports' operation order without FMA contraction -> bit-identical episodes
               "ode_f64.hip": ["-ffp-contract=off"]}
 

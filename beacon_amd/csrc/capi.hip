@@ -638,6 +638,18 @@ static int env1d_step_t(bcn_env_t h, int (*launch)(const Env1DArgs<real>&, int, 
   return rc;
 }
 
+// shkadov.reset with rand_init in one launch: the argument block of a reset (no actions, no noise tensor, no rwd / done / trunc / status),
+// the warm launcher's three arguments behind it; the handle keeps what was dispatched, as after a step
+template <typename real>
+static int shkadov_reset_random_t(bcn_env_t h, const void* init, const int32_t* n_steps, int rand_steps, int32_t* n_out, void* obs, void* stream) {
+  DeviceGuard g(h->device);
+  Env1DLaunch note;
+  const int rc = shkadov_launch_warm<real>(env1d_io<real>(h, nullptr, nullptr, init, obs, nullptr, nullptr, nullptr, nullptr), h->batch, n_steps,
+                                           rand_steps, n_out, static_cast<hipStream_t>(stream), &note);
+  static_cast<Env1D<real>*>(h)->last = rc ? Env1DLaunch() : note;
+  return rc;
+}
+
 // ------------------------------------------------------------------------------------------
 // snapshots (snapshot.h): which arrays of a handle are state, and where they sit in a snapshot of n replicas
 // ------------------------------------------------------------------------------------------
@@ -854,6 +866,15 @@ int bcn_shkadov_create(const bcn_shkadov_cfg* c, int batch, int dtype, int devic
 int bcn_shkadov_reset(bcn_env_t h, const void* init_fields_dev, void* obs_dev, void* stream) {
   BCN_CHECK_KIND(h, BCN_SHKADOV);
   return BCN_BY_DTYPE(h->dtype, env1d_reset_t, h, shkadov_launch_reset, init_fields_dev, obs_dev, stream);
+}
+int bcn_shkadov_reset_random(bcn_env_t h, const void* init_fields_dev, const int32_t* n_steps_dev, int rand_steps, int32_t* n_out_dev,
+                             void* obs_dev, void* stream) {
+  BCN_CHECK_KIND(h, BCN_SHKADOV);
+  if (rand_steps < 0 || rand_steps > 65535) {
+    bcn_set_error("bcn_shkadov_reset_random: rand_steps %d outside [0, 65535]", rand_steps);
+    return BCN_ERR_ARG;
+  }
+  return BCN_BY_DTYPE(h->dtype, shkadov_reset_random_t, h, init_fields_dev, n_steps_dev, rand_steps, n_out_dev, obs_dev, stream);
 }
 int bcn_shkadov_step(bcn_env_t h, const void* actions_dev, const void* noise_dev, void* obs_dev, void* rwd_dev,
                      uint8_t* done_dev, uint8_t* trunc_dev, int32_t* status_dev, void* stream) {

@@ -82,5 +82,9 @@ template <typename real> int burgers_launch_step(const Env1DArgs<real>& a, int b
 template <typename real> int burgers_launch_reset(const Env1DArgs<real>& a, int batch, hipStream_t s);
 template <typename real> int shkadov_launch_step(const Env1DArgs<real>& a, int batch, hipStream_t s, Env1DLaunch* note);
 template <typename real> int shkadov_launch_reset(const Env1DArgs<real>& a, int batch, hipStream_t s);
+// shkadov.reset with its rand_init loop in one launch (shkadov_warm_f32.hip / shkadov_warm_f64.hip): reset, n[b] action steps of the zero
+// action under device noise, n[b] from n_steps [B] (clamped to [0, rand_steps]) or drawn on {0 .. rand_steps}; n_out [B] or NULL
+template <typename real> int shkadov_launch_warm(const Env1DArgs<real>& a, int batch, const int32_t* n_steps, int rand_steps, int32_t* n_out,
+                                                 hipStream_t s, Env1DLaunch* note);
 template <typename real> int sloshing_launch_step(const Env1DArgs<real>& a, int batch, hipStream_t s, Env1DLaunch* note);
 template <typename real> int sloshing_launch_reset(const Env1DArgs<real>& a, int batch, hipStream_t s);

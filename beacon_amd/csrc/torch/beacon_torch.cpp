@@ -1,5 +1,6 @@
 // beacon_torch.cpp -- the thin PyTorch-ROCm extension over the C ABI (include/beacon_hip.h): torch.library ops
 //   beacon::{rayleigh,mixing,burgers,shkadov,sloshing,lorenz,vortex}_{step,reset}(int handle, Tensor ...) -> ()
+//   beacon::shkadov_reset_random(int handle, Tensor? init_fields, Tensor? n_steps, int rand_steps, Tensor? n_out, Tensor obs) -> ()
 //   beacon::snapshot_{save,load}(int handle, Tensor ...) -> ()
 //   beacon::episode_track(int handle, Tensor out_buf, Tensor ep_buf, Tensor? mask) -> ()
 // Each op is ONE dispatcher call that takes device tensors, reads torch's current HIP stream in C++ and forwards to the
@@ -135,6 +136,16 @@ void shkadov_reset(int64_t h_, OptT init_fields, const Tensor& obs) {
   const Outs o(h_, obs);
   check(bcn_shkadov_reset(o.h, dpo(init_fields, o.h, true, "init_fields"), o.obs, o.stream), "bcn_shkadov_reset");
 }
+// shkadov.reset with rand_init (shkadov.py:119-123) in one launch: n_steps (the counts; None: drawn on the device) and n_out (the
+// counts taken) are int32 [B]
+void shkadov_reset_random(int64_t h_, OptT init_fields, OptT n_steps, int64_t rand_steps, OptT n_out, const Tensor& obs) {
+  const Outs o(h_, obs);
+  TORCH_CHECK(rand_steps >= 0 && rand_steps <= 65535, "rand_steps: ", rand_steps, " outside [0, 65535]");
+  const int32_t* n = n_steps.has_value() ? i32(*n_steps, o.h, 1, "n_steps") : nullptr;
+  int32_t* taken = n_out.has_value() ? i32(*n_out, o.h, 1, "n_out") : nullptr;
+  check(bcn_shkadov_reset_random(o.h, dpo(init_fields, o.h, true, "init_fields"), n, (int)rand_steps, taken, o.obs, o.stream),
+        "bcn_shkadov_reset_random");
+}
 void shkadov_step(int64_t h_, OptT actions, OptT noise, const Tensor& obs, const Tensor& rwd, const Tensor& done, const Tensor& trunc,
                   const Tensor& status) {
   const Outs o(h_, obs, rwd, done, trunc, status);
@@ -213,6 +224,7 @@ void episode_track(int64_t h_, const Tensor& out_buf, const Tensor& ep_buf, OptT
 // Meta (fake-tensor) kernels: the ops return nothing and their outputs keep their shapes, so tracing needs no more than this.
 void reset2_meta(int64_t, const Tensor&) {}
 void reset3_meta(int64_t, OptT, const Tensor&) {}
+void reset_random_meta(int64_t, OptT, OptT, int64_t, OptT, const Tensor&) {}
 void rayleigh_step_meta(int64_t, OptT, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&) {}
 void mixing_step_meta(int64_t, OptT, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&) {}
 void noisy_step_meta(int64_t, OptT, OptT, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&) {}
@@ -236,6 +248,7 @@ TORCH_LIBRARY(beacon, m) {
   m.def("burgers_step(int handle, Tensor? actions, Tensor? noise, Tensor(a!) obs, Tensor(b!) rwd, Tensor(c!) done, Tensor(d!) trunc, "
         "Tensor(e!) status) -> ()");
   m.def("shkadov_reset(int handle, Tensor? init_fields, Tensor(a!) obs) -> ()");
+  m.def("shkadov_reset_random(int handle, Tensor? init_fields, Tensor? n_steps, int rand_steps, Tensor(a!)? n_out, Tensor(b!) obs) -> ()");
   m.def("shkadov_step(int handle, Tensor? actions, Tensor? noise, Tensor(a!) obs, Tensor(b!) rwd, Tensor(c!) done, Tensor(d!) trunc, "
         "Tensor(e!) status) -> ()");
   m.def("sloshing_reset(int handle, Tensor? init_fields, Tensor(a!) obs) -> ()");
@@ -260,6 +273,7 @@ TORCH_LIBRARY_IMPL(beacon, CUDA, m) {
   m.impl("burgers_reset", &burgers_reset);
   m.impl("burgers_step", &burgers_step);
   m.impl("shkadov_reset", &shkadov_reset);
+  m.impl("shkadov_reset_random", &shkadov_reset_random);
   m.impl("shkadov_step", &shkadov_step);
   m.impl("sloshing_reset", &sloshing_reset);
   m.impl("sloshing_step", &sloshing_step);
@@ -280,6 +294,7 @@ TORCH_LIBRARY_IMPL(beacon, Meta, m) {
   m.impl("burgers_reset", &reset2_meta);
   m.impl("burgers_step", &noisy_step_meta);
   m.impl("shkadov_reset", &reset3_meta);
+  m.impl("shkadov_reset_random", &reset_random_meta);
   m.impl("shkadov_step", &noisy_step_meta);
   m.impl("sloshing_reset", &reset3_meta);
   m.impl("sloshing_step", &sloshing_step_meta);

@@ -95,18 +95,20 @@ _OPS = ("rayleigh_reset", "rayleigh_step", "mixing_reset", "mixing_step", "burge
 _ODE_OPS = ("lorenz_reset", "lorenz_step", "vortex_reset", "vortex_step")     # the ODE envs (csrc/ode_env.h)
 _STATE_OPS = ("snapshot_save", "snapshot_load")                               # every env (csrc/snapshot.hip)
 _EPISODE_OPS = ("episode_track",)                                             # every env (csrc/episode.hip)
+_WARM_OPS = ("shkadov_reset_random",)                                         # shkadov (csrc/shkadov_warm_f32.hip, _f64.hip)
+_ALL_OPS = _OPS + _ODE_OPS + _STATE_OPS + _EPISODE_OPS + _WARM_OPS
 
 
 def _op_table():
     """{name: torch.ops.beacon.<name>.default} of the torch extension (beacon_amd/torch_ext.py), or None without it."""
     from . import torch_ext
     ops = torch_ext.load()
-    return None if ops is None else {n: getattr(ops, n).default for n in _OPS + _ODE_OPS + _STATE_OPS + _EPISODE_OPS}
+    return None if ops is None else {n: getattr(ops, n).default for n in _ALL_OPS}
 
 
 def _c_table(lib):
     """{name: bcn_<name> of libbeacon_hip.so}: the same entry points through ctypes, resolved once per env."""
-    return {n: getattr(lib, "bcn_" + n) for n in _OPS + _ODE_OPS + _STATE_OPS + _EPISODE_OPS}
+    return {n: getattr(lib, "bcn_" + n) for n in _ALL_OPS}
 
 
 class Snapshot(object):
@@ -312,7 +314,7 @@ class VecEnv(object):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _call(self, name, *args):
-        """The entry point `name` (one of _OPS, _ODE_OPS, _STATE_OPS, _EPISODE_OPS) through the binding in force: the torch op, or
+        """The entry point `name` (one of _OPS, _ODE_OPS, _STATE_OPS, _EPISODE_OPS, _WARM_OPS) through the binding in force: the torch op, or
         bcn_<name> through ctypes.  `args`: what both take between the handle and the stream, in their common order -- tensors
         (None: a null pointer) and ints; the op reads torch's current stream itself, ctypes gets it appended."""
         if self._ops is not None:
@@ -1125,6 +1127,7 @@ class VecShkadov(VecEnv):
     PARAMS = ("delta",)
 
     needs_noise = True
+    rand_steps = None        # set_random_init: None = every reset restarts from the film itself
 
     def __init__(self, batch, device="cuda:0", dtype="f32", init_fields=None, L0=150.0, n_jets=5,
                  jet_pos=150.0, jet_space=10.0, delta=0.1, t_act=20.0, seed=0):
@@ -1137,6 +1140,9 @@ class VecShkadov(VecEnv):
         self._init_dev = None
         if self._init_np is not None:
             self._init_dev = self._real(np.ascontiguousarray(self._init_np[:, :self.nx]), (2, self.nx))
+        self.rand_steps = None                     # set_random_init: None = reset() restarts from the packaged film itself
+        self._n_rand = torch.zeros((self.batch,), dtype=torch.int32, device=self.device)   # written by the fused reset
+        self.n_rand = self._n_rand
 
     def _make_spaces(self):
         self.action_space = spaces.box(-1.0, 1.0, (self.n_jets,))               # shkadov.py:96-99
@@ -1184,7 +1190,11 @@ class VecShkadov(VecEnv):
     def reset_random(self, rand_steps=400, n_steps=None):
         """reset() followed by a per-replica random number of uncontrolled steps, the batched form
         of shkadov.reset with rand_init (shkadov.py:119-123: n = random.randint(0, rand_steps)).
-        n_steps: optional explicit int tensor [B]; drawn on the device otherwise."""
+        n_steps: optional explicit int tensor [B]; drawn on the device otherwise.
+        This is the whole-batch HOST loop (one host synchronisation, up to rand_steps masked step() launches, counts from the
+        torch generator `gen`); it cannot be captured and cannot restart only the replicas that finished.  set_random_init()
+        makes every reset -- reset(mask), reset_done(), step_autoreset(), capture(..., autoreset=True) -- do the same thing in
+        one kernel launch on the device."""
         self.reset()
         if n_steps is None:
             n_steps = torch.randint(0, rand_steps + 1, (self.batch,), generator=self.gen, device=self.device)
@@ -1195,8 +1205,53 @@ class VecShkadov(VecEnv):
         self.set_stp(0)
         return self.obs, None
 
+    def set_random_init(self, rand_steps=400):
+        """The reference's default reset, rand_init = True (shkadov.py:51-52, 119-123), on the device: while this is on, every
+        reset of this env -- reset(), reset(mask), reset_done(), step_autoreset(), capture(..., autoreset=True) -- reloads the film
+        and then lets each replica it touches take its OWN n[b] uncontrolled action steps under the device's inlet noise, n[b]
+        uniform on {0 .. rand_steps}, in ONE kernel launch (bcn_shkadov_reset_random: no host synchronisation, the fields stay
+        in registers between the steps), after which stp is 0 again.  `n_rand` (int32 [B]) holds the counts of the last such
+        reset for the replicas it touched.  set_random_init(None) turns it off (the default): reset() restarts from the film itself.
+        The counts come from the env's Philox stream (set_noise_seed: seed, replica_offset, the per-replica draw counter that a
+        Snapshot carries), one tick per reset: consecutive resets differ, a restored run repeats, shards agree with the single
+        batch.  rand_steps is configuration like sigma and the seed -- a kernel argument, recorded in no Snapshot; a captured
+        graph keeps the value it was recorded with.  With sigma = 0 the warm-up runs without noise."""
+        if rand_steps is not None:
+            if isinstance(rand_steps, bool) or not isinstance(rand_steps, (int, np.integer)) or not 0 <= int(rand_steps) <= 65535:
+                raise ValueError("VecShkadov.set_random_init: rand_steps must be an integer in [0, 65535] or None, got %r" % (rand_steps,))
+            rand_steps = int(rand_steps)
+        self.rand_steps = rand_steps
+        return self
+
+    def reset_random_device(self, n_steps=None, mask=None):
+        """The reset that set_random_init() switches on, called directly: reset(mask) with EXPLICIT counts n_steps (int [B]; each
+        clamped to [0, rand_steps] by the kernel), or with drawn ones (None) -- one launch either way, and the draw counter ticks
+        either way.  For tests, measurements and callers who want the reference's numbers of steps.  Needs set_random_init()."""
+        if self.rand_steps is None:
+            raise ValueError("VecShkadov.reset_random_device: set_random_init(rand_steps) first")
+        if n_steps is not None:
+            n_steps = torch.as_tensor(n_steps)
+            if n_steps.numel() != self.batch or n_steps.is_floating_point():
+                raise ValueError("VecShkadov.reset_random_device: n_steps must hold %d integers" % self.batch)
+            n_steps = n_steps.to(device=self.device, dtype=torch.int32).reshape(self.batch).contiguous()
+        self._apply_mask(mask)
+        try:
+            self._reset_random(n_steps)
+        finally:
+            if mask is not None:
+                self._apply_mask(None)
+        return self.obs, None
+
+    def _reset_random(self, n_steps=None):
+        self._keep_n = n_steps                     # alive behind the asynchronous launch
+        self.n_rand = self._n_rand
+        self._call("shkadov_reset_random", self._init_dev, n_steps, self.rand_steps, self._n_rand, self.obs)
+
     def _reset(self):
-        self._call("shkadov_reset", self._init_dev, self.obs)
+        if self.rand_steps is not None:
+            self._reset_random(None)
+        else:
+            self._call("shkadov_reset", self._init_dev, self.obs)
 
     def _step(self, actions, noise=None):
         a = self._real(actions, (self.batch, self.n_jets))

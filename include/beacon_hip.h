@@ -140,9 +140,26 @@ typedef struct {
 
 /* replaces shkadov.__init__ (shkadov.py:20-110) */
 BCN_API int bcn_shkadov_create(const bcn_shkadov_cfg* cfg, int batch, int dtype, int device, bcn_env_t* out);
-/* replaces shkadov.reset without its rand_init loop (shkadov.py:113-146): init_fields_dev [2][nx]
- * (h_init, q_init) shared by all replicas, NULL = flat film h=q=1 (reset_fields only). */
+/* replaces shkadov.reset with rand_init = False (shkadov.py:113-146; bcn_shkadov_reset_random below is the reference's default,
+ * rand_init = True): init_fields_dev [2][nx] (h_init, q_init) shared by all replicas, NULL = flat film h=q=1 (reset_fields only). */
 BCN_API int bcn_shkadov_reset(bcn_env_t h, const void* init_fields_dev, void* obs_dev, void* stream);
+/* replaces shkadov.reset with rand_init = True (shkadov.py:113-146 with :119-123), in ONE launch and without host work: every replica
+ * that bcn_set_mask leaves on is reset as by bcn_shkadov_reset and then takes n[b] action steps of the zero action under the
+ * device's inlet noise (bcn_set_noise; sigma = 0: no noise) -- what n[b] calls of bcn_shkadov_step(actions NULL, noise NULL) compute
+ * for it, bit for bit, with the fields kept in registers in between -- after which its episode counter is 0 again.
+ *   n[b]: n_steps_dev[b] clamped to [0, rand_steps], or, with n_steps_dev NULL, uniform on {0 .. rand_steps} from the env's Philox
+ *         stream: key = the noise seed, counter = (replica_offset + b, the replica's draw counter, 0, 1) -- the last word is 0 in every
+ *         noise draw -- mapped by the high word of word0 * (rand_steps + 1).  0 <= rand_steps <= 65535 (the reference: 400).
+ *   The count costs one tick of the replica's draw counter (a snapshot segment), with n_steps_dev and with sigma = 0 as well, and
+ *   every warm-up step with noise one more, as a step does: two resets in a row draw different counts, a run restored from a
+ *   snapshot redraws the same ones, and a sharded batch draws what the single one draws for the same global replica.
+ *   Written: the fields, stp = 0, the stored actions (0), the observation rows obs_dev [B][n_obs] and n_out_dev [B] (NULL: not
+ *   wanted) of the replicas that were reset.  There are no rwd / done / trunc / status arguments: a reset leaves those rows alone.
+ *   A film that blows up during the warm-up is not flagged here (the reference prints and carries on); the first step reports it.
+ * Per-replica delta (bcn_set_params) is honoured.  bcn_kernel_name / bcn_kernel_shape afterwards: "shkadov_warm_k" and the (K, NT)
+ * the next bcn_shkadov_step will run with. */
+BCN_API int bcn_shkadov_reset_random(bcn_env_t h, const void* init_fields_dev, const int32_t* n_steps_dev /* [B] or NULL: drawn */,
+                             int rand_steps, int32_t* n_out_dev /* [B] or NULL */, void* obs_dev, void* stream);
 /* replaces shkadov.step (shkadov.py:161-264).  actions_dev[B][n_jets] (NULL = repeat last);
  * noise_dev[B][ndt_act]: inlet draws, one per timestep (shkadov.py:204). */
 BCN_API int bcn_shkadov_step(bcn_env_t h, const void* actions_dev, const void* noise_dev, void* obs_dev,
