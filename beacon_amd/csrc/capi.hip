@@ -14,6 +14,7 @@
 #include "params.h"
 #include "snapshot.h"
 #include "episode.h"
+#include "shkadov_jets.h"
 
 static thread_local char g_err[512] = "";
 
@@ -762,6 +763,53 @@ int episode_build(bcn_env_t h, bcn_snapshot_seg* lay, size_t* bytes) {
   return BCN_EP_NSEG;
 }
 
+// Lays out the per-jet buffer of a shkadov handle (shkadov_jets.h): the four [B][n_jets] segments into `lay` (room for
+// BCN_JETS_NSEG) and / or the bytes it takes.  Only batch, jet count (the action length) and dtype of the handle are used.
+int jets_build(bcn_env_t h, bcn_snapshot_seg* lay, size_t* bytes) {
+  const size_t B = (size_t)h->batch, esz = h->esz, nj = (size_t)h->n_act;
+  if (h->batch < 1 || h->n_act < 1 || B * nj > 0x7fffffffull) {
+    bcn_set_error("shkadov jets: batch %d x %d jets is outside what one launch covers", h->batch, h->n_act);
+    return -1;
+  }
+  const struct { const char* name; int elem; size_t el; } d[BCN_JETS_NSEG] = {
+      {"rwd_jets", BCN_SNAP_REAL, esz}, {"ret", BCN_SNAP_REAL, esz}, {"last_ret", BCN_SNAP_REAL, esz}, {"sum_ret", BCN_SNAP_F64, 8}};
+  size_t off = 0;
+  for (int k = 0; k < BCN_JETS_NSEG; k++) {
+    off = snap_up16(off);
+    if (lay) {
+      memset(&lay[k], 0, sizeof(lay[k]));
+      strncpy(lay[k].name, d[k].name, sizeof(lay[k].name) - 1);
+      lay[k].offset = off; lay[k].elem = d[k].elem; lay[k].planes = 1; lay[k].row_elems = (int64_t)nj;
+    }
+    off += B * nj * d[k].el;
+  }
+  if (bytes) *bytes = snap_up16(off);
+  return BCN_JETS_NSEG;
+}
+
+// bcn_shkadov_jet_rewards of a checked shkadov handle: the film and the jet layout come from the handle's argument block, the
+// replica mask is the one bcn_set_mask left there, status / done / trunc are those of the step's packed outputs
+template <typename real>
+int shkadov_jets_t(bcn_env_t h, const char* out, char* jets, const bcn_snapshot_seg* lay, int with_stats, void* stream) {
+  const Env1DArgs<real>& e = static_cast<Env1D<real>*>(h)->a;
+  const bcn_out_layout_t o = bcn_out_layout((size_t)h->batch, (size_t)h->n_obs, h->esz);
+  ShkadovJetsArgs<real> a;
+  a.h = e.f0;
+  a.status = reinterpret_cast<const int32_t*>(out + o.status);
+  a.done = reinterpret_cast<const uint8_t*>(out + o.done); a.trunc = reinterpret_cast<const uint8_t*>(out + o.trunc);
+  a.mask = e.mask;
+  a.rwd_jets = reinterpret_cast<real*>(jets + lay[0].offset);
+  a.ret = with_stats ? reinterpret_cast<real*>(jets + lay[1].offset) : nullptr;
+  a.last_ret = reinterpret_cast<real*>(jets + lay[2].offset);
+  a.sum_ret = reinterpret_cast<double*>(jets + lay[3].offset);
+  a.npairs = (unsigned)h->batch * (unsigned)e.n_jets;
+  a.n = e.n; a.nx = e.nx;
+  a.n_jets = e.n_jets; a.jet_pos = e.jet_pos; a.jet_space = e.jet_space; a.l_rwd = e.l_rwd;
+  a.dx = e.dx; a.blowup_rwd = e.blowup_rwd;
+  DeviceGuard g(h->device);
+  return shkadov_jets_launch<real>(a, static_cast<hipStream_t>(stream));
+}
+
 // bcn_set_params: the table of derived constants of every replica, narrowed once to the handle's dtype, row k of replica b at
 // [k * B + b]
 template <typename real>
@@ -1178,6 +1226,33 @@ int bcn_episode_track(bcn_env_t h, const void* out_buf_dev, void* ep_buf_dev, co
   a.f64 = h->dtype == BCN_F64;
   DeviceGuard g(h->device);
   return episode_launch(a, static_cast<hipStream_t>(stream));
+}
+// ---- per-jet rewards and returns of shkadov (shkadov_jets.h) --------------------------------------
+size_t bcn_shkadov_jets_bytes(bcn_env_t h) {
+  size_t bytes = 0;
+  if (!h) { bcn_set_error("bcn_shkadov_jets_bytes: null handle"); return 0; }
+  if (h->kind != BCN_SHKADOV) { bcn_set_error("bcn_shkadov_jets_bytes: handle is not a BCN_SHKADOV env"); return 0; }
+  if (jets_build(h, nullptr, &bytes) < 0) return 0;         // (jets_build has set the message)
+  return bytes;
+}
+int bcn_shkadov_jets_layout(bcn_env_t h, bcn_snapshot_seg* segs, int max_segs) {
+  if (!h || (max_segs > 0 && !segs)) { bcn_set_error("bcn_shkadov_jets_layout: null handle/array"); return 0; }
+  if (h->kind != BCN_SHKADOV) { bcn_set_error("bcn_shkadov_jets_layout: handle is not a BCN_SHKADOV env"); return 0; }
+  bcn_snapshot_seg lay[BCN_JETS_NSEG];
+  const int nd = jets_build(h, lay, nullptr);
+  for (int k = 0; k < nd && k < max_segs; k++) segs[k] = lay[k];
+  return nd < 0 ? 0 : nd;
+}
+int bcn_shkadov_jet_rewards(bcn_env_t h, const void* out_buf_dev, void* jets_buf_dev, int with_stats, void* stream) {
+  if (!h || !out_buf_dev || !jets_buf_dev) { bcn_set_error("bcn_shkadov_jet_rewards: null handle/buffer"); return BCN_ERR_ARG; }
+  if (h->kind != BCN_SHKADOV) { bcn_set_error("bcn_shkadov_jet_rewards: handle is not a BCN_SHKADOV env"); return BCN_ERR_ARG; }
+  if (!snap_ptr_ok(out_buf_dev) || !snap_ptr_ok(jets_buf_dev)) {
+    bcn_set_error("bcn_shkadov_jet_rewards: buffers must be 16-byte aligned");
+    return BCN_ERR_ARG;
+  }
+  bcn_snapshot_seg lay[BCN_JETS_NSEG];
+  if (jets_build(h, lay, nullptr) < 0) return BCN_ERR_ARG;
+  return BCN_BY_DTYPE(h->dtype, shkadov_jets_t, h, static_cast<const char*>(out_buf_dev), static_cast<char*>(jets_buf_dev), lay, with_stats, stream);
 }
 const char* bcn_kernel_name(bcn_env_t h) { return h ? h->kernel_name() : ""; }
 int bcn_kernel_shape(bcn_env_t h, int* cells_per_thread, int* threads) {

@@ -3,6 +3,7 @@
 //   beacon::shkadov_reset_random(int handle, Tensor? init_fields, Tensor? n_steps, int rand_steps, Tensor? n_out, Tensor obs) -> ()
 //   beacon::snapshot_{save,load}(int handle, Tensor ...) -> ()
 //   beacon::episode_track(int handle, Tensor out_buf, Tensor ep_buf, Tensor? mask) -> ()
+//   beacon::shkadov_jet_rewards(int handle, Tensor out_buf, Tensor jets_buf, int with_stats) -> ()
 // Each op is ONE dispatcher call that takes device tensors, reads torch's current HIP stream in C++ and forwards to the
 // bcn_* entry point of libbeacon_hip.so -- no ctypes marshalling, no Python-side stream query (what the per-call host cost of
 // the ctypes binding was made of: scripts/host_cost.py), and an op CUDA-graph capture and fake-tensor tracing can see (Meta kernels below).  The ops
@@ -221,6 +222,15 @@ void episode_track(int64_t h_, const Tensor& out_buf, const Tensor& ep_buf, OptT
   check(bcn_episode_track(h, o, e, m, stream_of(ep_buf)), "bcn_episode_track");
 }
 
+// ---- per-jet rewards of shkadov (include/beacon_hip.h: bcn_shkadov_jet_rewards; shkadov.py:469-481) ----------------------
+void shkadov_jet_rewards(int64_t h_, const Tensor& out_buf, const Tensor& jets_buf, int64_t with_stats) {
+  bcn_env_t h = H(h_);
+  TORCH_CHECK(h && bcn_env_kind(h) == BCN_SHKADOV, "shkadov_jet_rewards: the handle is not a shkadov env");
+  const uint8_t* o = bytes_of(out_buf, h, out_buf_bytes(h), "out_buf");
+  uint8_t* j = bytes_of(jets_buf, h, (int64_t)bcn_shkadov_jets_bytes(h), "jets_buf");
+  check(bcn_shkadov_jet_rewards(h, o, j, with_stats != 0, stream_of(jets_buf)), "bcn_shkadov_jet_rewards");
+}
+
 // Meta (fake-tensor) kernels: the ops return nothing and their outputs keep their shapes, so tracing needs no more than this.
 void reset2_meta(int64_t, const Tensor&) {}
 void reset3_meta(int64_t, OptT, const Tensor&) {}
@@ -232,6 +242,7 @@ void sloshing_step_meta(int64_t, OptT, const Tensor&, const Tensor&, const Tenso
 void snapshot_save_meta(int64_t, const Tensor&, const Tensor&) {}
 void snapshot_load_meta(int64_t, const Tensor&, int64_t, OptT, OptT, const Tensor&) {}
 void episode_track_meta(int64_t, const Tensor&, const Tensor&, OptT) {}
+void shkadov_jet_rewards_meta(int64_t, const Tensor&, const Tensor&, int64_t) {}
 
 }  // namespace
 
@@ -263,6 +274,7 @@ TORCH_LIBRARY(beacon, m) {
   m.def("snapshot_save(int handle, Tensor(a!) snap, Tensor out_buf) -> ()");
   m.def("snapshot_load(int handle, Tensor snap, int n_src, Tensor? src, Tensor? mask, Tensor(a!) out_buf) -> ()");
   m.def("episode_track(int handle, Tensor out_buf, Tensor(a!) ep_buf, Tensor? mask) -> ()");
+  m.def("shkadov_jet_rewards(int handle, Tensor out_buf, Tensor(a!) jets_buf, int with_stats) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(beacon, CUDA, m) {
@@ -284,6 +296,7 @@ TORCH_LIBRARY_IMPL(beacon, CUDA, m) {
   m.impl("snapshot_save", &snapshot_save);
   m.impl("snapshot_load", &snapshot_load);
   m.impl("episode_track", &episode_track);
+  m.impl("shkadov_jet_rewards", &shkadov_jet_rewards);
 }
 
 TORCH_LIBRARY_IMPL(beacon, Meta, m) {
@@ -305,4 +318,5 @@ TORCH_LIBRARY_IMPL(beacon, Meta, m) {
   m.impl("snapshot_save", &snapshot_save_meta);
   m.impl("snapshot_load", &snapshot_load_meta);
   m.impl("episode_track", &episode_track_meta);
+  m.impl("shkadov_jet_rewards", &shkadov_jet_rewards_meta);
 }

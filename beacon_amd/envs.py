@@ -359,7 +359,8 @@ class sloshing(_Single):
 class shkadov_separable(shkadov):
     """shkadov/shkadov.py:376-481: round-robin per-jet view of shkadov -- the solver advances only
     when the jet counter is 0; every call returns the 10 observations and the reward term of ONE
-    jet.  Host-side re-indexing of the batched kernel's outputs; no new numerics."""
+    jet.  Host-side re-indexing of the batched kernels' outputs (obs, and rwd_jets of VecShkadov.set_jet_rewards): one [n_jets]
+    read per round, no state download; no new numerics."""
 
     def __init__(self, *args, **kw):
         super().__init__(*args, **kw)
@@ -367,13 +368,12 @@ class shkadov_separable(shkadov):
         self.count = 0
         self.act = np.zeros(self.n_jets)
         self._obs_all = np.zeros(self.n_obs * self.n_jets)
+        self._rwd_all = np.zeros(self.n_jets)
         self._blow = False
+        self.vec.set_jet_rewards(True, stats=False)       # the per-jet rewards come from the device (csrc/shkadov_jets.hip)
 
     def _jet_rwd(self, i):
-        h = self.h
-        s = self.jet_pos + i * self.jet_space
-        d = h[s:s + self.l_rwd] - 1.0
-        return -(np.sum(np.square(d)) * self.dx) / (self.n_jets * self.l_rwd)
+        return self._rwd_all[i]                           # shkadov.py:469-481, computed once per round for every jet
 
     def _advance(self):
         if self.count == self.n_jets - 1:
@@ -384,7 +384,11 @@ class shkadov_separable(shkadov):
 
     def reset(self):
         if self.count == 0:
-            self._obs_all, _ = super().reset()
+            self.vec.set_jet_rewards(False)               # the random-start steps of reset() produce no rewards
+            try:
+                self._obs_all, _ = super().reset()
+            finally:
+                self.vec.set_jet_rewards(True, stats=False)
             self._blow = False
             self._stp_shadow = 0
         obs = self._obs_all[self.count * self.n_obs:(self.count + 1) * self.n_obs].copy()
@@ -398,6 +402,7 @@ class shkadov_separable(shkadov):
             self.vec.step(None if u is None else np.asarray(u, dtype=np.float64).reshape(1, -1), self._noise())
             self.vec.set_stp(self._stp_shadow)            # the batched kernel counts solver steps;
             self._obs_all = self._np(self.vec.obs)[0]      # the separable episode counter moves per round
+            self._rwd_all = self._np(self.vec.rwd_jets)[0]
             self._blow = bool(int(self.vec.status[0].item()) & 2)
         obs = self._obs_all[self.count * self.n_obs:(self.count + 1) * self.n_obs].copy()
         rwd = self._jet_rwd(self.count)

@@ -96,7 +96,8 @@ _ODE_OPS = ("lorenz_reset", "lorenz_step", "vortex_reset", "vortex_step")     # 
 _STATE_OPS = ("snapshot_save", "snapshot_load")                               # every env (csrc/snapshot.hip)
 _EPISODE_OPS = ("episode_track",)                                             # every env (csrc/episode.hip)
 _WARM_OPS = ("shkadov_reset_random",)                                         # shkadov (csrc/shkadov_warm_f32.hip, _f64.hip)
-_ALL_OPS = _OPS + _ODE_OPS + _STATE_OPS + _EPISODE_OPS + _WARM_OPS
+_JET_OPS = ("shkadov_jet_rewards",)                                           # shkadov (csrc/shkadov_jets.hip)
+_ALL_OPS = _OPS + _ODE_OPS + _STATE_OPS + _EPISODE_OPS + _WARM_OPS + _JET_OPS
 
 
 def _op_table():
@@ -226,6 +227,61 @@ class EpisodeStats(object):
         return self
 
 
+class JetStats(object):
+    """Per-jet rewards and episode returns of one VecShkadov, kept on the device by the launch that follows every step while
+    VecShkadov.set_jet_rewards is on (csrc/shkadov_jets.hip): `buf`, one uint8 tensor in the layout of bcn_shkadov_jets_layout
+    (include/beacon_hip.h), and typed no-copy views of its segments, all [B, n_jets]:
+      rwd_jets   the reward of every jet after the last step (shkadov_separable.get_rwd, shkadov.py:469-481)
+      ret        the return (env dtype) of every jet in the episode in progress
+      last_ret   that of the replica's last finished episode
+      sum_ret    the sum (float64) of the finished returns
+    Episode lengths and counts are those of EpisodeStats: all jets of a replica share one episode clock.
+    Bookkeeping, like EpisodeStats: not part of a Snapshot or of snapshot_signature(); restore() / fork() leave these where they
+    are -- clear(mask) is the tool after a fork."""
+
+    NAMES = ("rwd_jets", "ret", "last_ret", "sum_ret")
+
+    def __init__(self, env):
+        segs = (_lib.SnapshotSeg * 8)()
+        k = env.lib.bcn_shkadov_jets_layout(env.h, segs, 8)
+        nbytes = env.lib.bcn_shkadov_jets_bytes(env.h)
+        if k != len(self.NAMES) or nbytes == 0:
+            raise _lib.BeaconHipError("libbeacon_hip: %s" % env.lib.bcn_last_error().decode())
+        self.batch, self.n_jets, self.tdtype = env.batch, env.n_jets, env.tdtype
+        self.buf = torch.zeros((nbytes,), dtype=torch.uint8, device=env.device)
+        self.layout = _segments(segs, k)
+        assert tuple(seg["name"] for seg in self.layout) == self.NAMES
+        for seg in self.layout:
+            setattr(self, seg["name"], self.view(seg["name"]))
+
+    def view(self, name):
+        """Typed [B, n_jets] view (no copy) of one segment; KeyError for an unknown name."""
+        return _seg_view(self.buf, self.layout, name, self.batch, self.tdtype)[1].view(self.batch, self.n_jets)
+
+    def clear(self, mask=None):
+        """Zero every segment of the replicas selected by `mask` ([B] bool / uint8 tensor or array; None: all).  No host
+        synchronisation."""
+        if mask is None:
+            self.buf.zero_()
+            return self
+        m = _mask_u8(mask, self.batch, self.buf.device) != 0
+        for name in self.NAMES:
+            getattr(self, name).masked_fill_(m[:, None], 0)
+        return self
+
+    def state_dict(self):
+        """For checkpoints: the buffer on the CPU and what it was laid out for."""
+        return {"buf": self.buf.cpu(), "batch": self.batch, "n_jets": self.n_jets, "dtype": dtype_name(self.tdtype)}
+
+    def load_state_dict(self, d):
+        if (int(d["batch"]), int(d["n_jets"]), _DT[d["dtype"]][0]) != (self.batch, self.n_jets, self.tdtype) or \
+                d["buf"].numel() != self.buf.numel():
+            raise ValueError("JetStats.load_state_dict: statistics of %s replicas x %s jets (%s), this env has %d x %d"
+                             % (d["batch"], d["n_jets"], d["dtype"], self.batch, self.n_jets))
+        self.buf.copy_(d["buf"])
+        return self
+
+
 class ParamsWarning(UserWarning):
     """A 2D env whose default kernel is a register-resident one received per-replica parameters: it steps through the generic
     kernel until clear_params() (VecEnv.set_params).  set_params_kernel("fast") on the env selects the register-resident kernels
@@ -314,7 +370,7 @@ class VecEnv(object):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _call(self, name, *args):
-        """The entry point `name` (one of _OPS, _ODE_OPS, _STATE_OPS, _EPISODE_OPS, _WARM_OPS) through the binding in force: the torch op, or
+        """The entry point `name` (one of _OPS, _ODE_OPS, _STATE_OPS, _EPISODE_OPS, _WARM_OPS, _JET_OPS) through the binding in force: the torch op, or
         bcn_<name> through ctypes.  `args`: what both take between the handle and the stream, in their common order -- tensors
         (None: a null pointer) and ints; the op reads torch's current stream itself, ctypes gets it appended."""
         if self._ops is not None:
@@ -689,15 +745,21 @@ class VecEnv(object):
                 self._apply_mask(None)
         return self.obs, None
 
+    def _after_step(self):
+        """What an env launches directly behind its step kernel in step() / step_autoreset() / capture(), under the same replica
+        mask (VecShkadov.set_jet_rewards).  Nothing by default."""
+
     def step(self, actions=None, noise=None, mask=None):
         if self._rotate:
             self._next_outputs(carry=mask is not None)
         if mask is None and getattr(self, "_mask", None) is None:
             self._step(actions, noise)            # the common case: no mask now, none set -- nothing to tell the library
+            self._after_step()
         else:
             self._apply_mask(mask)
             try:
                 self._step(actions, noise)
+                self._after_step()
             finally:
                 if mask is not None:
                     self._apply_mask(None)
@@ -754,6 +816,7 @@ class VecEnv(object):
             self._apply_mask(mask)
         try:
             self._step(actions, noise)
+            self._after_step()                    # (reads the film: in front of the masked reset)
             self._track(ep, self._mask)
             self._reset_finished(ep)
         finally:
@@ -803,7 +866,7 @@ class VecEnv(object):
 class StepGraph(object):
     """n step() calls (autoreset: step_autoreset() calls) of one VecEnv on static inputs, as a HIP graph (VecEnv.capture).  After replay() the env's own
     obs / rwd / done / trunc hold the last step's results; `obs_seq`, `rwd_seq`, `done_seq`, `trunc_seq` ([n, B, ...])
-    hold every step's."""
+    hold every step's -- and `rwd_jets_seq` ([n, B, n_jets]) for a VecShkadov captured with set_jet_rewards() on."""
 
     def __init__(self, env, actions, noise=None, n_steps=None, keep_steps=True, autoreset=False):
         self.env, self.actions, self.noise, self.autoreset = env, actions, noise, bool(autoreset)
@@ -815,6 +878,9 @@ class StepGraph(object):
         self.rwd_seq = torch.empty((n,) + tuple(env.rwd.shape), dtype=env.rwd.dtype, device=env.device)
         self.done_seq = torch.empty((n,) + tuple(env.done.shape), dtype=env.done.dtype, device=env.device)
         self.trunc_seq = torch.empty((n,) + tuple(env.trunc.shape), dtype=env.trunc.dtype, device=env.device)
+        jets = getattr(env, "_jets", None) if getattr(env, "_jets_on", False) else None      # VecShkadov.set_jet_rewards
+        if jets is not None:
+            self.rwd_jets_seq = torch.empty((n,) + tuple(jets.rwd_jets.shape), dtype=jets.rwd_jets.dtype, device=env.device)
         self.graph = torch.cuda.CUDAGraph()
         gen = getattr(env, "gen", None)
         if gen is not None and noise is None:
@@ -825,6 +891,7 @@ class StepGraph(object):
                 a = actions[k] if seq else actions
                 z = None if noise is None else (noise[k] if seq else noise)
                 env._step(a, z)
+                env._after_step()
                 if autoreset:
                     env._track(ep, None)
                     env._reset_finished(ep)
@@ -835,6 +902,8 @@ class StepGraph(object):
                 self.rwd_seq[k].copy_(env.rwd)
                 self.done_seq[k].copy_(env.done)
                 self.trunc_seq[k].copy_(env.trunc)
+                if jets is not None:
+                    self.rwd_jets_seq[k].copy_(jets.rwd_jets)
 
     def replay(self):
         self.graph.replay()
@@ -1128,6 +1197,9 @@ class VecShkadov(VecEnv):
 
     needs_noise = True
     rand_steps = None        # set_random_init: None = every reset restarts from the film itself
+    _jets = None             # set_jet_rewards: the JetStats, allocated by the first call and kept
+    _jets_on = False         # ... whether the per-jet launch follows every step
+    _jets_stats = 0          # ... and whether it keeps the per-jet returns (the kernel's with_stats)
 
     def __init__(self, batch, device="cuda:0", dtype="f32", init_fields=None, L0=150.0, n_jets=5,
                  jet_pos=150.0, jet_space=10.0, delta=0.1, t_act=20.0, seed=0):
@@ -1200,8 +1272,12 @@ class VecShkadov(VecEnv):
             n_steps = torch.randint(0, rand_steps + 1, (self.batch,), generator=self.gen, device=self.device)
         n_steps = torch.as_tensor(n_steps).to(self.device)
         self.n_rand = n_steps
-        for i in range(int(n_steps.max().item())):
-            self.step(None, None, mask=(n_steps > i))
+        jets_on, self._jets_on = self._jets_on, False          # a reset produces no rewards (set_jet_rewards)
+        try:
+            for i in range(int(n_steps.max().item())):
+                self.step(None, None, mask=(n_steps > i))
+        finally:
+            self._jets_on = jets_on
         self.set_stp(0)
         return self.obs, None
 
@@ -1258,6 +1334,59 @@ class VecShkadov(VecEnv):
         nz = None if noise is None else self._real(noise, (self.batch, self.ndt_act))   # None: drawn inside the kernel
         self._keep = (a, nz)
         self._call("shkadov_step", a, nz, self.obs, self.rwd, self.done, self.trunc, self.status)
+
+    # -- the multi-agent form: every jet an agent (shkadov_separable, shkadov.py:376-481) ------------
+    def set_jet_rewards(self, on=True, stats=True):
+        """Per-jet rewards on the device, for trainers of the reference's multi-agent shkadov (shkadov_separable: every jet an
+        agent with its own 10 observations and its own reward, shkadov.py:469-481).  While on, ONE extra launch
+        (bcn_shkadov_jet_rewards, csrc/shkadov_jets.hip) directly follows the step kernel in step(), in step_autoreset() -- in
+        front of the bookkeeping launch and the masked reset, which overwrites the film -- and in every step a capture()
+        records; it writes
+          rwd_jets [B, n_jets]   -(sum of (h - 1)^2 dx over the l_rwd cells downstream of the jet) / (n_jets l_rwd), or blowup_rwd
+                                 in every jet of a replica whose step reported a blow-up (:441-445); the rows sum to `rwd` up to
+                                 rounding
+        and, with stats=True, keeps `jet_episodes` (JetStats: ret, last_ret, sum_ret, all [B, n_jets]) with the semantics of
+        EpisodeStats, per jet.  A StepGraph captured while on also has rwd_jets_seq [n, B, n_jets] (keep_steps).  No host
+        synchronisation, nothing allocated after the first call; a replica a mask skips keeps its rows; with double_buffer() the
+        launch reads the outputs the step just wrote.  warmup(), reset() and the random-start resets produce no rewards and
+        launch nothing extra.  `obs_jets` is the matching per-jet view of the observations.
+        set_jet_rewards(False) turns it off -- the default, in which step() launches exactly what it always did -- and keeps the
+        buffer.  The setting is recorded into a graph at capture(): re-capture after changing it.
+        rwd_jets and jet_episodes are bookkeeping, like `episodes`: they are in no Snapshot, snapshot_signature() does not
+        change, and restore() / fork() leave them where they are (JetStats.clear(mask) after a fork).  `rwd`, `done` and `trunc`
+        are untouched: all jets of a replica share one episode clock.  ShardedVecEnv does not offer this."""
+        if on and self._jets is None:
+            self._jets = JetStats(self)
+        self._jets_on, self._jets_stats = bool(on), int(bool(stats))
+        return self
+
+    def _jets_or_raise(self, what):
+        if not self._jets_on or self._jets is None:
+            raise AttributeError("%s.%s: per-jet rewards are off -- call set_jet_rewards() first" % (type(self).__name__, what))
+        return self._jets
+
+    @property
+    def rwd_jets(self):
+        """[B, n_jets] rewards of every jet after the last step() (a no-copy view; set_jet_rewards)."""
+        return self._jets_or_raise("rwd_jets").rwd_jets
+
+    @property
+    def jet_episodes(self):
+        """The JetStats of this env (set_jet_rewards(stats=True))."""
+        jets = self._jets_or_raise("jet_episodes")
+        if not self._jets_stats:
+            raise ValueError("%s.jet_episodes: per-jet returns are not kept -- set_jet_rewards(True, stats=True)" % type(self).__name__)
+        return jets
+
+    @property
+    def obs_jets(self):
+        """`obs` regrouped per jet, [B, n_jets, n_obs], without a copy: the row is jet-major (shkadov.py:243-248), so obs_jets[b, j]
+        is what shkadov_separable.get_obs(j) returns (:455-466)."""
+        return self.obs.view(self.batch, self.n_jets, self.n_obs)
+
+    def _after_step(self):
+        if self._jets_on:
+            self._call("shkadov_jet_rewards", self.out_buf, self._jets.buf, self._jets_stats)
 
 
 class VecSloshing(VecEnv):

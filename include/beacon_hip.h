@@ -490,6 +490,33 @@ enum { BCN_SNAP_F64 = 4, BCN_SNAP_I64 = 5 };   /* element types of bcn_episode_l
 BCN_API size_t bcn_episode_bytes(bcn_env_t h);
 BCN_API int bcn_episode_layout(bcn_env_t h, bcn_snapshot_seg* segs, int max_segs);
 BCN_API int bcn_episode_track(bcn_env_t h, const void* out_buf_dev, void* ep_buf_dev, const uint8_t* mask_dev, void* stream);
+/* Per-jet rewards and returns of shkadov: the multi-agent form of the env, shkadov_separable (shkadov.py:376-481), in which every
+ * jet is an agent with its own reward, for all B replicas and without host work.  ONE kernel launch on `stream` behind
+ * bcn_shkadov_step (no host synchronisation, no host read, no allocation, no atomics: it can be captured into a graph, and two runs
+ * agree bit for bit).  The per-jet buffer belongs to the caller (bcn_shkadov_jets_bytes(h) bytes, 16-byte aligned, zeroed before
+ * its first use); its segments, in this order, every start a multiple of 16 bytes, each [B][n_jets]:
+ *   rwd_jets real     the reward of every jet after the step
+ *   ret real          the return of every jet in the episode in progress
+ *   last_ret real     that of the replica's last finished episode
+ *   sum_ret float64   the sum of the finished returns
+ * bcn_shkadov_jets_bytes replaces nothing in the reference (its rewards are host scalars); 0 and bcn_last_error for a NULL or
+ * non-shkadov handle.  bcn_shkadov_jets_layout writes the segments as bcn_snapshot_seg with planes = 1 and row_elems = n_jets, as
+ * bcn_episode_layout does, and returns their number, 4 (only the first max_segs are written; 0 and bcn_last_error on a bad argument).
+ * bcn_shkadov_jet_rewards replaces shkadov_separable.get_rwd (shkadov.py:469-481) and the blow-up rule of shkadov_separable.step
+ * (:441-445).  out_buf_dev is the packed output buffer the step wrote (bcn_snapshot_save: [obs | rwd | status | done | trunc]).
+ * For every replica b that bcn_set_mask leaves on and every jet j, with s = jet_pos + j jet_space:
+ *   rwd_jets[b][j] = -(sum_{c = s .. s + l_rwd - 1, c < nx} (h[b][c] - 1)^2 * dx) / (n_jets l_rwd)
+ *                    or blowup_rwd where status[b] has BCN_ST_BLOWUP (the step's own flag: the film is not scanned again);
+ *   with_stats != 0, fin = done[b] | trunc[b]:
+ *     ret[b][j] += rwd_jets[b][j] (one add in the handle's dtype);
+ *     if fin: last_ret[b][j] = ret[b][j]; sum_ret[b][j] += (double)ret[b][j]; ret[b][j] = 0.
+ *   with_stats == 0 leaves ret, last_ret and sum_ret alone.  A replica the mask switches off keeps its rows of all four.
+ * Episode lengths and counts are those of bcn_episode_track (one episode clock for all jets of a replica).  Call it after the step
+ * and before the reset of the finished replicas, which overwrites the film.  BCN_ERR_ARG, and nothing dereferenced, for a NULL
+ * handle or buffer and for a handle of another env. */
+BCN_API size_t bcn_shkadov_jets_bytes(bcn_env_t h);
+BCN_API int bcn_shkadov_jets_layout(bcn_env_t h, bcn_snapshot_seg* segs, int max_segs);
+BCN_API int bcn_shkadov_jet_rewards(bcn_env_t h, const void* out_buf_dev, void* jets_buf_dev, int with_stats, void* stream);
 /* name of the kernel the last *_step dispatched, e.g. "ns2d_fast_sched" (before the first step: the
  * variant's plain kernel); for profiles */
 BCN_API const char* bcn_kernel_name(bcn_env_t h);
