@@ -140,6 +140,9 @@ SIGNATURES = {
     "bcn_shkadov_jets_bytes": (C.c_size_t, [vp]),
     "bcn_shkadov_jets_layout": (C.c_int, [vp, C.POINTER(SnapshotSeg), C.c_int]),
     "bcn_shkadov_jet_rewards": (C.c_int, [vp, vp, vp, C.c_int, vp]),
+    "bcn_normalize_bytes": (C.c_size_t, [vp]),
+    "bcn_normalize_layout": (C.c_int, [vp, C.POINTER(SnapshotSeg), C.c_int]),
+    "bcn_normalize": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, vp]),
     "bcn_n_params": (C.c_int, [vp]),
     "bcn_param_name": (C.c_char_p, [vp, C.c_int]),
     "bcn_set_params": (C.c_int, [vp, C.POINTER(C.c_double), vp]),

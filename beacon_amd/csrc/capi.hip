@@ -15,6 +15,7 @@
 #include "snapshot.h"
 #include "episode.h"
 #include "shkadov_jets.h"
+#include "normalize.h"
 
 static thread_local char g_err[512] = "";
 
@@ -763,6 +764,38 @@ int episode_build(bcn_env_t h, bcn_snapshot_seg* lay, size_t* bytes) {
   return BCN_EP_NSEG;
 }
 
+// Lays out the normaliser buffer of this handle's batch (normalize.h): the eleven segments into `lay` (room for BCN_NRM_NSEG) and / or
+// the bytes it takes.  Only batch, observation length and dtype of the handle are used.  A segment that does not scale with the
+// batch has planes = 0 and row_elems = its length in elements.
+int normalize_build(bcn_env_t h, bcn_snapshot_seg* lay, size_t* bytes) {
+  const size_t B = (size_t)h->batch, esz = h->esz, n = (size_t)h->n_obs;
+  if (h->batch < 1 || h->n_obs < 1 || B * n > 0x7fffffffull) {
+    bcn_set_error("normalize: batch %d x %d observations is outside what one launch covers", h->batch, h->n_obs);
+    return -1;
+  }
+  const NormalizeShape sh = normalize_shape(B, n);
+  const size_t scratch = ((2 * (n + 1) + 2) + (size_t)sh.G * (n + 1) * 3) * 8;
+  // name, element type, planes (0: not per replica), row_elems, bytes
+  const struct { const char* name; int elem; int planes; int64_t row_elems; size_t nbytes; } d[BCN_NRM_NSEG] = {
+      {"obs_mean", BCN_SNAP_F64, 0, (int64_t)n, n * 8}, {"obs_var", BCN_SNAP_F64, 0, (int64_t)n, n * 8}, {"obs_count", BCN_SNAP_F64, 0, 1, 8},
+      {"ret_mean", BCN_SNAP_F64, 0, 1, 8},              {"ret_var", BCN_SNAP_F64, 0, 1, 8},              {"ret_count", BCN_SNAP_F64, 0, 1, 8},
+      {"ret", BCN_SNAP_F64, 1, 1, B * 8},               {"norm_obs", BCN_SNAP_REAL, 1, (int64_t)n, B * n * esz},
+      {"norm_rwd", BCN_SNAP_REAL, 1, 1, B * esz},       {"norm_final_obs", BCN_SNAP_REAL, 1, (int64_t)n, B * n * esz},
+      {"scratch", BCN_SNAP_U8, 0, (int64_t)scratch, scratch}};
+  size_t off = 0;
+  for (int k = 0; k < BCN_NRM_NSEG; k++) {
+    off = snap_up16(off);
+    if (lay) {
+      memset(&lay[k], 0, sizeof(lay[k]));
+      strncpy(lay[k].name, d[k].name, sizeof(lay[k].name) - 1);
+      lay[k].offset = off; lay[k].elem = d[k].elem; lay[k].planes = d[k].planes; lay[k].row_elems = d[k].row_elems;
+    }
+    off += d[k].nbytes;
+  }
+  if (bytes) *bytes = snap_up16(off);
+  return BCN_NRM_NSEG;
+}
+
 // Lays out the per-jet buffer of a shkadov handle (shkadov_jets.h): the four [B][n_jets] segments into `lay` (room for
 // BCN_JETS_NSEG) and / or the bytes it takes.  Only batch, jet count (the action length) and dtype of the handle are used.
 int jets_build(bcn_env_t h, bcn_snapshot_seg* lay, size_t* bytes) {
@@ -1253,6 +1286,64 @@ int bcn_shkadov_jet_rewards(bcn_env_t h, const void* out_buf_dev, void* jets_buf
   bcn_snapshot_seg lay[BCN_JETS_NSEG];
   if (jets_build(h, lay, nullptr) < 0) return BCN_ERR_ARG;
   return BCN_BY_DTYPE(h->dtype, shkadov_jets_t, h, static_cast<const char*>(out_buf_dev), static_cast<char*>(jets_buf_dev), lay, with_stats, stream);
+}
+// ---- running normalisation of observations and rewards (normalize.h) ------------------------------
+size_t bcn_normalize_bytes(bcn_env_t h) {
+  size_t bytes = 0;
+  if (!h) { bcn_set_error("bcn_normalize_bytes: null handle"); return 0; }
+  if (normalize_build(h, nullptr, &bytes) < 0) return 0;    // (normalize_build has set the message)
+  return bytes;
+}
+int bcn_normalize_layout(bcn_env_t h, bcn_snapshot_seg* segs, int max_segs) {
+  if (!h || (max_segs > 0 && !segs)) { bcn_set_error("bcn_normalize_layout: null handle/array"); return 0; }
+  bcn_snapshot_seg lay[BCN_NRM_NSEG];
+  const int nd = normalize_build(h, lay, nullptr);
+  for (int k = 0; k < nd && k < max_segs; k++) segs[k] = lay[k];
+  return nd < 0 ? 0 : nd;
+}
+int bcn_normalize(bcn_env_t h, const void* out_buf_dev, void* norm_buf_dev, const void* ep_buf_dev, const uint8_t* mask_dev, int kind,
+                  int training, double gamma, double eps, double clip_obs, double clip_rwd, void* stream) {
+  if (!h || !out_buf_dev || !norm_buf_dev) { bcn_set_error("bcn_normalize: null handle/buffer"); return BCN_ERR_ARG; }
+  if (!snap_ptr_ok(out_buf_dev) || !snap_ptr_ok(norm_buf_dev) || !snap_ptr_ok(ep_buf_dev)) {
+    bcn_set_error("bcn_normalize: buffers must be 16-byte aligned");
+    return BCN_ERR_ARG;
+  }
+  if (kind != BCN_NORM_STEP && kind != BCN_NORM_RESET) { bcn_set_error("bcn_normalize: kind %d is neither BCN_NORM_STEP nor BCN_NORM_RESET", kind); return BCN_ERR_ARG; }
+  if (!(gamma >= 0.0 && gamma <= 1.0) || !(eps > 0.0) || !(clip_obs > 0.0) || !(clip_rwd > 0.0)) {
+    bcn_set_error("bcn_normalize: gamma %g must lie in [0, 1], eps %g, clip_obs %g and clip_rwd %g must be > 0", gamma, eps, clip_obs, clip_rwd);
+    return BCN_ERR_ARG;
+  }
+  bcn_snapshot_seg lay[BCN_NRM_NSEG], el[BCN_EP_NSEG];
+  if (normalize_build(h, lay, nullptr) < 0) return BCN_ERR_ARG;
+  if (ep_buf_dev && episode_build(h, el, nullptr) < 0) return BCN_ERR_ARG;
+  const size_t B = (size_t)h->batch, n = (size_t)h->n_obs;
+  const bcn_out_layout_t o = bcn_out_layout(B, n, h->esz);
+  const NormalizeShape sh = normalize_shape(B, n);
+  const char* out = static_cast<const char*>(out_buf_dev);
+  const char* ep = static_cast<const char*>(ep_buf_dev);
+  char* nb = static_cast<char*>(norm_buf_dev);
+  NormalizeArgs a;
+  a.obs = out + o.obs; a.rwd = out + o.rwd;
+  a.status = reinterpret_cast<const int32_t*>(out + o.status);
+  a.done = reinterpret_cast<const uint8_t*>(out + o.done); a.trunc = reinterpret_cast<const uint8_t*>(out + o.trunc);
+  a.mask = mask_dev;
+  a.finished = ep ? reinterpret_cast<const uint8_t*>(ep + el[7].offset) : nullptr;
+  a.final_obs = ep ? ep + el[8].offset : nullptr;
+  a.obs_mean = reinterpret_cast<double*>(nb + lay[0].offset); a.obs_var = reinterpret_cast<double*>(nb + lay[1].offset);
+  a.obs_count = reinterpret_cast<double*>(nb + lay[2].offset); a.ret_mean = reinterpret_cast<double*>(nb + lay[3].offset);
+  a.ret_var = reinterpret_cast<double*>(nb + lay[4].offset); a.ret_count = reinterpret_cast<double*>(nb + lay[5].offset);
+  a.ret = reinterpret_cast<double*>(nb + lay[6].offset);
+  a.norm_obs = nb + lay[7].offset; a.norm_rwd = nb + lay[8].offset; a.norm_final_obs = nb + lay[9].offset;
+  a.prev = reinterpret_cast<double*>(nb + lay[10].offset);
+  a.part = a.prev + 2 * (n + 1) + 2;
+  a.batch = (unsigned)B; a.n_obs = (unsigned)n;
+  a.w = sh.w; a.R = sh.R; a.chunks = sh.chunks; a.S = sh.S; a.G = sh.G;
+  a.f64 = h->dtype == BCN_F64;
+  a.kind = kind == BCN_NORM_RESET ? BCN_NRM_RESET : BCN_NRM_STEP;
+  a.training = training != 0;
+  a.gamma = gamma; a.eps = eps; a.clip_obs = clip_obs; a.clip_rwd = clip_rwd;
+  DeviceGuard g(h->device);
+  return normalize_launch(a, static_cast<hipStream_t>(stream));
 }
 const char* bcn_kernel_name(bcn_env_t h) { return h ? h->kernel_name() : ""; }
 int bcn_kernel_shape(bcn_env_t h, int* cells_per_thread, int* threads) {

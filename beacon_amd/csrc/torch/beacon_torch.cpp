@@ -4,6 +4,8 @@
 //   beacon::snapshot_{save,load}(int handle, Tensor ...) -> ()
 //   beacon::episode_track(int handle, Tensor out_buf, Tensor ep_buf, Tensor? mask) -> ()
 //   beacon::shkadov_jet_rewards(int handle, Tensor out_buf, Tensor jets_buf, int with_stats) -> ()
+//   beacon::normalize(int handle, Tensor out_buf, Tensor norm_buf, Tensor? ep_buf, Tensor? mask, int kind, int training, float gamma, float eps,
+//                     float clip_obs, float clip_rwd) -> ()
 // Each op is ONE dispatcher call that takes device tensors, reads torch's current HIP stream in C++ and forwards to the
 // bcn_* entry point of libbeacon_hip.so -- no ctypes marshalling, no Python-side stream query (what the per-call host cost of
 // the ctypes binding was made of: scripts/host_cost.py), and an op CUDA-graph capture and fake-tensor tracing can see (Meta kernels below).  The ops
@@ -231,6 +233,18 @@ void shkadov_jet_rewards(int64_t h_, const Tensor& out_buf, const Tensor& jets_b
   check(bcn_shkadov_jet_rewards(h, o, j, with_stats != 0, stream_of(jets_buf)), "bcn_shkadov_jet_rewards");
 }
 
+// ---- running normalisation of observations and rewards (include/beacon_hip.h: bcn_normalize) ----------------------------
+void normalize(int64_t h_, const Tensor& out_buf, const Tensor& norm_buf, OptT ep_buf, OptT mask, int64_t kind, int64_t training, double gamma,
+               double eps, double clip_obs, double clip_rwd) {
+  bcn_env_t h = H(h_);
+  const uint8_t* o = bytes_of(out_buf, h, out_buf_bytes(h), "out_buf");
+  uint8_t* n = bytes_of(norm_buf, h, (int64_t)bcn_normalize_bytes(h), "norm_buf");
+  const uint8_t* e = ep_buf.has_value() ? bytes_of(*ep_buf, h, (int64_t)bcn_episode_bytes(h), "ep_buf") : nullptr;
+  const uint8_t* m = mask.has_value() ? u8(*mask, h, 1, "mask") : nullptr;
+  TORCH_CHECK(kind == BCN_NORM_STEP || kind == BCN_NORM_RESET, "kind: ", kind, " is neither BCN_NORM_STEP nor BCN_NORM_RESET");
+  check(bcn_normalize(h, o, n, e, m, (int)kind, training != 0, gamma, eps, clip_obs, clip_rwd, stream_of(norm_buf)), "bcn_normalize");
+}
+
 // Meta (fake-tensor) kernels: the ops return nothing and their outputs keep their shapes, so tracing needs no more than this.
 void reset2_meta(int64_t, const Tensor&) {}
 void reset3_meta(int64_t, OptT, const Tensor&) {}
@@ -243,6 +257,7 @@ void snapshot_save_meta(int64_t, const Tensor&, const Tensor&) {}
 void snapshot_load_meta(int64_t, const Tensor&, int64_t, OptT, OptT, const Tensor&) {}
 void episode_track_meta(int64_t, const Tensor&, const Tensor&, OptT) {}
 void shkadov_jet_rewards_meta(int64_t, const Tensor&, const Tensor&, int64_t) {}
+void normalize_meta(int64_t, const Tensor&, const Tensor&, OptT, OptT, int64_t, int64_t, double, double, double, double) {}
 
 }  // namespace
 
@@ -275,6 +290,8 @@ TORCH_LIBRARY(beacon, m) {
   m.def("snapshot_load(int handle, Tensor snap, int n_src, Tensor? src, Tensor? mask, Tensor(a!) out_buf) -> ()");
   m.def("episode_track(int handle, Tensor out_buf, Tensor(a!) ep_buf, Tensor? mask) -> ()");
   m.def("shkadov_jet_rewards(int handle, Tensor out_buf, Tensor(a!) jets_buf, int with_stats) -> ()");
+  m.def("normalize(int handle, Tensor out_buf, Tensor(a!) norm_buf, Tensor? ep_buf, Tensor? mask, int kind, int training, float gamma, "
+        "float eps, float clip_obs, float clip_rwd) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(beacon, CUDA, m) {
@@ -297,6 +314,7 @@ TORCH_LIBRARY_IMPL(beacon, CUDA, m) {
   m.impl("snapshot_load", &snapshot_load);
   m.impl("episode_track", &episode_track);
   m.impl("shkadov_jet_rewards", &shkadov_jet_rewards);
+  m.impl("normalize", &normalize);
 }
 
 TORCH_LIBRARY_IMPL(beacon, Meta, m) {
@@ -319,4 +337,5 @@ TORCH_LIBRARY_IMPL(beacon, Meta, m) {
   m.impl("snapshot_load", &snapshot_load_meta);
   m.impl("episode_track", &episode_track_meta);
   m.impl("shkadov_jet_rewards", &shkadov_jet_rewards_meta);
+  m.impl("normalize", &normalize_meta);
 }

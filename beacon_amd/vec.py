@@ -98,18 +98,19 @@ _EPISODE_OPS = ("episode_track",)                                             # 
 _WARM_OPS = ("shkadov_reset_random",)                                         # shkadov (csrc/shkadov_warm_f32.hip, _f64.hip)
 _JET_OPS = ("shkadov_jet_rewards",)                                           # shkadov (csrc/shkadov_jets.hip)
 _ALL_OPS = _OPS + _ODE_OPS + _STATE_OPS + _EPISODE_OPS + _WARM_OPS + _JET_OPS
+_NORM_OPS = ("normalize",)                                                    # every env (csrc/normalize.hip)
 
 
 def _op_table():
     """{name: torch.ops.beacon.<name>.default} of the torch extension (beacon_amd/torch_ext.py), or None without it."""
     from . import torch_ext
     ops = torch_ext.load()
-    return None if ops is None else {n: getattr(ops, n).default for n in _ALL_OPS}
+    return None if ops is None else {n: getattr(ops, n).default for n in _ALL_OPS + _NORM_OPS}
 
 
 def _c_table(lib):
     """{name: bcn_<name> of libbeacon_hip.so}: the same entry points through ctypes, resolved once per env."""
-    return {n: getattr(lib, "bcn_" + n) for n in _ALL_OPS}
+    return {n: getattr(lib, "bcn_" + n) for n in _ALL_OPS + _NORM_OPS}
 
 
 class Snapshot(object):
@@ -282,6 +283,81 @@ class JetStats(object):
         return self
 
 
+class Normalizer(object):
+    """Running normalisation of the observations and rewards of one VecEnv, kept on the device by the launches that follow every
+    reset and step while VecEnv.set_normalize is on (csrc/normalize.hip; what the VecNormalize wrapper of the RL libraries
+    computes): `buf`, one uint8 tensor in the layout of bcn_normalize_layout (include/beacon_hip.h), and typed no-copy views of
+    its segments:
+      obs_mean, obs_var [obs_dim], obs_count [1]   float64: running mean, population variance and sample count of every column
+      ret_mean, ret_var, ret_count [1]             float64: those of the discounted return
+      ret [B]                                      float64: the discounted return of every replica
+      norm_obs [B, obs_dim], norm_rwd [B]          env dtype: what reset() / step() return while the feature is on
+      norm_final_obs [B, obs_dim]                  env dtype: the normalised terminal observations of step_autoreset()
+    (`scratch` is private to the kernels.)  `training` (bool): False freezes the statistics -- evaluation -- and only the three
+    outputs are written.  gamma, eps, clip_obs, clip_rwd: the arguments of the launch, set by VecEnv.set_normalize.
+    Bookkeeping, like EpisodeStats: not part of a Snapshot or of snapshot_signature(); restore() / fork() leave the normaliser
+    where it is.  state_dict() / load_state_dict() are for checkpoints and for evaluation with the statistics of a training run."""
+
+    NAMES = ("obs_mean", "obs_var", "obs_count", "ret_mean", "ret_var", "ret_count", "ret", "norm_obs", "norm_rwd", "norm_final_obs",
+             "scratch")
+    KINDS = {"step": 0, "reset": 1}              # include/beacon_hip.h: BCN_NORM_STEP, BCN_NORM_RESET
+
+    def __init__(self, env, gamma=0.99, eps=1e-8, clip_obs=10.0, clip_rwd=10.0, training=True):
+        segs = (_lib.SnapshotSeg * 16)()
+        k = env.lib.bcn_normalize_layout(env.h, segs, 16)
+        nbytes = env.lib.bcn_normalize_bytes(env.h)
+        if k != len(self.NAMES) or nbytes == 0:
+            raise _lib.BeaconHipError("libbeacon_hip: %s" % env.lib.bcn_last_error().decode())
+        self.batch, self.obs_dim, self.tdtype = env.batch, env.obs_dim, env.tdtype
+        self.gamma, self.eps, self.clip_obs, self.clip_rwd = float(gamma), float(eps), float(clip_obs), float(clip_rwd)
+        self.training = bool(training)
+        self.buf = torch.zeros((nbytes,), dtype=torch.uint8, device=env.device)
+        self.layout = _segments(segs, k)
+        assert tuple(seg["name"] for seg in self.layout) == self.NAMES
+        for seg in self.layout:
+            setattr(self, seg["name"], self.view(seg["name"]))
+        self.clear()
+
+    def view(self, name):
+        """Typed view (no copy) of one segment; KeyError for an unknown name.  A segment with planes = 0 does not scale with the
+        batch: row_elems is its length."""
+        for seg in self.layout:
+            if seg["name"] == name:
+                break
+        else:
+            raise KeyError(name)
+        if seg["planes"] == 0:
+            dt = _SEG_ELEM.get(seg["elem"], self.tdtype)
+            nbytes = seg["row_elems"] * torch.empty((), dtype=dt).element_size()
+            return self.buf[seg["offset"]:seg["offset"] + nbytes].view(dt)
+        v = _seg_view(self.buf, self.layout, name, self.batch, self.tdtype)[1]
+        return v.view(self.batch, seg["row_elems"]) if seg["row_elems"] > 1 else v
+
+    def clear(self):
+        """Back to the initial state: counts 0, means 0, variances 1, returns 0 (and the outputs zeroed).  No host
+        synchronisation."""
+        self.buf.zero_()
+        self.obs_var.fill_(1.0)
+        self.ret_var.fill_(1.0)
+        return self
+
+    def state_dict(self):
+        """For checkpoints: the buffer on the CPU, what it was laid out for and the arguments of the launch."""
+        return {"buf": self.buf.cpu(), "batch": self.batch, "obs_dim": self.obs_dim, "dtype": dtype_name(self.tdtype),
+                "gamma": self.gamma, "eps": self.eps, "clip_obs": self.clip_obs, "clip_rwd": self.clip_rwd}
+
+    def load_state_dict(self, d):
+        if (int(d["batch"]), int(d["obs_dim"]), _DT[d["dtype"]][0]) != (self.batch, self.obs_dim, self.tdtype) or \
+                d["buf"].numel() != self.buf.numel():
+            raise ValueError("Normalizer.load_state_dict: statistics of %s replicas x %s observations (%s), this env has %d x %d"
+                             % (d["batch"], d["obs_dim"], d["dtype"], self.batch, self.obs_dim))
+        self.buf.copy_(d["buf"])
+        for name in ("gamma", "eps", "clip_obs", "clip_rwd"):
+            if name in d:
+                setattr(self, name, float(d[name]))
+        return self
+
+
 class ParamsWarning(UserWarning):
     """A 2D env whose default kernel is a register-resident one received per-replica parameters: it steps through the generic
     kernel until clear_params() (VecEnv.set_params).  set_params_kernel("fast") on the env selects the register-resident kernels
@@ -296,6 +372,8 @@ class VecEnv(object):
     needs_noise = False
     _plugin_defs = None      # extra -D flags of this class's on-demand kernels (tests: the deliberately broken plugin)
     _plugin_prm_defs = None  # ... of their table-reading twins alone (set_params_kernel), on top of _plugin_defs
+    _norm = None             # set_normalize: the Normalizer, allocated by the first call and kept
+    _norm_on = False         # ... whether the normalising launches follow every reset and step
 
     def __init__(self, batch, device="cuda:0", dtype="f32"):
         if not torch.cuda.is_available():
@@ -370,12 +448,12 @@ class VecEnv(object):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _call(self, name, *args):
-        """The entry point `name` (one of _OPS, _ODE_OPS, _STATE_OPS, _EPISODE_OPS, _WARM_OPS, _JET_OPS) through the binding in force: the torch op, or
+        """The entry point `name` (one of _OPS, _ODE_OPS, _STATE_OPS, _EPISODE_OPS, _WARM_OPS, _JET_OPS, _NORM_OPS) through the binding in force: the torch op, or
         bcn_<name> through ctypes.  `args`: what both take between the handle and the stream, in their common order -- tensors
-        (None: a null pointer) and ints; the op reads torch's current stream itself, ctypes gets it appended."""
+        (None: a null pointer), ints and floats; the op reads torch's current stream itself, ctypes gets it appended."""
         if self._ops is not None:
             return self._ops[name](self.h.value, *args)
-        _lib.check(self._cfn[name](self.h, *[a if a is None or isinstance(a, int) else C.c_void_p(a.data_ptr()) for a in args],
+        _lib.check(self._cfn[name](self.h, *[a if a is None or isinstance(a, (int, float)) else C.c_void_p(a.data_ptr()) for a in args],
                                    self._stream()))
 
     def _int_actions(self, actions):
@@ -740,10 +818,12 @@ class VecEnv(object):
         self._apply_mask(mask)
         try:
             self._reset()
+            if self._norm_on:
+                self._normalize("reset", self._mask)
         finally:
             if mask is not None:
                 self._apply_mask(None)
-        return self.obs, None
+        return (self._norm.norm_obs if self._norm_on else self.obs), None
 
     def _after_step(self):
         """What an env launches directly behind its step kernel in step() / step_autoreset() / capture(), under the same replica
@@ -755,14 +835,20 @@ class VecEnv(object):
         if mask is None and getattr(self, "_mask", None) is None:
             self._step(actions, noise)            # the common case: no mask now, none set -- nothing to tell the library
             self._after_step()
+            if self._norm_on:
+                self._normalize("step", None)
         else:
             self._apply_mask(mask)
             try:
                 self._step(actions, noise)
                 self._after_step()
+                if self._norm_on:
+                    self._normalize("step", self._mask)
             finally:
                 if mask is not None:
                     self._apply_mask(None)
+        if self._norm_on:
+            return self._norm.norm_obs, self._norm.norm_rwd, self.done, self.trunc, None
         return self.obs, self.rwd, self.done, self.trunc, None
 
     # -- episodes ---------------------------------------------------------------------------
@@ -815,14 +901,79 @@ class VecEnv(object):
         if mask is not None or self._mask is not None:
             self._apply_mask(mask)
         try:
+            stepped = self._mask
             self._step(actions, noise)
             self._after_step()                    # (reads the film: in front of the masked reset)
-            self._track(ep, self._mask)
+            self._track(ep, stepped)
             self._reset_finished(ep)
+            if self._norm_on:                     # last: counts the reset rows of obs, normalises ep.final_obs without counting it
+                self._normalize("step", stepped, ep)
         finally:
             if self._mask is not None:
                 self._apply_mask(None)
+        if self._norm_on:
+            return self._norm.norm_obs, self._norm.norm_rwd, self.done, self.trunc, ep
         return self.obs, self.rwd, self.done, self.trunc, ep
+
+    # -- running normalisation --------------------------------------------------------------
+    def set_normalize(self, on=True, gamma=0.99, eps=1e-8, clip_obs=10.0, clip_rwd=10.0, training=True):
+        """Running normalisation of observations and rewards on the device (the VecNormalize wrapper of the RL libraries; Normalizer,
+        csrc/normalize.hip).  While on, reset(), reset_done(), step(), step_autoreset() and every step a capture() records
+        (autoreset=True included) enqueue bcn_normalize LAST -- in step_autoreset() behind the masked reset -- and return
+        `normalizer.norm_obs` and `normalizer.norm_rwd` in place of obs and rwd: two small launches, one with training=False; no
+        host synchronisation, nothing allocated after the first call.  Per call, over the replicas S that were stepped (or reset)
+        and whose status holds neither BCN_ST_ITMAX nor BCN_ST_BLOWUP (a reset ignores the status):
+          observations  the batch mean and the sum of squared deviations of every column over S are merged into obs_mean / obs_var /
+                        obs_count; norm_obs = clip((obs - obs_mean) / sqrt(obs_var + eps), +-clip_obs) with the merged statistics
+          rewards       ret = gamma ret + rwd; ret_mean / ret_var / ret_count merged from ret over S; norm_rwd = clip(rwd /
+                        sqrt(ret_var + eps), +-clip_rwd); ret = 0 where done | trunc.  A reset zeroes ret of the replicas it touches
+          step_autoreset  the reset rows of obs are what is counted; the terminal rows, info.final_obs, are normalised into
+                        normalizer.norm_final_obs (where info.finished) with the same statistics and not counted
+        all in float64, rounded once to the env dtype.  training=False (evaluation) applies the statistics and changes none;
+        `normalizer.training` can be flipped at any time.  A replica a mask skips keeps its rows and its ret.  A StepGraph
+        captured while on also has norm_obs_seq / norm_rwd_seq (keep_steps); the settings are recorded at capture().
+        obs, rwd, done, trunc, status and the env's state are untouched: they are bit for bit those of an env without the
+        feature.  set_normalize(False) -- the default, in which every call launches exactly what it always did -- keeps the
+        Normalizer and its statistics.
+        The normaliser is bookkeeping, like `episodes`: it is in no Snapshot, snapshot_signature() does not change, restore() /
+        fork() leave it where it is; Normalizer.state_dict() / load_state_dict() carry it to a checkpoint or an evaluation env.
+        ShardedVecEnv does not offer this (each rank would hold its own statistics), the single-env mirrors neither."""
+        if on:
+            if not (0.0 <= float(gamma) <= 1.0) or not float(eps) > 0.0 or not float(clip_obs) > 0.0 or not float(clip_rwd) > 0.0:
+                raise ValueError("%s.set_normalize: gamma must lie in [0, 1], eps, clip_obs and clip_rwd must be > 0"
+                                 % type(self).__name__)
+            if self._norm is None:
+                self._norm = Normalizer(self)
+            nz = self._norm
+            nz.gamma, nz.eps, nz.clip_obs, nz.clip_rwd, nz.training = float(gamma), float(eps), float(clip_obs), float(clip_rwd), bool(training)
+        self._norm_on = bool(on)
+        return self
+
+    @property
+    def normalizer(self):
+        """The Normalizer of this env (set_normalize)."""
+        if not self._norm_on or self._norm is None:
+            raise AttributeError("%s.normalizer: normalisation is off -- call set_normalize() first" % type(self).__name__)
+        return self._norm
+
+    def _normalize(self, kind, mask, ep=None):
+        nz = self._norm
+        self._call("normalize", self.out_buf, nz.buf, None if ep is None else ep.buf, mask, Normalizer.KINDS[kind], int(nz.training),
+                   nz.gamma, nz.eps, nz.clip_obs, nz.clip_rwd)
+
+    def normalize_outputs(self, mask=None, kind="step", episodes=None):
+        """The normalising launch alone, the counterpart of track_episodes(): for callers who sequence things by hand.  Updates
+        `normalizer` from the current outputs (obs, rwd, status, done, trunc).  `mask`: the mask the step or reset was given;
+        kind: "step" or "reset"; episodes: an EpisodeStats whose final_obs rows are normalised where `finished` (what
+        step_autoreset() passes).  Needs set_normalize().  Returns the Normalizer."""
+        nz = self.normalizer
+        if kind not in Normalizer.KINDS:
+            raise ValueError("%s.normalize_outputs: kind %r; \"step\" or \"reset\"" % (type(self).__name__, kind))
+        if mask is not None:
+            mask = _mask_u8(mask, self.batch, self.device)
+        self._keep_norm = mask            # alive behind the asynchronous launch
+        self._normalize(kind, mask, episodes)
+        return nz
 
     def capture(self, actions, noise=None, n_steps=None, keep_steps=True, autoreset=False):
         """Record step() calls into ONE HIP graph (torch.cuda.CUDAGraph) and return it as a StepGraph: replay()
@@ -866,7 +1017,8 @@ class VecEnv(object):
 class StepGraph(object):
     """n step() calls (autoreset: step_autoreset() calls) of one VecEnv on static inputs, as a HIP graph (VecEnv.capture).  After replay() the env's own
     obs / rwd / done / trunc hold the last step's results; `obs_seq`, `rwd_seq`, `done_seq`, `trunc_seq` ([n, B, ...])
-    hold every step's -- and `rwd_jets_seq` ([n, B, n_jets]) for a VecShkadov captured with set_jet_rewards() on."""
+    hold every step's -- and `rwd_jets_seq` ([n, B, n_jets]) for a VecShkadov captured with set_jet_rewards() on, `norm_obs_seq` /
+    `norm_rwd_seq` (the shapes of obs_seq / rwd_seq) for an env captured with set_normalize() on."""
 
     def __init__(self, env, actions, noise=None, n_steps=None, keep_steps=True, autoreset=False):
         self.env, self.actions, self.noise, self.autoreset = env, actions, noise, bool(autoreset)
@@ -881,6 +1033,10 @@ class StepGraph(object):
         jets = getattr(env, "_jets", None) if getattr(env, "_jets_on", False) else None      # VecShkadov.set_jet_rewards
         if jets is not None:
             self.rwd_jets_seq = torch.empty((n,) + tuple(jets.rwd_jets.shape), dtype=jets.rwd_jets.dtype, device=env.device)
+        norm = env._norm if env._norm_on else None                                            # VecEnv.set_normalize
+        if norm is not None:
+            self.norm_obs_seq = torch.empty_like(self.obs_seq)
+            self.norm_rwd_seq = torch.empty_like(self.rwd_seq)
         self.graph = torch.cuda.CUDAGraph()
         gen = getattr(env, "gen", None)
         if gen is not None and noise is None:
@@ -896,6 +1052,8 @@ class StepGraph(object):
                     env._track(ep, None)
                     env._reset_finished(ep)
                     env._apply_mask(None)
+                if norm is not None:
+                    env._normalize("step", None, ep)
                 if not keep_steps:
                     continue
                 self.obs_seq[k].copy_(env.obs)
@@ -904,6 +1062,9 @@ class StepGraph(object):
                 self.trunc_seq[k].copy_(env.trunc)
                 if jets is not None:
                     self.rwd_jets_seq[k].copy_(jets.rwd_jets)
+                if norm is not None:
+                    self.norm_obs_seq[k].copy_(norm.norm_obs)
+                    self.norm_rwd_seq[k].copy_(norm.norm_rwd)
 
     def replay(self):
         self.graph.replay()
@@ -1267,18 +1428,22 @@ class VecShkadov(VecEnv):
         torch generator `gen`); it cannot be captured and cannot restart only the replicas that finished.  set_random_init()
         makes every reset -- reset(mask), reset_done(), step_autoreset(), capture(..., autoreset=True) -- do the same thing in
         one kernel launch on the device."""
-        self.reset()
-        if n_steps is None:
-            n_steps = torch.randint(0, rand_steps + 1, (self.batch,), generator=self.gen, device=self.device)
-        n_steps = torch.as_tensor(n_steps).to(self.device)
-        self.n_rand = n_steps
         jets_on, self._jets_on = self._jets_on, False          # a reset produces no rewards (set_jet_rewards)
+        norm_on, self._norm_on = self._norm_on, False          # ... and is normalised once, at its end (set_normalize)
         try:
+            self.reset()
+            if n_steps is None:
+                n_steps = torch.randint(0, rand_steps + 1, (self.batch,), generator=self.gen, device=self.device)
+            n_steps = torch.as_tensor(n_steps).to(self.device)
+            self.n_rand = n_steps
             for i in range(int(n_steps.max().item())):
                 self.step(None, None, mask=(n_steps > i))
         finally:
-            self._jets_on = jets_on
+            self._jets_on, self._norm_on = jets_on, norm_on
         self.set_stp(0)
+        if norm_on:
+            self._normalize("reset", None)
+            return self._norm.norm_obs, None
         return self.obs, None
 
     def set_random_init(self, rand_steps=400):

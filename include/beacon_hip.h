@@ -517,6 +517,41 @@ BCN_API int bcn_episode_track(bcn_env_t h, const void* out_buf_dev, void* ep_buf
 BCN_API size_t bcn_shkadov_jets_bytes(bcn_env_t h);
 BCN_API int bcn_shkadov_jets_layout(bcn_env_t h, bcn_snapshot_seg* segs, int max_segs);
 BCN_API int bcn_shkadov_jet_rewards(bcn_env_t h, const void* out_buf_dev, void* jets_buf_dev, int with_stats, void* stream);
+/* Running normalisation of observations and rewards over the batch (what the VecNormalize wrapper of the common RL libraries
+ * computes with a dozen tensor operations per step; the reference has no counterpart), on the device, behind a step or a reset:
+ * at most TWO kernel launches on `stream`, ONE with training == 0 -- no host synchronisation, no host read, no allocation, no
+ * atomics: it can be captured into a graph, and the same buffer and inputs give the same bits every time.  The normaliser buffer
+ * belongs to the caller (bcn_normalize_bytes(h) bytes, 16-byte aligned, zeroed before its first use and then obs_var and ret_var
+ * set to 1); its segments, in this order, every start a multiple of 16 bytes:
+ *   obs_mean, obs_var float64 [n_obs]; obs_count float64 [1]       running mean, population variance and sample count per column
+ *   ret_mean, ret_var, ret_count float64 [1]                       those of the discounted return
+ *   ret float64 [B]                                                the discounted return of every replica
+ *   norm_obs real [B][n_obs], norm_rwd real [B], norm_final_obs real [B][n_obs]   the outputs, in the handle's dtype
+ *   scratch uint8                                                  private to the kernels; its contents mean nothing to a caller
+ * bcn_normalize_layout writes them as bcn_snapshot_seg and returns their number, 11 (only the first max_segs are written; 0 and
+ * bcn_last_error on a bad argument).  A segment that scales with the batch has planes = 1, as in bcn_episode_layout: B rows of
+ * row_elems elements.  One that does NOT scale with the batch has planes = 0, and row_elems is the number of its elements.
+ * bcn_normalize: out_buf_dev is the packed output buffer [obs | rwd | status | done | trunc] a step or reset wrote; ep_buf_dev
+ * (NULL: none) the episode buffer of bcn_episode_track, of which `finished` and `final_obs` are read; mask_dev uint8[B] (NULL: all;
+ * the mask of bcn_set_mask plays no part).  With S = { b : mask[b] != 0, and -- kind BCN_NORM_STEP only -- status[b] has neither
+ * BCN_ST_ITMAX nor BCN_ST_BLOWUP }, n = |S|, and for a column x (all in float64):
+ *   update (training != 0, n > 0):  m_b = mean_S x; M2_b = sum_S (x - m_b)^2, summed from deviations; d = m_b - mean; tot = count + n;
+ *                                   mean' = mean + d n / tot; var' = (var count + M2_b + d^2 count n / tot) / tot; count' = tot
+ *   apply:                          y = clip((x - mean') / sqrt(var' + eps), -clip, clip), rounded once to the handle's dtype
+ * kind BCN_NORM_STEP: the columns of obs are updated and norm_obs[b] written for mask[b] != 0; ret[b] = gamma ret[b] + rwd[b] for
+ *   mask[b] != 0, the return statistics updated from ret over S, norm_rwd[b] = clip(rwd[b] / sqrt(ret_var' + eps), +-clip_rwd), then
+ *   ret[b] = 0 where done[b] | trunc[b]; with ep_buf_dev, norm_final_obs[b] = apply(final_obs[b]) where mask[b] != 0 and
+ *   finished[b] != 0 (these rows are NOT counted: behind a masked reset obs already holds the reset observation, which is).
+ * kind BCN_NORM_RESET: status is ignored (it is stale); observation statistics and norm_obs of the masked replicas only, and their
+ *   ret becomes 0; norm_rwd and the return statistics stay.
+ * training == 0: apply only, with the statistics as they are; nothing but the three outputs is written.
+ * A replica the mask switches off keeps its rows of every output and its ret.  BCN_ERR_ARG, and nothing dereferenced, for a NULL
+ * handle or buffer, a misaligned buffer, another kind, gamma outside [0, 1] or eps, clip_obs, clip_rwd <= 0. */
+enum { BCN_NORM_STEP = 0, BCN_NORM_RESET = 1 };
+BCN_API size_t bcn_normalize_bytes(bcn_env_t h);
+BCN_API int bcn_normalize_layout(bcn_env_t h, bcn_snapshot_seg* segs, int max_segs);
+BCN_API int bcn_normalize(bcn_env_t h, const void* out_buf_dev, void* norm_buf_dev, const void* ep_buf_dev, const uint8_t* mask_dev,
+                          int kind, int training, double gamma, double eps, double clip_obs, double clip_rwd, void* stream);
 /* name of the kernel the last *_step dispatched, e.g. "ns2d_fast_sched" (before the first step: the
  * variant's plain kernel); for profiles */
 BCN_API const char* bcn_kernel_name(bcn_env_t h);
