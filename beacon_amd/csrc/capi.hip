@@ -655,9 +655,9 @@ static int shkadov_reset_random_t(bcn_env_t h, const void* init, const int32_t* 
 // ------------------------------------------------------------------------------------------
 // snapshots (snapshot.h): which arrays of a handle are state, and where they sit in a snapshot of n replicas
 // ------------------------------------------------------------------------------------------
-// One named segment: `planes` arrays of [replicas][row_elems] one behind the other -- in the handle (plane stride = batch rows) and
-// in the snapshot (plane stride = n rows).
-struct SnapDesc { const char* name; int elem; int planes; size_t row_elems; void* dev; };
+// One named segment of a handle (SegDesc, snapshot.h) and where it lives there: plane stride = batch rows in the handle, n rows in the
+// snapshot.
+struct SnapDesc { SegDesc seg; void* dev; };
 
 // What the next *_step reads of what an earlier call wrote ("Snapshots", has the reasoning for what is left out: us / vs,
 // the work arrays, fscr, the sweep counts, the scheduler block and the cycle counters are rewritten or zeroed inside every step).
@@ -666,28 +666,48 @@ int snap_desc(bcn_env_t h, SnapDesc* d) {
   int n = 0;
   if (h->kind == BCN_RAYLEIGH || h->kind == BCN_MIXING) {
     auto* e = static_cast<NS2DEnv<real>*>(h);
-    d[n++] = {"fields", BCN_SNAP_REAL, 4, (size_t)e->a.ncell, e->fields.p};
-    d[n++] = {"obs_hist", BCN_SNAP_REAL, 1, (size_t)e->a.n_obs, e->obs_hist.p};
-    if (h->kind == BCN_RAYLEIGH) d[n++] = {"a_last", BCN_SNAP_REAL, 1, (size_t)e->a.n_sgts, e->a_last.p};
-    else d[n++] = {"ia_last", BCN_SNAP_I32, 1, 1, e->ia_last.p};
-    d[n++] = {"stp", BCN_SNAP_I32, 1, 1, e->stpbuf.p};
+    d[n++] = {{"fields", BCN_SNAP_REAL, 4, (size_t)e->a.ncell}, e->fields.p};
+    d[n++] = {{"obs_hist", BCN_SNAP_REAL, 1, (size_t)e->a.n_obs}, e->obs_hist.p};
+    if (h->kind == BCN_RAYLEIGH) d[n++] = {{"a_last", BCN_SNAP_REAL, 1, (size_t)e->a.n_sgts}, e->a_last.p};
+    else d[n++] = {{"ia_last", BCN_SNAP_I32, 1, 1}, e->ia_last.p};
+    d[n++] = {{"stp", BCN_SNAP_I32, 1, 1}, e->stpbuf.p};
   } else if (h->kind == BCN_LORENZ || h->kind == BCN_VORTEX) {
     auto* e = static_cast<OdeEnv<real>*>(h);
-    d[n++] = {"fields", BCN_SNAP_REAL, e->nreal, 1, e->st.p};
-    if (h->kind == BCN_LORENZ) d[n++] = {"iu", BCN_SNAP_I32, 1, 1, e->iubuf.p};
-    d[n++] = {"stp", BCN_SNAP_I32, 1, 1, e->stpbuf.p};
+    d[n++] = {{"fields", BCN_SNAP_REAL, e->nreal, 1}, e->st.p};
+    if (h->kind == BCN_LORENZ) d[n++] = {{"iu", BCN_SNAP_I32, 1, 1}, e->iubuf.p};
+    d[n++] = {{"stp", BCN_SNAP_I32, 1, 1}, e->stpbuf.p};
   } else {
     auto* e = static_cast<Env1D<real>*>(h);
-    d[n++] = {"fields", BCN_SNAP_REAL, e->nfields, (size_t)e->a.n, e->fields.p};
-    d[n++] = {"a_last", BCN_SNAP_REAL, 1, (size_t)e->nact, e->a_last.p};
-    d[n++] = {"a_prev", BCN_SNAP_REAL, 1, (size_t)e->nact, e->a_prev.p};
-    d[n++] = {"stp", BCN_SNAP_I32, 1, 1, e->stpbuf.p};
-    d[n++] = {"nctr", BCN_SNAP_U32, 1, 1, e->nctrbuf.p};
+    d[n++] = {{"fields", BCN_SNAP_REAL, e->nfields, (size_t)e->a.n}, e->fields.p};
+    d[n++] = {{"a_last", BCN_SNAP_REAL, 1, (size_t)e->nact}, e->a_last.p};
+    d[n++] = {{"a_prev", BCN_SNAP_REAL, 1, (size_t)e->nact}, e->a_prev.p};
+    d[n++] = {{"stp", BCN_SNAP_I32, 1, 1}, e->stpbuf.p};
+    d[n++] = {{"nctr", BCN_SNAP_U32, 1, 1}, e->nctrbuf.p};
   }
   return n;
 }
 
 inline size_t snap_up16(size_t x) { return (x + 15) / 16 * 16; }
+inline size_t seg_elem_bytes(int elem, size_t esz) {
+  return elem == BCN_SNAP_REAL ? esz : elem == BCN_SNAP_U8 ? 1 : elem == BCN_SNAP_F64 || elem == BCN_SNAP_I64 ? 8 : 4;
+}
+
+// THE layout of every packed buffer (snapshot, episode, per-jet, normaliser): the nd segments of `d` one behind the other for n
+// replicas of an env whose reals take esz bytes, every start a multiple of 16 bytes; a segment takes (planes == 0 ? 1 : planes * n) *
+// row_elems elements.  Fills the first max_lay entries of `lay` (NULL: none) and returns the bytes of the buffer.
+size_t seg_layout(const SegDesc* d, int nd, size_t n, size_t esz, bcn_snapshot_seg* lay, int max_lay) {
+  size_t off = 0;
+  for (int k = 0; k < nd; k++) {
+    off = snap_up16(off);
+    if (lay && k < max_lay) {
+      memset(&lay[k], 0, sizeof(lay[k]));
+      strncpy(lay[k].name, d[k].name, sizeof(lay[k].name) - 1);
+      lay[k].offset = off; lay[k].elem = d[k].elem; lay[k].planes = d[k].planes; lay[k].row_elems = (int64_t)d[k].row_elems;
+    }
+    off += (d[k].planes == 0 ? 1 : (size_t)d[k].planes * n) * d[k].row_elems * seg_elem_bytes(d[k].elem, esz);
+  }
+  return snap_up16(off);
+}
 
 // Lays out a snapshot of n replicas of this handle's configuration: the bytes it takes, optionally the named segments (`lay`, up to
 // max_lay; the count is returned) and the kernels' table `t` (handle side: this handle's arrays and the packed output buffer
@@ -697,27 +717,25 @@ int snap_build(bcn_env_t h, int n, char* out_buf, SnapTable* t, bcn_snapshot_seg
   int nd = BCN_BY_DTYPE(h->dtype, snap_desc, h, d);
   const size_t B = (size_t)h->batch, esz = h->esz;
   const bcn_out_layout_t o = bcn_out_layout(B, (size_t)h->n_obs, esz);   // the callers' out_buf
-  d[nd++] = {"obs", BCN_SNAP_REAL, 1, (size_t)h->n_obs, out_buf};
-  d[nd++] = {"rwd", BCN_SNAP_REAL, 1, 1, out_buf ? out_buf + o.rwd : nullptr};
-  d[nd++] = {"status", BCN_SNAP_I32, 1, 1, out_buf ? out_buf + o.status : nullptr};
-  d[nd++] = {"done", BCN_SNAP_U8, 1, 1, out_buf ? out_buf + o.done : nullptr};
-  d[nd++] = {"trunc", BCN_SNAP_U8, 1, 1, out_buf ? out_buf + o.trunc : nullptr};
-  size_t off = 0, blk = 0;
+  d[nd++] = {{"obs", BCN_SNAP_REAL, 1, (size_t)h->n_obs}, out_buf};
+  d[nd++] = {{"rwd", BCN_SNAP_REAL, 1, 1}, out_buf ? out_buf + o.rwd : nullptr};
+  d[nd++] = {{"status", BCN_SNAP_I32, 1, 1}, out_buf ? out_buf + o.status : nullptr};
+  d[nd++] = {{"done", BCN_SNAP_U8, 1, 1}, out_buf ? out_buf + o.done : nullptr};
+  d[nd++] = {{"trunc", BCN_SNAP_U8, 1, 1}, out_buf ? out_buf + o.trunc : nullptr};
+  SegDesc sd[16];
+  bcn_snapshot_seg sl[16];
+  for (int k = 0; k < nd; k++) sd[k] = d[k].seg;
+  const size_t total = seg_layout(sd, nd, (size_t)n, esz, sl, nd);
+  size_t blk = 0;
   int ns = 0;
   for (int k = 0; k < nd; k++) {
-    off = snap_up16(off);
-    const size_t el = d[k].elem == BCN_SNAP_REAL ? esz : d[k].elem == BCN_SNAP_U8 ? 1 : 4;
-    const size_t row = d[k].row_elems * el;
-    if (lay && k < max_lay) {
-      memset(&lay[k], 0, sizeof(lay[k]));
-      strncpy(lay[k].name, d[k].name, sizeof(lay[k].name) - 1);
-      lay[k].offset = off; lay[k].elem = d[k].elem; lay[k].planes = d[k].planes; lay[k].row_elems = (int64_t)d[k].row_elems;
-    }
-    for (int pl = 0; t && d[k].dev && pl < d[k].planes; pl++) {
+    const size_t row = sd[k].row_elems * seg_elem_bytes(sd[k].elem, esz);
+    if (lay && k < max_lay) lay[k] = sl[k];
+    for (int pl = 0; t && d[k].dev && pl < sd[k].planes; pl++) {
       if (ns >= BCN_SNAP_MAX_SEG || row == 0 || row > 0xffffffffull) { bcn_set_error("snapshot: segment table overflow"); return -1; }
       SnapSeg& g = t->seg[ns++];
       g.dev = static_cast<char*>(d[k].dev) + (size_t)pl * B * row;
-      g.snap_off = off + (size_t)pl * (size_t)n * row;
+      g.snap_off = sl[k].offset + (size_t)pl * (size_t)n * row;
       g.row_bytes = (unsigned)row;
       g.blk0 = (unsigned)blk;
       if (row >= BCN_SNAP_LONG_ROW) {
@@ -731,93 +749,61 @@ int snap_build(bcn_env_t h, int n, char* out_buf, SnapTable* t, bcn_snapshot_seg
       }
       if (blk > 0x7fffffffull) { bcn_set_error("snapshot: batch too large for one launch"); return -1; }
     }
-    off += (size_t)d[k].planes * (size_t)n * row;
   }
-  if (bytes) *bytes = snap_up16(off);
+  if (bytes) *bytes = total;
   if (t) { t->nseg = ns; t->batch = h->batch; t->n_src = n; t->nblk = (unsigned)blk; }
   return nd;
 }
 
-// Lays out the episode buffer of this handle's batch (episode.h): the nine segments into `lay` (room for BCN_EP_NSEG) and / or the
-// bytes it takes.  Only batch, observation length and dtype of the handle are used.
-int episode_build(bcn_env_t h, bcn_snapshot_seg* lay, size_t* bytes) {
-  const size_t B = (size_t)h->batch, esz = h->esz;
-  if (h->batch < 1 || h->n_obs < 1 || B * (size_t)h->n_obs * esz / 4 > 0x7fffffffull) {
+// The three bookkeeping buffers of this handle's batch: their range check, their segment table (episode.h, normalize.h,
+// shkadov_jets.h) and seg_layout -- the first max_lay segments into `lay` and / or the bytes the buffer takes; the segment count is
+// returned, -1 with the message set when one launch cannot cover the batch.  Only batch, observation length (jets: the action
+// length, which is the jet count) and dtype of the handle are used.
+int episode_build(bcn_env_t h, bcn_snapshot_seg* lay, int max_lay, size_t* bytes) {
+  const size_t B = (size_t)h->batch;
+  if (h->batch < 1 || h->n_obs < 1 || B * (size_t)h->n_obs * h->esz / 4 > 0x7fffffffull) {
     bcn_set_error("episode: batch %d x %d observations is outside what one launch covers", h->batch, h->n_obs);
     return -1;
   }
-  const struct { const char* name; int elem; size_t row_bytes; int64_t row_elems; } d[BCN_EP_NSEG] = {
-      {"ret", BCN_SNAP_REAL, esz, 1},      {"len", BCN_SNAP_I32, 4, 1},     {"last_ret", BCN_SNAP_REAL, esz, 1},
-      {"last_len", BCN_SNAP_I32, 4, 1},    {"count", BCN_SNAP_I32, 4, 1},   {"sum_ret", BCN_SNAP_F64, 8, 1},
-      {"sum_len", BCN_SNAP_I64, 8, 1},     {"finished", BCN_SNAP_U8, 1, 1}, {"final_obs", BCN_SNAP_REAL, (size_t)h->n_obs * esz, h->n_obs}};
-  size_t off = 0;
-  for (int k = 0; k < BCN_EP_NSEG; k++) {
-    off = snap_up16(off);
-    if (lay) {
-      memset(&lay[k], 0, sizeof(lay[k]));
-      strncpy(lay[k].name, d[k].name, sizeof(lay[k].name) - 1);
-      lay[k].offset = off; lay[k].elem = d[k].elem; lay[k].planes = 1; lay[k].row_elems = d[k].row_elems;
-    }
-    off += B * d[k].row_bytes;
-  }
-  if (bytes) *bytes = snap_up16(off);
+  SegDesc d[BCN_EP_NSEG];
+  episode_segs((size_t)h->n_obs, d);
+  const size_t total = seg_layout(d, BCN_EP_NSEG, B, h->esz, lay, max_lay);
+  if (bytes) *bytes = total;
   return BCN_EP_NSEG;
 }
-
-// Lays out the normaliser buffer of this handle's batch (normalize.h): the eleven segments into `lay` (room for BCN_NRM_NSEG) and / or
-// the bytes it takes.  Only batch, observation length and dtype of the handle are used.  A segment that does not scale with the
-// batch has planes = 0 and row_elems = its length in elements.
-int normalize_build(bcn_env_t h, bcn_snapshot_seg* lay, size_t* bytes) {
-  const size_t B = (size_t)h->batch, esz = h->esz, n = (size_t)h->n_obs;
+int normalize_build(bcn_env_t h, bcn_snapshot_seg* lay, int max_lay, size_t* bytes) {
+  const size_t B = (size_t)h->batch, n = (size_t)h->n_obs;
   if (h->batch < 1 || h->n_obs < 1 || B * n > 0x7fffffffull) {
     bcn_set_error("normalize: batch %d x %d observations is outside what one launch covers", h->batch, h->n_obs);
     return -1;
   }
-  const NormalizeShape sh = normalize_shape(B, n);
-  const size_t scratch = ((2 * (n + 1) + 2) + (size_t)sh.G * (n + 1) * 3) * 8;
-  // name, element type, planes (0: not per replica), row_elems, bytes
-  const struct { const char* name; int elem; int planes; int64_t row_elems; size_t nbytes; } d[BCN_NRM_NSEG] = {
-      {"obs_mean", BCN_SNAP_F64, 0, (int64_t)n, n * 8}, {"obs_var", BCN_SNAP_F64, 0, (int64_t)n, n * 8}, {"obs_count", BCN_SNAP_F64, 0, 1, 8},
-      {"ret_mean", BCN_SNAP_F64, 0, 1, 8},              {"ret_var", BCN_SNAP_F64, 0, 1, 8},              {"ret_count", BCN_SNAP_F64, 0, 1, 8},
-      {"ret", BCN_SNAP_F64, 1, 1, B * 8},               {"norm_obs", BCN_SNAP_REAL, 1, (int64_t)n, B * n * esz},
-      {"norm_rwd", BCN_SNAP_REAL, 1, 1, B * esz},       {"norm_final_obs", BCN_SNAP_REAL, 1, (int64_t)n, B * n * esz},
-      {"scratch", BCN_SNAP_U8, 0, (int64_t)scratch, scratch}};
-  size_t off = 0;
-  for (int k = 0; k < BCN_NRM_NSEG; k++) {
-    off = snap_up16(off);
-    if (lay) {
-      memset(&lay[k], 0, sizeof(lay[k]));
-      strncpy(lay[k].name, d[k].name, sizeof(lay[k].name) - 1);
-      lay[k].offset = off; lay[k].elem = d[k].elem; lay[k].planes = d[k].planes; lay[k].row_elems = d[k].row_elems;
-    }
-    off += d[k].nbytes;
-  }
-  if (bytes) *bytes = snap_up16(off);
+  SegDesc d[BCN_NRM_NSEG];
+  normalize_segs(B, n, d);
+  const size_t total = seg_layout(d, BCN_NRM_NSEG, B, h->esz, lay, max_lay);
+  if (bytes) *bytes = total;
   return BCN_NRM_NSEG;
 }
-
-// Lays out the per-jet buffer of a shkadov handle (shkadov_jets.h): the four [B][n_jets] segments into `lay` (room for
-// BCN_JETS_NSEG) and / or the bytes it takes.  Only batch, jet count (the action length) and dtype of the handle are used.
-int jets_build(bcn_env_t h, bcn_snapshot_seg* lay, size_t* bytes) {
-  const size_t B = (size_t)h->batch, esz = h->esz, nj = (size_t)h->n_act;
+int jets_build(bcn_env_t h, bcn_snapshot_seg* lay, int max_lay, size_t* bytes) {
+  const size_t B = (size_t)h->batch, nj = (size_t)h->n_act;
   if (h->batch < 1 || h->n_act < 1 || B * nj > 0x7fffffffull) {
     bcn_set_error("shkadov jets: batch %d x %d jets is outside what one launch covers", h->batch, h->n_act);
     return -1;
   }
-  const struct { const char* name; int elem; size_t el; } d[BCN_JETS_NSEG] = {
-      {"rwd_jets", BCN_SNAP_REAL, esz}, {"ret", BCN_SNAP_REAL, esz}, {"last_ret", BCN_SNAP_REAL, esz}, {"sum_ret", BCN_SNAP_F64, 8}};
-  size_t off = 0;
-  for (int k = 0; k < BCN_JETS_NSEG; k++) {
-    off = snap_up16(off);
-    if (lay) {
-      memset(&lay[k], 0, sizeof(lay[k]));
-      strncpy(lay[k].name, d[k].name, sizeof(lay[k].name) - 1);
-      lay[k].offset = off; lay[k].elem = d[k].elem; lay[k].planes = 1; lay[k].row_elems = (int64_t)nj;
-    }
-    off += B * nj * d[k].el;
-  }
-  if (bytes) *bytes = snap_up16(off);
+  SegDesc d[BCN_JETS_NSEG];
+  jets_segs(nj, d);
+  const size_t total = seg_layout(d, BCN_JETS_NSEG, B, h->esz, lay, max_lay);
+  if (bytes) *bytes = total;
   return BCN_JETS_NSEG;
+}
+// the bodies of the bcn_*_bytes / bcn_*_layout pairs of those three, behind each entry point's own argument checks
+typedef int (*seg_build_fn)(bcn_env_t, bcn_snapshot_seg*, int, size_t*);
+inline size_t built_bytes(seg_build_fn build, bcn_env_t h) {
+  size_t bytes = 0;
+  return build(h, nullptr, 0, &bytes) < 0 ? 0 : bytes;       // (the build function has set the message)
+}
+inline int built_layout(seg_build_fn build, bcn_env_t h, bcn_snapshot_seg* segs, int max_segs) {
+  const int nd = build(h, segs, max_segs, nullptr);
+  return nd < 0 ? 0 : nd;
 }
 
 // bcn_shkadov_jet_rewards of a checked shkadov handle: the film and the jet layout come from the handle's argument block, the
@@ -831,10 +817,10 @@ int shkadov_jets_t(bcn_env_t h, const char* out, char* jets, const bcn_snapshot_
   a.status = reinterpret_cast<const int32_t*>(out + o.status);
   a.done = reinterpret_cast<const uint8_t*>(out + o.done); a.trunc = reinterpret_cast<const uint8_t*>(out + o.trunc);
   a.mask = e.mask;
-  a.rwd_jets = reinterpret_cast<real*>(jets + lay[0].offset);
-  a.ret = with_stats ? reinterpret_cast<real*>(jets + lay[1].offset) : nullptr;
-  a.last_ret = reinterpret_cast<real*>(jets + lay[2].offset);
-  a.sum_ret = reinterpret_cast<double*>(jets + lay[3].offset);
+  a.rwd_jets = reinterpret_cast<real*>(jets + lay[JETS_RWD_JETS].offset);
+  a.ret = with_stats ? reinterpret_cast<real*>(jets + lay[JETS_RET].offset) : nullptr;
+  a.last_ret = reinterpret_cast<real*>(jets + lay[JETS_LAST_RET].offset);
+  a.sum_ret = reinterpret_cast<double*>(jets + lay[JETS_SUM_RET].offset);
   a.npairs = (unsigned)h->batch * (unsigned)e.n_jets;
   a.n = e.n; a.nx = e.nx;
   a.n_jets = e.n_jets; a.jet_pos = e.jet_pos; a.jet_space = e.jet_space; a.l_rwd = e.l_rwd;
@@ -1221,23 +1207,18 @@ int bcn_snapshot_load(bcn_env_t h, const void* snap_dev, int n_src, const int32_
 }
 // ---- episode statistics (episode.h) ------------------------------------------------------------
 size_t bcn_episode_bytes(bcn_env_t h) {
-  size_t bytes = 0;
   if (!h) { bcn_set_error("bcn_episode_bytes: null handle"); return 0; }
-  if (episode_build(h, nullptr, &bytes) < 0) return 0;      // (episode_build has set the message)
-  return bytes;
+  return built_bytes(episode_build, h);
 }
 int bcn_episode_layout(bcn_env_t h, bcn_snapshot_seg* segs, int max_segs) {
   if (!h || (max_segs > 0 && !segs)) { bcn_set_error("bcn_episode_layout: null handle/array"); return 0; }
-  bcn_snapshot_seg lay[BCN_EP_NSEG];
-  const int nd = episode_build(h, lay, nullptr);
-  for (int k = 0; k < nd && k < max_segs; k++) segs[k] = lay[k];
-  return nd < 0 ? 0 : nd;
+  return built_layout(episode_build, h, segs, max_segs);
 }
 int bcn_episode_track(bcn_env_t h, const void* out_buf_dev, void* ep_buf_dev, const uint8_t* mask_dev, void* stream) {
   if (!h || !out_buf_dev || !ep_buf_dev) { bcn_set_error("bcn_episode_track: null handle/buffer"); return BCN_ERR_ARG; }
   if (!snap_ptr_ok(out_buf_dev) || !snap_ptr_ok(ep_buf_dev)) { bcn_set_error("bcn_episode_track: buffers must be 16-byte aligned"); return BCN_ERR_ARG; }
   bcn_snapshot_seg lay[BCN_EP_NSEG];
-  if (episode_build(h, lay, nullptr) < 0) return BCN_ERR_ARG;
+  if (episode_build(h, lay, BCN_EP_NSEG, nullptr) < 0) return BCN_ERR_ARG;
   const size_t B = (size_t)h->batch, row = (size_t)h->n_obs * h->esz;
   const bcn_out_layout_t o = bcn_out_layout(B, (size_t)h->n_obs, h->esz);
   const char* out = static_cast<const char*>(out_buf_dev);
@@ -1246,11 +1227,11 @@ int bcn_episode_track(bcn_env_t h, const void* out_buf_dev, void* ep_buf_dev, co
   a.obs = out; a.rwd = out + o.rwd;
   a.done = reinterpret_cast<const uint8_t*>(out + o.done); a.trunc = reinterpret_cast<const uint8_t*>(out + o.trunc);
   a.mask = mask_dev;
-  a.ret = ep + lay[0].offset; a.len = reinterpret_cast<int32_t*>(ep + lay[1].offset);
-  a.last_ret = ep + lay[2].offset; a.last_len = reinterpret_cast<int32_t*>(ep + lay[3].offset);
-  a.count = reinterpret_cast<int32_t*>(ep + lay[4].offset); a.sum_ret = reinterpret_cast<double*>(ep + lay[5].offset);
-  a.sum_len = reinterpret_cast<long long*>(ep + lay[6].offset); a.finished = reinterpret_cast<uint8_t*>(ep + lay[7].offset);
-  a.final_obs = ep + lay[8].offset;
+  a.ret = ep + lay[EP_RET].offset; a.len = reinterpret_cast<int32_t*>(ep + lay[EP_LEN].offset);
+  a.last_ret = ep + lay[EP_LAST_RET].offset; a.last_len = reinterpret_cast<int32_t*>(ep + lay[EP_LAST_LEN].offset);
+  a.count = reinterpret_cast<int32_t*>(ep + lay[EP_COUNT].offset); a.sum_ret = reinterpret_cast<double*>(ep + lay[EP_SUM_RET].offset);
+  a.sum_len = reinterpret_cast<long long*>(ep + lay[EP_SUM_LEN].offset); a.finished = reinterpret_cast<uint8_t*>(ep + lay[EP_FINISHED].offset);
+  a.final_obs = ep + lay[EP_FINAL_OBS].offset;
   a.batch = (unsigned)B;
   a.nbk = (unsigned)((B + BCN_EP_NT - 1) / BCN_EP_NT);
   a.unit = copy_unit(row);      // rows are reals: multiples of 4 bytes
@@ -1262,19 +1243,14 @@ int bcn_episode_track(bcn_env_t h, const void* out_buf_dev, void* ep_buf_dev, co
 }
 // ---- per-jet rewards and returns of shkadov (shkadov_jets.h) --------------------------------------
 size_t bcn_shkadov_jets_bytes(bcn_env_t h) {
-  size_t bytes = 0;
   if (!h) { bcn_set_error("bcn_shkadov_jets_bytes: null handle"); return 0; }
   if (h->kind != BCN_SHKADOV) { bcn_set_error("bcn_shkadov_jets_bytes: handle is not a BCN_SHKADOV env"); return 0; }
-  if (jets_build(h, nullptr, &bytes) < 0) return 0;         // (jets_build has set the message)
-  return bytes;
+  return built_bytes(jets_build, h);
 }
 int bcn_shkadov_jets_layout(bcn_env_t h, bcn_snapshot_seg* segs, int max_segs) {
   if (!h || (max_segs > 0 && !segs)) { bcn_set_error("bcn_shkadov_jets_layout: null handle/array"); return 0; }
   if (h->kind != BCN_SHKADOV) { bcn_set_error("bcn_shkadov_jets_layout: handle is not a BCN_SHKADOV env"); return 0; }
-  bcn_snapshot_seg lay[BCN_JETS_NSEG];
-  const int nd = jets_build(h, lay, nullptr);
-  for (int k = 0; k < nd && k < max_segs; k++) segs[k] = lay[k];
-  return nd < 0 ? 0 : nd;
+  return built_layout(jets_build, h, segs, max_segs);
 }
 int bcn_shkadov_jet_rewards(bcn_env_t h, const void* out_buf_dev, void* jets_buf_dev, int with_stats, void* stream) {
   if (!h || !out_buf_dev || !jets_buf_dev) { bcn_set_error("bcn_shkadov_jet_rewards: null handle/buffer"); return BCN_ERR_ARG; }
@@ -1284,22 +1260,17 @@ int bcn_shkadov_jet_rewards(bcn_env_t h, const void* out_buf_dev, void* jets_buf
     return BCN_ERR_ARG;
   }
   bcn_snapshot_seg lay[BCN_JETS_NSEG];
-  if (jets_build(h, lay, nullptr) < 0) return BCN_ERR_ARG;
+  if (jets_build(h, lay, BCN_JETS_NSEG, nullptr) < 0) return BCN_ERR_ARG;
   return BCN_BY_DTYPE(h->dtype, shkadov_jets_t, h, static_cast<const char*>(out_buf_dev), static_cast<char*>(jets_buf_dev), lay, with_stats, stream);
 }
 // ---- running normalisation of observations and rewards (normalize.h) ------------------------------
 size_t bcn_normalize_bytes(bcn_env_t h) {
-  size_t bytes = 0;
   if (!h) { bcn_set_error("bcn_normalize_bytes: null handle"); return 0; }
-  if (normalize_build(h, nullptr, &bytes) < 0) return 0;    // (normalize_build has set the message)
-  return bytes;
+  return built_bytes(normalize_build, h);
 }
 int bcn_normalize_layout(bcn_env_t h, bcn_snapshot_seg* segs, int max_segs) {
   if (!h || (max_segs > 0 && !segs)) { bcn_set_error("bcn_normalize_layout: null handle/array"); return 0; }
-  bcn_snapshot_seg lay[BCN_NRM_NSEG];
-  const int nd = normalize_build(h, lay, nullptr);
-  for (int k = 0; k < nd && k < max_segs; k++) segs[k] = lay[k];
-  return nd < 0 ? 0 : nd;
+  return built_layout(normalize_build, h, segs, max_segs);
 }
 int bcn_normalize(bcn_env_t h, const void* out_buf_dev, void* norm_buf_dev, const void* ep_buf_dev, const uint8_t* mask_dev, int kind,
                   int training, double gamma, double eps, double clip_obs, double clip_rwd, void* stream) {
@@ -1314,8 +1285,8 @@ int bcn_normalize(bcn_env_t h, const void* out_buf_dev, void* norm_buf_dev, cons
     return BCN_ERR_ARG;
   }
   bcn_snapshot_seg lay[BCN_NRM_NSEG], el[BCN_EP_NSEG];
-  if (normalize_build(h, lay, nullptr) < 0) return BCN_ERR_ARG;
-  if (ep_buf_dev && episode_build(h, el, nullptr) < 0) return BCN_ERR_ARG;
+  if (normalize_build(h, lay, BCN_NRM_NSEG, nullptr) < 0) return BCN_ERR_ARG;
+  if (ep_buf_dev && episode_build(h, el, BCN_EP_NSEG, nullptr) < 0) return BCN_ERR_ARG;
   const size_t B = (size_t)h->batch, n = (size_t)h->n_obs;
   const bcn_out_layout_t o = bcn_out_layout(B, n, h->esz);
   const NormalizeShape sh = normalize_shape(B, n);
@@ -1327,14 +1298,15 @@ int bcn_normalize(bcn_env_t h, const void* out_buf_dev, void* norm_buf_dev, cons
   a.status = reinterpret_cast<const int32_t*>(out + o.status);
   a.done = reinterpret_cast<const uint8_t*>(out + o.done); a.trunc = reinterpret_cast<const uint8_t*>(out + o.trunc);
   a.mask = mask_dev;
-  a.finished = ep ? reinterpret_cast<const uint8_t*>(ep + el[7].offset) : nullptr;
-  a.final_obs = ep ? ep + el[8].offset : nullptr;
-  a.obs_mean = reinterpret_cast<double*>(nb + lay[0].offset); a.obs_var = reinterpret_cast<double*>(nb + lay[1].offset);
-  a.obs_count = reinterpret_cast<double*>(nb + lay[2].offset); a.ret_mean = reinterpret_cast<double*>(nb + lay[3].offset);
-  a.ret_var = reinterpret_cast<double*>(nb + lay[4].offset); a.ret_count = reinterpret_cast<double*>(nb + lay[5].offset);
-  a.ret = reinterpret_cast<double*>(nb + lay[6].offset);
-  a.norm_obs = nb + lay[7].offset; a.norm_rwd = nb + lay[8].offset; a.norm_final_obs = nb + lay[9].offset;
-  a.prev = reinterpret_cast<double*>(nb + lay[10].offset);
+  a.finished = ep ? reinterpret_cast<const uint8_t*>(ep + el[EP_FINISHED].offset) : nullptr;
+  a.final_obs = ep ? ep + el[EP_FINAL_OBS].offset : nullptr;
+  a.obs_mean = reinterpret_cast<double*>(nb + lay[NRM_OBS_MEAN].offset); a.obs_var = reinterpret_cast<double*>(nb + lay[NRM_OBS_VAR].offset);
+  a.obs_count = reinterpret_cast<double*>(nb + lay[NRM_OBS_COUNT].offset); a.ret_mean = reinterpret_cast<double*>(nb + lay[NRM_RET_MEAN].offset);
+  a.ret_var = reinterpret_cast<double*>(nb + lay[NRM_RET_VAR].offset); a.ret_count = reinterpret_cast<double*>(nb + lay[NRM_RET_COUNT].offset);
+  a.ret = reinterpret_cast<double*>(nb + lay[NRM_RET].offset);
+  a.norm_obs = nb + lay[NRM_NORM_OBS].offset; a.norm_rwd = nb + lay[NRM_NORM_RWD].offset;
+  a.norm_final_obs = nb + lay[NRM_NORM_FINAL_OBS].offset;
+  a.prev = reinterpret_cast<double*>(nb + lay[NRM_SCRATCH].offset);
   a.part = a.prev + 2 * (n + 1) + 2;
   a.batch = (unsigned)B; a.n_obs = (unsigned)n;
   a.w = sh.w; a.R = sh.R; a.chunks = sh.chunks; a.S = sh.S; a.G = sh.G;

@@ -9,10 +9,22 @@
 // The kernel reads the packed outputs of a step [obs | rwd | status | done | trunc] and updates the buffer in ONE launch.
 #pragma once
 #include "bcn_common.h"
+#include "snapshot.h"
 
 #define BCN_EP_NT 256             // threads per workgroup
 #define BCN_EP_UPL 4              // copy workgroups: units of the flattened [replica][unit] space per lane
 #define BCN_EP_NSEG 9
+
+// The segments in buffer order: the host addresses them by these names, never by number.
+enum { EP_RET, EP_LEN, EP_LAST_RET, EP_LAST_LEN, EP_COUNT, EP_SUM_RET, EP_SUM_LEN, EP_FINISHED, EP_FINAL_OBS, EP_NSEG_ };
+static_assert(EP_NSEG_ == BCN_EP_NSEG, "episode.h: the enum and BCN_EP_NSEG disagree");
+inline void episode_segs(size_t n_obs, SegDesc* d) {
+  d[EP_RET] = {"ret", BCN_SNAP_REAL, 1, 1};           d[EP_LEN] = {"len", BCN_SNAP_I32, 1, 1};
+  d[EP_LAST_RET] = {"last_ret", BCN_SNAP_REAL, 1, 1}; d[EP_LAST_LEN] = {"last_len", BCN_SNAP_I32, 1, 1};
+  d[EP_COUNT] = {"count", BCN_SNAP_I32, 1, 1};        d[EP_SUM_RET] = {"sum_ret", BCN_SNAP_F64, 1, 1};
+  d[EP_SUM_LEN] = {"sum_len", BCN_SNAP_I64, 1, 1};    d[EP_FINISHED] = {"finished", BCN_SNAP_U8, 1, 1};
+  d[EP_FINAL_OBS] = {"final_obs", BCN_SNAP_REAL, 1, n_obs};
+}
 
 struct EpisodeArgs {
   // the step's outputs

@@ -12,6 +12,7 @@
 // episode buffer (episode.h).
 #pragma once
 #include "bcn_common.h"
+#include "snapshot.h"
 
 #define BCN_NRM_NT 256            // threads per workgroup
 #define BCN_NRM_W 64              // columns a workgroup covers at most: rows longer than this are cut into chunks
@@ -71,6 +72,20 @@ inline NormalizeShape normalize_shape(size_t batch, size_t n_obs) {
   s.S = (unsigned)((batch + g - 1) / g);
   s.G = (unsigned)((batch + s.S - 1) / s.S);
   return s;
+}
+
+// The segments in buffer order: the host addresses them by these names, never by number.
+enum { NRM_OBS_MEAN, NRM_OBS_VAR, NRM_OBS_COUNT, NRM_RET_MEAN, NRM_RET_VAR, NRM_RET_COUNT, NRM_RET, NRM_NORM_OBS, NRM_NORM_RWD,
+       NRM_NORM_FINAL_OBS, NRM_SCRATCH, NRM_NSEG_ };
+static_assert(NRM_NSEG_ == BCN_NRM_NSEG, "normalize.h: the enum and BCN_NRM_NSEG disagree");
+inline void normalize_segs(size_t batch, size_t n_obs, SegDesc* d) {
+  const size_t scratch = ((2 * (n_obs + 1) + 2) + (size_t)normalize_shape(batch, n_obs).G * (n_obs + 1) * 3) * 8;   // prev + part, in bytes
+  d[NRM_OBS_MEAN] = {"obs_mean", BCN_SNAP_F64, 0, n_obs}; d[NRM_OBS_VAR] = {"obs_var", BCN_SNAP_F64, 0, n_obs};
+  d[NRM_OBS_COUNT] = {"obs_count", BCN_SNAP_F64, 0, 1};   d[NRM_RET_MEAN] = {"ret_mean", BCN_SNAP_F64, 0, 1};
+  d[NRM_RET_VAR] = {"ret_var", BCN_SNAP_F64, 0, 1};       d[NRM_RET_COUNT] = {"ret_count", BCN_SNAP_F64, 0, 1};
+  d[NRM_RET] = {"ret", BCN_SNAP_F64, 1, 1};               d[NRM_NORM_OBS] = {"norm_obs", BCN_SNAP_REAL, 1, n_obs};
+  d[NRM_NORM_RWD] = {"norm_rwd", BCN_SNAP_REAL, 1, 1};    d[NRM_NORM_FINAL_OBS] = {"norm_final_obs", BCN_SNAP_REAL, 1, n_obs};
+  d[NRM_SCRATCH] = {"scratch", BCN_SNAP_U8, 0, scratch};
 }
 
 int normalize_launch(const NormalizeArgs& a, hipStream_t s);

@@ -10,10 +10,19 @@
 // The kernel reads the film h of the handle and status / done / trunc of the step's packed outputs [obs | rwd | status | done | trunc].
 #pragma once
 #include "bcn_common.h"
+#include "snapshot.h"
 
 #define BCN_JETS_NT 256                          // threads per workgroup
 #define BCN_JETS_PAIRS (BCN_JETS_NT / BCN_WAVE)  // (replica, jet) pairs per workgroup: one wavefront each
 #define BCN_JETS_NSEG 4
+
+// The segments in buffer order: the host addresses them by these names, never by number.
+enum { JETS_RWD_JETS, JETS_RET, JETS_LAST_RET, JETS_SUM_RET, JETS_NSEG_ };
+static_assert(JETS_NSEG_ == BCN_JETS_NSEG, "shkadov_jets.h: the enum and BCN_JETS_NSEG disagree");
+inline void jets_segs(size_t n_jets, SegDesc* d) {
+  d[JETS_RWD_JETS] = {"rwd_jets", BCN_SNAP_REAL, 1, n_jets}; d[JETS_RET] = {"ret", BCN_SNAP_REAL, 1, n_jets};
+  d[JETS_LAST_RET] = {"last_ret", BCN_SNAP_REAL, 1, n_jets}; d[JETS_SUM_RET] = {"sum_ret", BCN_SNAP_F64, 1, n_jets};
+}
 
 template <typename real>
 struct ShkadovJetsArgs {

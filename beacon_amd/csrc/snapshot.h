@@ -11,6 +11,11 @@
 #define BCN_SNAP_TILE 16384u      // bytes of a long row one workgroup copies: 256 lanes x 4 x 16 B
 #define BCN_SNAP_LONG_ROW 1024u   // rows of at least this many bytes get workgroups of their own (tiles); shorter ones share them
 
+// One named segment of a packed device buffer -- a snapshot, or a bookkeeping buffer (episode.h, shkadov_jets.h, normalize.h): `planes`
+// arrays of [replicas][row_elems] elements of kind `elem` (BCN_SNAP_*) one behind the other; planes = 0: ONE array of row_elems
+// elements that does not scale with the replicas.  seg_layout (capi.hip) lays a table of these out.
+struct SegDesc { const char* name; int elem; int planes; size_t row_elems; };
+
 // One array of the handle: replica b's row is dev + b * row_bytes (rows are contiguous in every handle array), and
 // snap_off + b * row_bytes in a snapshot.
 struct SnapSeg {

@@ -75,17 +75,19 @@ def _segments(segs, k):
             for g in segs[:k]]
 
 
-def _seg_view(buf, layout, name, n, real):
-    """(segment dict, flat typed no-copy view of its planes x n x row_elems elements) of the segment `name` of `buf`, laid out
-    for n replicas of an env computing in `real`; KeyError for an unknown name."""
+def _seg_view(buf, layout, name, n, real, rows_2d=()):
+    """(segment dict, typed no-copy view) of the segment `name` of `buf`, laid out for n replicas of an env computing in `real`;
+    KeyError for an unknown name.  A segment with planes = 0 does not scale with the replicas: row_elems is its length and the view
+    is flat.  The others hold planes x n rows: [planes * n, row_elems] when row_elems > 1 or the name is in `rows_2d`, else flat."""
     for seg in layout:
         if seg["name"] == name:
             break
     else:
         raise KeyError(name)
     dt = _SEG_ELEM.get(seg["elem"], real)
-    nbytes = int(seg["planes"]) * n * int(seg["row_elems"]) * torch.empty((), dtype=dt).element_size()
-    return seg, buf[seg["offset"]:seg["offset"] + nbytes].view(dt)
+    rows, row = int(seg["planes"]) * n, int(seg["row_elems"])
+    v = buf[seg["offset"]:seg["offset"] + max(rows, 1) * row * torch.empty((), dtype=dt).element_size()].view(dt)
+    return seg, (v.view(rows, row) if rows and (row > 1 or name in rows_2d) else v)
 
 
 _POSITIVE_PARAMS = ("ra", "re", "pe", "delta", "g")       # divisors / arguments of roots (include/beacon_hip.h: bcn_set_params)
@@ -121,6 +123,8 @@ class Snapshot(object):
     constructor kwargs), version (of the library that wrote it), noise (sigma, seed, replica_offset: kernel arguments, recorded
     only) and gen_state (the env's torch generator, or None)."""
 
+    ROWS_2D = ("obs", "obs_hist", "a_last", "a_prev")    # [batch, row_elems] also where a row is one element long
+
     def __init__(self, buf, meta):
         if not torch.is_tensor(buf) or buf.dtype != torch.uint8 or buf.dim() != 1:
             raise ValueError("Snapshot: buf must be a 1-D uint8 tensor")
@@ -137,12 +141,10 @@ class Snapshot(object):
         """Typed view (no copy) of one segment: "fields" [planes, batch, ...] (the planes of get_state() in front of the batch
         axis), "obs_hist", "a_last" / "ia_last" / "iu", "a_prev", "stp", "nctr" (the uint32 counters as int32 bits), "obs", "rwd",
         "status", "done", "trunc" -- whichever the env has (names()).  KeyError for any other name."""
-        seg, v = _seg_view(self.buf, self.meta["layout"], name, self.batch, _DT[self.meta["dtype"]][0])
-        n, planes, row = self.batch, int(seg["planes"]), int(seg["row_elems"])
+        seg, v = _seg_view(self.buf, self.meta["layout"], name, self.batch, _DT[self.meta["dtype"]][0], self.ROWS_2D)
         if name == "fields":
-            shape = tuple(self.meta.get("field_shape") or ())
-            return v.view((planes, n) + shape) if shape else v.view(planes, n)
-        return v.view(n, row) if row > 1 or name in ("obs", "obs_hist", "a_last", "a_prev") else v.view(n)
+            return v.view((int(seg["planes"]), self.batch) + tuple(self.meta.get("field_shape") or ()))
+        return v
 
     def to(self, device):
         """The same snapshot with `buf` on `device` (self when it is there already)."""
@@ -160,39 +162,38 @@ class Snapshot(object):
         return snap if device is None else snap.to(device)
 
 
-class EpisodeStats(object):
-    """Episode statistics of one VecEnv, kept on the device by VecEnv.step_autoreset / track_episodes (csrc/episode.hip): `buf`,
-    one uint8 tensor in the layout of bcn_episode_layout (include/beacon_hip.h), and typed no-copy views of its segments, all [B]
-    but the last:
-      ret, len            return (env dtype) and length (int32) of the episode in progress
-      last_ret, last_len  those of the replica's last finished episode
-      count               finished episodes (int32)
-      sum_ret, sum_len    sums of the returns (float64) and lengths (int64) of the finished episodes
-      finished            uint8, 1 where the last tracked step ended an episode (done | trunc): which rows of `obs` are fresh
-      final_obs           [B, obs_dim], the terminal observation; a row is written when its replica finishes and kept until it finishes again
-    Batch totals are not kept: totals() sums the columns.
+class _SegBuffer(object):
+    """One uint8 device buffer `buf` that a bcn_*_layout / bcn_*_bytes pair of the library lays out for an env (the segments:
+    include/beacon_hip.h), with a typed no-copy view of every segment as an attribute of its name.  A subclass states NAMES (the
+    segments, in buffer order), C_FUNCS (the pair), ROWS_2D (the segments viewed [B, row_elems] even where a row is one element
+    long; the others are 2-D only when row_elems > 1, and a segment with planes = 0 is flat [row_elems]), and SHAPE_KEY / NOUN: the
+    env attribute its rows are as long as, recorded by state_dict(), and what load_state_dict() calls it.
     Bookkeeping, like `sweeps`: not part of a Snapshot or of snapshot_signature(); restore() / fork() move env state and leave
-    these statistics where they are -- clear(mask) is the tool after a fork."""
+    these buffers where they are -- clear(mask) is the tool after a fork."""
 
-    NAMES = ("ret", "len", "last_ret", "last_len", "count", "sum_ret", "sum_len", "finished", "final_obs")
+    NAMES, C_FUNCS, ROWS_2D = (), (), ()
+    SHAPE_KEY, NOUN = "obs_dim", "observations"
 
     def __init__(self, env):
         segs = (_lib.SnapshotSeg * 16)()
-        k = env.lib.bcn_episode_layout(env.h, segs, 16)
-        nbytes = env.lib.bcn_episode_bytes(env.h)
+        k = getattr(env.lib, self.C_FUNCS[0])(env.h, segs, 16)
+        nbytes = getattr(env.lib, self.C_FUNCS[1])(env.h)
         if k != len(self.NAMES) or nbytes == 0:
             raise _lib.BeaconHipError("libbeacon_hip: %s" % env.lib.bcn_last_error().decode())
-        self.batch, self.obs_dim, self.tdtype = env.batch, env.obs_dim, env.tdtype
+        self.batch, self.tdtype = env.batch, env.tdtype
+        setattr(self, self.SHAPE_KEY, getattr(env, self.SHAPE_KEY))
         self.buf = torch.zeros((nbytes,), dtype=torch.uint8, device=env.device)
-        self.layout = _segments(segs, k)
-        assert tuple(seg["name"] for seg in self.layout) == self.NAMES
-        for seg in self.layout:
-            setattr(self, seg["name"], self.view(seg["name"]))
+        self._bind(_segments(segs, k))
+
+    def _bind(self, layout):
+        self.layout = layout
+        assert tuple(seg["name"] for seg in layout) == self.NAMES
+        for name in self.NAMES:
+            setattr(self, name, self.view(name))
 
     def view(self, name):
         """Typed view (no copy) of one segment; KeyError for an unknown name."""
-        seg, v = _seg_view(self.buf, self.layout, name, self.batch, self.tdtype)
-        return v.view(self.batch, seg["row_elems"]) if name == "final_obs" else v
+        return _seg_view(self.buf, self.layout, name, self.batch, self.tdtype, self.ROWS_2D)[1]
 
     def clear(self, mask=None):
         """Zero every segment of the replicas selected by `mask` ([B] bool / uint8 tensor or array; None: all).  No host
@@ -206,6 +207,35 @@ class EpisodeStats(object):
             v.masked_fill_(m[:, None] if v.dim() == 2 else m, 0)
         return self
 
+    def state_dict(self):
+        """For checkpoints: the buffer on the CPU and what it was laid out for."""
+        return {"buf": self.buf.cpu(), "batch": self.batch, self.SHAPE_KEY: getattr(self, self.SHAPE_KEY), "dtype": dtype_name(self.tdtype)}
+
+    def load_state_dict(self, d):
+        key, mine = self.SHAPE_KEY, getattr(self, self.SHAPE_KEY)
+        if (int(d["batch"]), int(d[key]), _DT[d["dtype"]][0]) != (self.batch, mine, self.tdtype) or d["buf"].numel() != self.buf.numel():
+            raise ValueError("%s.load_state_dict: statistics of %s replicas x %s %s (%s), this env has %d x %d"
+                             % (type(self).__name__, d["batch"], d[key], self.NOUN, d["dtype"], self.batch, mine))
+        self.buf.copy_(d["buf"])
+        return self
+
+
+class EpisodeStats(_SegBuffer):
+    """Episode statistics of one VecEnv, kept on the device by VecEnv.step_autoreset / track_episodes (csrc/episode.hip): `buf`,
+    one uint8 tensor in the layout of bcn_episode_layout (include/beacon_hip.h), and typed no-copy views of its segments, all [B]
+    but the last:
+      ret, len            return (env dtype) and length (int32) of the episode in progress
+      last_ret, last_len  those of the replica's last finished episode
+      count               finished episodes (int32)
+      sum_ret, sum_len    sums of the returns (float64) and lengths (int64) of the finished episodes
+      finished            uint8, 1 where the last tracked step ended an episode (done | trunc): which rows of `obs` are fresh
+      final_obs           [B, obs_dim], the terminal observation; a row is written when its replica finishes and kept until it finishes again
+    Batch totals are not kept: totals() sums the columns.  Bookkeeping (_SegBuffer)."""
+
+    NAMES = ("ret", "len", "last_ret", "last_len", "count", "sum_ret", "sum_len", "finished", "final_obs")
+    C_FUNCS = ("bcn_episode_layout", "bcn_episode_bytes")
+    ROWS_2D = ("final_obs",)
+
     def totals(self):
         """The one host read: {"episodes", "return_sum", "length_sum", "return_mean", "length_mean"} over the batch, from
         count.sum(), sum_ret.sum() and sum_len.sum() (the means are nan before the first episode ends)."""
@@ -214,21 +244,8 @@ class EpisodeStats(object):
         return {"episodes": n, "return_sum": t[1], "length_sum": ls,
                 "return_mean": t[1] / n if n else float("nan"), "length_mean": ls / n if n else float("nan")}
 
-    def state_dict(self):
-        """For checkpoints: the buffer on the CPU and what it was laid out for."""
-        return {"buf": self.buf.cpu(), "batch": self.batch, "obs_dim": self.obs_dim,
-                "dtype": dtype_name(self.tdtype)}
 
-    def load_state_dict(self, d):
-        if (int(d["batch"]), int(d["obs_dim"]), _DT[d["dtype"]][0]) != (self.batch, self.obs_dim, self.tdtype) or \
-                d["buf"].numel() != self.buf.numel():
-            raise ValueError("EpisodeStats.load_state_dict: statistics of %s replicas x %s observations (%s), this env has %d x %d"
-                             % (d["batch"], d["obs_dim"], d["dtype"], self.batch, self.obs_dim))
-        self.buf.copy_(d["buf"])
-        return self
-
-
-class JetStats(object):
+class JetStats(_SegBuffer):
     """Per-jet rewards and episode returns of one VecShkadov, kept on the device by the launch that follows every step while
     VecShkadov.set_jet_rewards is on (csrc/shkadov_jets.hip): `buf`, one uint8 tensor in the layout of bcn_shkadov_jets_layout
     (include/beacon_hip.h), and typed no-copy views of its segments, all [B, n_jets]:
@@ -236,54 +253,16 @@ class JetStats(object):
       ret        the return (env dtype) of every jet in the episode in progress
       last_ret   that of the replica's last finished episode
       sum_ret    the sum (float64) of the finished returns
-    Episode lengths and counts are those of EpisodeStats: all jets of a replica share one episode clock.
-    Bookkeeping, like EpisodeStats: not part of a Snapshot or of snapshot_signature(); restore() / fork() leave these where they
-    are -- clear(mask) is the tool after a fork."""
+    Episode lengths and counts are those of EpisodeStats: all jets of a replica share one episode clock.  Bookkeeping
+    (_SegBuffer)."""
 
     NAMES = ("rwd_jets", "ret", "last_ret", "sum_ret")
-
-    def __init__(self, env):
-        segs = (_lib.SnapshotSeg * 8)()
-        k = env.lib.bcn_shkadov_jets_layout(env.h, segs, 8)
-        nbytes = env.lib.bcn_shkadov_jets_bytes(env.h)
-        if k != len(self.NAMES) or nbytes == 0:
-            raise _lib.BeaconHipError("libbeacon_hip: %s" % env.lib.bcn_last_error().decode())
-        self.batch, self.n_jets, self.tdtype = env.batch, env.n_jets, env.tdtype
-        self.buf = torch.zeros((nbytes,), dtype=torch.uint8, device=env.device)
-        self.layout = _segments(segs, k)
-        assert tuple(seg["name"] for seg in self.layout) == self.NAMES
-        for seg in self.layout:
-            setattr(self, seg["name"], self.view(seg["name"]))
-
-    def view(self, name):
-        """Typed [B, n_jets] view (no copy) of one segment; KeyError for an unknown name."""
-        return _seg_view(self.buf, self.layout, name, self.batch, self.tdtype)[1].view(self.batch, self.n_jets)
-
-    def clear(self, mask=None):
-        """Zero every segment of the replicas selected by `mask` ([B] bool / uint8 tensor or array; None: all).  No host
-        synchronisation."""
-        if mask is None:
-            self.buf.zero_()
-            return self
-        m = _mask_u8(mask, self.batch, self.buf.device) != 0
-        for name in self.NAMES:
-            getattr(self, name).masked_fill_(m[:, None], 0)
-        return self
-
-    def state_dict(self):
-        """For checkpoints: the buffer on the CPU and what it was laid out for."""
-        return {"buf": self.buf.cpu(), "batch": self.batch, "n_jets": self.n_jets, "dtype": dtype_name(self.tdtype)}
-
-    def load_state_dict(self, d):
-        if (int(d["batch"]), int(d["n_jets"]), _DT[d["dtype"]][0]) != (self.batch, self.n_jets, self.tdtype) or \
-                d["buf"].numel() != self.buf.numel():
-            raise ValueError("JetStats.load_state_dict: statistics of %s replicas x %s jets (%s), this env has %d x %d"
-                             % (d["batch"], d["n_jets"], d["dtype"], self.batch, self.n_jets))
-        self.buf.copy_(d["buf"])
-        return self
+    C_FUNCS = ("bcn_shkadov_jets_layout", "bcn_shkadov_jets_bytes")
+    ROWS_2D = NAMES
+    SHAPE_KEY, NOUN = "n_jets", "jets"
 
 
-class Normalizer(object):
+class Normalizer(_SegBuffer):
     """Running normalisation of the observations and rewards of one VecEnv, kept on the device by the launches that follow every
     reset and step while VecEnv.set_normalize is on (csrc/normalize.hip; what the VecNormalize wrapper of the RL libraries
     computes): `buf`, one uint8 tensor in the layout of bcn_normalize_layout (include/beacon_hip.h), and typed no-copy views of
@@ -295,43 +274,20 @@ class Normalizer(object):
       norm_final_obs [B, obs_dim]                  env dtype: the normalised terminal observations of step_autoreset()
     (`scratch` is private to the kernels.)  `training` (bool): False freezes the statistics -- evaluation -- and only the three
     outputs are written.  gamma, eps, clip_obs, clip_rwd: the arguments of the launch, set by VecEnv.set_normalize.
-    Bookkeeping, like EpisodeStats: not part of a Snapshot or of snapshot_signature(); restore() / fork() leave the normaliser
-    where it is.  state_dict() / load_state_dict() are for checkpoints and for evaluation with the statistics of a training run."""
+    Bookkeeping (_SegBuffer): restore() / fork() leave the normaliser where it is.  state_dict() / load_state_dict() are for
+    checkpoints and for evaluation with the statistics of a training run."""
 
     NAMES = ("obs_mean", "obs_var", "obs_count", "ret_mean", "ret_var", "ret_count", "ret", "norm_obs", "norm_rwd", "norm_final_obs",
              "scratch")
+    C_FUNCS = ("bcn_normalize_layout", "bcn_normalize_bytes")
     KINDS = {"step": 0, "reset": 1}              # include/beacon_hip.h: BCN_NORM_STEP, BCN_NORM_RESET
+    ARGS = ("gamma", "eps", "clip_obs", "clip_rwd")     # of the launch, in its order
 
     def __init__(self, env, gamma=0.99, eps=1e-8, clip_obs=10.0, clip_rwd=10.0, training=True):
-        segs = (_lib.SnapshotSeg * 16)()
-        k = env.lib.bcn_normalize_layout(env.h, segs, 16)
-        nbytes = env.lib.bcn_normalize_bytes(env.h)
-        if k != len(self.NAMES) or nbytes == 0:
-            raise _lib.BeaconHipError("libbeacon_hip: %s" % env.lib.bcn_last_error().decode())
-        self.batch, self.obs_dim, self.tdtype = env.batch, env.obs_dim, env.tdtype
         self.gamma, self.eps, self.clip_obs, self.clip_rwd = float(gamma), float(eps), float(clip_obs), float(clip_rwd)
         self.training = bool(training)
-        self.buf = torch.zeros((nbytes,), dtype=torch.uint8, device=env.device)
-        self.layout = _segments(segs, k)
-        assert tuple(seg["name"] for seg in self.layout) == self.NAMES
-        for seg in self.layout:
-            setattr(self, seg["name"], self.view(seg["name"]))
+        super().__init__(env)
         self.clear()
-
-    def view(self, name):
-        """Typed view (no copy) of one segment; KeyError for an unknown name.  A segment with planes = 0 does not scale with the
-        batch: row_elems is its length."""
-        for seg in self.layout:
-            if seg["name"] == name:
-                break
-        else:
-            raise KeyError(name)
-        if seg["planes"] == 0:
-            dt = _SEG_ELEM.get(seg["elem"], self.tdtype)
-            nbytes = seg["row_elems"] * torch.empty((), dtype=dt).element_size()
-            return self.buf[seg["offset"]:seg["offset"] + nbytes].view(dt)
-        v = _seg_view(self.buf, self.layout, name, self.batch, self.tdtype)[1]
-        return v.view(self.batch, seg["row_elems"]) if seg["row_elems"] > 1 else v
 
     def clear(self):
         """Back to the initial state: counts 0, means 0, variances 1, returns 0 (and the outputs zeroed).  No host
@@ -343,16 +299,11 @@ class Normalizer(object):
 
     def state_dict(self):
         """For checkpoints: the buffer on the CPU, what it was laid out for and the arguments of the launch."""
-        return {"buf": self.buf.cpu(), "batch": self.batch, "obs_dim": self.obs_dim, "dtype": dtype_name(self.tdtype),
-                "gamma": self.gamma, "eps": self.eps, "clip_obs": self.clip_obs, "clip_rwd": self.clip_rwd}
+        return dict(super().state_dict(), **{name: getattr(self, name) for name in self.ARGS})
 
     def load_state_dict(self, d):
-        if (int(d["batch"]), int(d["obs_dim"]), _DT[d["dtype"]][0]) != (self.batch, self.obs_dim, self.tdtype) or \
-                d["buf"].numel() != self.buf.numel():
-            raise ValueError("Normalizer.load_state_dict: statistics of %s replicas x %s observations (%s), this env has %d x %d"
-                             % (d["batch"], d["obs_dim"], d["dtype"], self.batch, self.obs_dim))
-        self.buf.copy_(d["buf"])
-        for name in ("gamma", "eps", "clip_obs", "clip_rwd"):
+        super().load_state_dict(d)
+        for name in self.ARGS:
             if name in d:
                 setattr(self, name, float(d[name]))
         return self
@@ -374,6 +325,7 @@ class VecEnv(object):
     _plugin_prm_defs = None  # ... of their table-reading twins alone (set_params_kernel), on top of _plugin_defs
     _norm = None             # set_normalize: the Normalizer, allocated by the first call and kept
     _norm_on = False         # ... whether the normalising launches follow every reset and step
+    _mask = None             # the replica mask in force in the library (_apply_mask, _masked); None: none
 
     def __init__(self, batch, device="cuda:0", dtype="f32"):
         if not torch.cuda.is_available():
@@ -811,45 +763,58 @@ class VecEnv(object):
         self._mask = _mask_u8(mask, self.batch, self.device)
         _lib.check(self.lib.bcn_set_mask(self.h, _ptr(self._mask)))
 
+    def _masked(self, mask, fn):
+        """THE mask frame of reset() / step() / step_autoreset() / capture(): fn(m) with `mask` in force in the library, m being
+        its uint8 form (None: all replicas); whatever mask is in force afterwards -- the caller's, or ep.finished, which
+        _reset_finished leaves there -- is cleared, also when fn raises.  No mask now and none set: nothing to tell the library."""
+        if mask is not None or self._mask is not None:
+            self._apply_mask(mask)
+        try:
+            return fn(self._mask)
+        finally:
+            if self._mask is not None:
+                self._apply_mask(None)
+
     # -- Gym surface ------------------------------------------------------------------------
     def reset(self, mask=None):
         """Reset every replica, or only those selected by `mask` (what a trainer does when it calls
         reset() on the one env whose episode ended)."""
-        self._apply_mask(mask)
-        try:
-            self._reset()
-            if self._norm_on:
-                self._normalize("reset", self._mask)
-        finally:
-            if mask is not None:
-                self._apply_mask(None)
-        return (self._norm.norm_obs if self._norm_on else self.obs), None
+        return self._masked(mask, self._enqueue_reset)
+
+    def _enqueue_reset(self, m):
+        self._reset()
+        if self._norm_on:
+            self._normalize("reset", m)
+            return self._norm.norm_obs, None
+        return self.obs, None
 
     def _after_step(self):
         """What an env launches directly behind its step kernel in step() / step_autoreset() / capture(), under the same replica
         mask (VecShkadov.set_jet_rewards).  Nothing by default."""
 
+    def _enqueue_step(self, actions, noise, stepped, ep):
+        """THE launches of one step, in the one order that is right, and what the step returns.  `stepped`: the mask in force
+        (_masked), `ep`: the EpisodeStats of a step with auto-reset, else None.
+          1. the step kernel;
+          2. _after_step: the per-jet rewards read the film, so they come in front of the masked reset, which overwrites it;
+          3. with `ep`: the bookkeeping launch and the env's own reset under ep.finished (the caller's _masked clears that mask);
+          4. the normalisation LAST: it counts the reset rows of obs, and normalises ep.final_obs without counting it."""
+        self._step(actions, noise)
+        self._after_step()
+        if ep is not None:
+            self._track(ep, stepped)
+            self._reset_finished(ep)
+        if self._norm_on:
+            self._normalize("step", stepped, ep)
+            return self._norm.norm_obs, self._norm.norm_rwd, self.done, self.trunc, ep
+        return self.obs, self.rwd, self.done, self.trunc, ep
+
     def step(self, actions=None, noise=None, mask=None):
         if self._rotate:
             self._next_outputs(carry=mask is not None)
-        if mask is None and getattr(self, "_mask", None) is None:
-            self._step(actions, noise)            # the common case: no mask now, none set -- nothing to tell the library
-            self._after_step()
-            if self._norm_on:
-                self._normalize("step", None)
-        else:
-            self._apply_mask(mask)
-            try:
-                self._step(actions, noise)
-                self._after_step()
-                if self._norm_on:
-                    self._normalize("step", self._mask)
-            finally:
-                if mask is not None:
-                    self._apply_mask(None)
-        if self._norm_on:
-            return self._norm.norm_obs, self._norm.norm_rwd, self.done, self.trunc, None
-        return self.obs, self.rwd, self.done, self.trunc, None
+        if mask is None and self._mask is None:       # the common case: one frame, no closure
+            return self._enqueue_step(actions, noise, None, None)
+        return self._masked(mask, lambda m: self._enqueue_step(actions, noise, m, None))
 
     # -- episodes ---------------------------------------------------------------------------
     @property
@@ -898,22 +863,7 @@ class VecEnv(object):
         ep = self.episodes
         if self._rotate:
             self._next_outputs(carry=mask is not None)
-        if mask is not None or self._mask is not None:
-            self._apply_mask(mask)
-        try:
-            stepped = self._mask
-            self._step(actions, noise)
-            self._after_step()                    # (reads the film: in front of the masked reset)
-            self._track(ep, stepped)
-            self._reset_finished(ep)
-            if self._norm_on:                     # last: counts the reset rows of obs, normalises ep.final_obs without counting it
-                self._normalize("step", stepped, ep)
-        finally:
-            if self._mask is not None:
-                self._apply_mask(None)
-        if self._norm_on:
-            return self._norm.norm_obs, self._norm.norm_rwd, self.done, self.trunc, ep
-        return self.obs, self.rwd, self.done, self.trunc, ep
+        return self._masked(mask, lambda m: self._enqueue_step(actions, noise, m, ep))
 
     # -- running normalisation --------------------------------------------------------------
     def set_normalize(self, on=True, gamma=0.99, eps=1e-8, clip_obs=10.0, clip_rwd=10.0, training=True):
@@ -1046,14 +996,7 @@ class StepGraph(object):
             for k in range(self.n):
                 a = actions[k] if seq else actions
                 z = None if noise is None else (noise[k] if seq else noise)
-                env._step(a, z)
-                env._after_step()
-                if autoreset:
-                    env._track(ep, None)
-                    env._reset_finished(ep)
-                    env._apply_mask(None)
-                if norm is not None:
-                    env._normalize("step", None, ep)
+                env._masked(None, lambda m: env._enqueue_step(a, z, m, ep))
                 if not keep_steps:
                     continue
                 self.obs_seq[k].copy_(env.obs)
@@ -1475,12 +1418,7 @@ class VecShkadov(VecEnv):
             if n_steps.numel() != self.batch or n_steps.is_floating_point():
                 raise ValueError("VecShkadov.reset_random_device: n_steps must hold %d integers" % self.batch)
             n_steps = n_steps.to(device=self.device, dtype=torch.int32).reshape(self.batch).contiguous()
-        self._apply_mask(mask)
-        try:
-            self._reset_random(n_steps)
-        finally:
-            if mask is not None:
-                self._apply_mask(None)
+        self._masked(mask, lambda m: self._reset_random(n_steps))
         return self.obs, None
 
     def _reset_random(self, n_steps=None):

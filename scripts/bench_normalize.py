@@ -141,11 +141,7 @@ for name, make, div in CASES:
     torch.cuda.synchronize()
     with torch.cuda.graph(gb):
         for _ in range(ng):
-            env._step(a, None)
-            env._after_step()
-            env._track(ep, None)
-            env._reset_finished(ep)
-            env._apply_mask(None)
+            env._masked(None, lambda m: env._enqueue_step(a, None, m, ep))      # what capture(autoreset=True) records per step
             tn.update(env, ep)
     graphs["b"] = gb
     for g in graphs.values():
