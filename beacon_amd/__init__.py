@@ -11,7 +11,7 @@ VecEnv.track_episodes() for the bookkeeping alone, VecEnv.capture(..., autoreset
 
 Importing the package does not touch the GPU; constructing an env does, and raises if the HIP
 library or a ROCm device is missing (there is no CPU fallback for the solver path)."""
-from .vec import Box, Discrete, EpisodeStats, JetStats, Normalizer, Snapshot, VecBurgers, VecEnv, VecLorenz, VecMixing, VecRayleigh, VecShkadov, VecSloshing, VecVortex  # noqa: F401
+from .vec import Box, Discrete, EpisodeStats, JetStats, Normalizer, Rollout, RolloutOverflow, Snapshot, VecBurgers, VecEnv, VecLorenz, VecMixing, VecRayleigh, VecShkadov, VecSloshing, VecVortex  # noqa: F401
 from .lorenz import lorenz  # noqa: F401
 from .vortex import vortex  # noqa: F401
 

@@ -79,6 +79,7 @@ class SnapshotSeg(C.Structure):
 
 SNAP_REAL, SNAP_I32, SNAP_U32, SNAP_U8 = 0, 1, 2, 3      # include/beacon_hip.h: BCN_SNAP_*
 SNAP_F64, SNAP_I64 = 4, 5                                # (bcn_episode_layout only)
+RO_FINAL_OBS, RO_JETS = 1, 2                             # include/beacon_hip.h: BCN_RO_*
 
 # every symbol include/beacon_hip.h declares: (restype, argtypes)
 SIGNATURES = {
@@ -143,6 +144,11 @@ SIGNATURES = {
     "bcn_normalize_bytes": (C.c_size_t, [vp]),
     "bcn_normalize_layout": (C.c_int, [vp, C.POINTER(SnapshotSeg), C.c_int]),
     "bcn_normalize": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, vp]),
+    "bcn_rollout_bytes": (C.c_size_t, [vp, C.c_int, C.c_int]),
+    "bcn_rollout_layout": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(SnapshotSeg), C.c_int]),
+    "bcn_rollout_begin": (C.c_int, [vp, vp, vp, vp, vp]),
+    "bcn_rollout_record": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]),
+    "bcn_rollout_gae": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, vp]),
     "bcn_n_params": (C.c_int, [vp]),
     "bcn_param_name": (C.c_char_p, [vp, C.c_int]),
     "bcn_set_params": (C.c_int, [vp, C.POINTER(C.c_double), vp]),

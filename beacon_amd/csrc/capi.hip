@@ -16,6 +16,7 @@
 #include "episode.h"
 #include "shkadov_jets.h"
 #include "normalize.h"
+#include "rollout.h"
 
 static thread_local char g_err[512] = "";
 
@@ -806,6 +807,39 @@ inline int built_layout(seg_build_fn build, bcn_env_t h, bcn_snapshot_seg* segs,
   return nd < 0 ? 0 : nd;
 }
 
+// The rollout buffer of this handle for T steps (rollout.h): the same, with the two arguments the layout depends on besides the
+// handle.  `who`: the entry point, for the message.  The actions are int32 [B] for the discrete envs and real [B][n_act] otherwise.
+inline bool rollout_int_actions(bcn_env_t h) { return h->kind == BCN_MIXING || h->kind == BCN_LORENZ; }
+int rollout_build(const char* who, bcn_env_t h, int T, int flags, bcn_snapshot_seg* lay, int max_lay, size_t* bytes) {
+  if (T < 1 || T > 0x3fffffff) { bcn_set_error("%s: T = %d steps; at least 1", who, T); return -1; }
+  if (flags & ~(BCN_RO_FINAL_OBS | BCN_RO_JETS)) { bcn_set_error("%s: unknown flags %#x", who, flags); return -1; }
+  if ((flags & BCN_RO_JETS) && h->kind != BCN_SHKADOV) { bcn_set_error("%s: BCN_RO_JETS needs a BCN_SHKADOV env", who); return -1; }
+  const size_t B = (size_t)h->batch;
+  const size_t widest = (size_t)(h->n_obs > h->n_act ? h->n_obs : h->n_act);
+  if (h->batch < 1 || h->n_obs < 1 || h->n_act < 1 || B * widest * h->esz / 4 > 0x7fffffffull) {
+    bcn_set_error("%s: batch %d x %d observations is outside what one launch covers", who, h->batch, h->n_obs);
+    return -1;
+  }
+  SegDesc d[BCN_RO_NSEG];
+  const bool ia = rollout_int_actions(h);
+  rollout_segs(T, (size_t)h->n_obs, ia ? BCN_SNAP_I32 : BCN_SNAP_REAL, ia ? 1 : (size_t)h->n_act, (size_t)h->n_act, flags, d);
+  const size_t total = seg_layout(d, BCN_RO_NSEG, B, h->esz, lay, max_lay);
+  if (bytes) *bytes = total;
+  return BCN_RO_NSEG;
+}
+// one row copy of a record or a begin: rows of `row` bytes of B replicas, `blk` = the copy workgroups in front of it (advanced)
+RolloutJob rollout_job(const char* src, char* dst, size_t B, size_t row, int when, int slot_off, unsigned* blk) {
+  RolloutJob j;
+  j.src = src; j.dst = dst; j.slot_bytes = (unsigned long long)(B * row);
+  j.unit = copy_unit(row);      // rows are reals or int32: multiples of 4 bytes
+  j.upr = (unsigned)(row / j.unit);
+  j.total = (unsigned)(B * j.upr);
+  j.blk0 = *blk;
+  j.when = when; j.slot_off = slot_off;
+  *blk += (j.total + BCN_RO_NT * BCN_RO_UPL - 1) / (BCN_RO_NT * BCN_RO_UPL);
+  return j;
+}
+
 // bcn_shkadov_jet_rewards of a checked shkadov handle: the film and the jet layout come from the handle's argument block, the
 // replica mask is the one bcn_set_mask left there, status / done / trunc are those of the step's packed outputs
 template <typename real>
@@ -1316,6 +1350,119 @@ int bcn_normalize(bcn_env_t h, const void* out_buf_dev, void* norm_buf_dev, cons
   a.gamma = gamma; a.eps = eps; a.clip_obs = clip_obs; a.clip_rwd = clip_rwd;
   DeviceGuard g(h->device);
   return normalize_launch(a, static_cast<hipStream_t>(stream));
+}
+// ---- rollout storage and generalised advantage estimation (rollout.h) -----------------------------
+size_t bcn_rollout_bytes(bcn_env_t h, int T, int flags) {
+  if (!h) { bcn_set_error("bcn_rollout_bytes: null handle"); return 0; }
+  size_t bytes = 0;
+  return rollout_build("bcn_rollout_bytes", h, T, flags, nullptr, 0, &bytes) < 0 ? 0 : bytes;
+}
+int bcn_rollout_layout(bcn_env_t h, int T, int flags, bcn_snapshot_seg* segs, int max_segs) {
+  if (!h || (max_segs > 0 && !segs)) { bcn_set_error("bcn_rollout_layout: null handle/array"); return 0; }
+  const int nd = rollout_build("bcn_rollout_layout", h, T, flags, segs, max_segs, nullptr);
+  return nd < 0 ? 0 : nd;
+}
+int bcn_rollout_begin(bcn_env_t h, void* ro_buf_dev, const void* out_buf_dev, const void* norm_buf_dev, void* stream) {
+  if (!h || !ro_buf_dev || !out_buf_dev) { bcn_set_error("bcn_rollout_begin: null handle/buffer"); return BCN_ERR_ARG; }
+  if (!snap_ptr_ok(ro_buf_dev) || !snap_ptr_ok(out_buf_dev) || !snap_ptr_ok(norm_buf_dev)) {
+    bcn_set_error("bcn_rollout_begin: buffers must be 16-byte aligned");
+    return BCN_ERR_ARG;
+  }
+  bcn_snapshot_seg lay[BCN_RO_NSEG], nl[BCN_NRM_NSEG];
+  if (rollout_build("bcn_rollout_begin", h, 1, 0, lay, BCN_RO_NSEG, nullptr) < 0) return BCN_ERR_ARG;   // cursor and obs sit in front of whatever T scales
+  if (norm_buf_dev && normalize_build(h, nl, BCN_NRM_NSEG, nullptr) < 0) return BCN_ERR_ARG;
+  const size_t B = (size_t)h->batch, row = (size_t)h->n_obs * h->esz;
+  char* ro = static_cast<char*>(ro_buf_dev);
+  const char* obs = norm_buf_dev ? static_cast<const char*>(norm_buf_dev) + nl[NRM_NORM_OBS].offset
+                                 : static_cast<const char*>(out_buf_dev) + bcn_out_layout(B, (size_t)h->n_obs, h->esz).obs;
+  unsigned blk = 0;
+  const RolloutJob j = rollout_job(obs, ro + lay[RO_OBS].offset, B, row, RO_COPY_ALWAYS, 0, &blk);
+  DeviceGuard g(h->device);
+  return rollout_begin_launch(reinterpret_cast<int32_t*>(ro + lay[RO_CURSOR].offset), j, static_cast<hipStream_t>(stream));
+}
+int bcn_rollout_record(bcn_env_t h, const void* out_buf_dev, void* ro_buf_dev, const void* act_dev, const void* ep_buf_dev,
+                       const void* norm_buf_dev, const void* jets_buf_dev, const uint8_t* mask_dev, int T, int flags, void* stream) {
+  if (!h || !out_buf_dev || !ro_buf_dev) { bcn_set_error("bcn_rollout_record: null handle/buffer"); return BCN_ERR_ARG; }
+  if (!snap_ptr_ok(out_buf_dev) || !snap_ptr_ok(ro_buf_dev) || !snap_ptr_ok(ep_buf_dev) || !snap_ptr_ok(norm_buf_dev) ||
+      !snap_ptr_ok(jets_buf_dev)) {
+    bcn_set_error("bcn_rollout_record: buffers must be 16-byte aligned");
+    return BCN_ERR_ARG;
+  }
+  if ((reinterpret_cast<uintptr_t>(act_dev) & 3) != 0) { bcn_set_error("bcn_rollout_record: actions must be 4-byte aligned"); return BCN_ERR_ARG; }
+  bcn_snapshot_seg lay[BCN_RO_NSEG], el[BCN_EP_NSEG], nl[BCN_NRM_NSEG], jl[BCN_JETS_NSEG];
+  if (rollout_build("bcn_rollout_record", h, T, flags, lay, BCN_RO_NSEG, nullptr) < 0) return BCN_ERR_ARG;
+  if (jets_buf_dev && !(flags & BCN_RO_JETS)) { bcn_set_error("bcn_rollout_record: a per-jet buffer without BCN_RO_JETS"); return BCN_ERR_ARG; }
+  if (ep_buf_dev && episode_build(h, el, BCN_EP_NSEG, nullptr) < 0) return BCN_ERR_ARG;
+  if (norm_buf_dev && normalize_build(h, nl, BCN_NRM_NSEG, nullptr) < 0) return BCN_ERR_ARG;
+  if (jets_buf_dev && jets_build(h, jl, BCN_JETS_NSEG, nullptr) < 0) return BCN_ERR_ARG;
+  const size_t B = (size_t)h->batch, n = (size_t)h->n_obs, esz = h->esz;
+  const bcn_out_layout_t o = bcn_out_layout(B, n, esz);
+  const char* out = static_cast<const char*>(out_buf_dev);
+  const char* ep = static_cast<const char*>(ep_buf_dev);
+  const char* nb = static_cast<const char*>(norm_buf_dev);
+  char* ro = static_cast<char*>(ro_buf_dev);
+  RolloutRecordArgs a;
+  a.cursor = reinterpret_cast<int32_t*>(ro + lay[RO_CURSOR].offset);
+  a.rwd = nb ? nb + nl[NRM_NORM_RWD].offset : out + o.rwd;
+  a.status = reinterpret_cast<const int32_t*>(out + o.status);
+  a.done = reinterpret_cast<const uint8_t*>(out + o.done); a.trunc = reinterpret_cast<const uint8_t*>(out + o.trunc);
+  a.mask = mask_dev;
+  a.finished = ep ? reinterpret_cast<const uint8_t*>(ep + el[EP_FINISHED].offset) : nullptr;
+  a.d_rwd = ro + lay[RO_RWD].offset; a.d_status = reinterpret_cast<int32_t*>(ro + lay[RO_STATUS].offset);
+  a.d_done = reinterpret_cast<uint8_t*>(ro + lay[RO_DONE].offset); a.d_trunc = reinterpret_cast<uint8_t*>(ro + lay[RO_TRUNC].offset);
+  a.d_valid = reinterpret_cast<uint8_t*>(ro + lay[RO_VALID].offset);
+  unsigned blk = 0, nj = 0;
+  const char* obs = nb ? nb + nl[NRM_NORM_OBS].offset : out + o.obs;
+  a.job[nj++] = rollout_job(obs, ro + lay[RO_OBS].offset, B, n * esz, RO_COPY_ALWAYS, 1, &blk);
+  if (ep && (flags & BCN_RO_FINAL_OBS)) {
+    const char* fo = nb ? nb + nl[NRM_NORM_FINAL_OBS].offset : ep + el[EP_FINAL_OBS].offset;
+    a.job[nj++] = rollout_job(fo, ro + lay[RO_FINAL_OBS].offset, B, n * esz, RO_COPY_FINISHED, 0, &blk);
+  }
+  const size_t act_row = rollout_int_actions(h) ? 4 : (size_t)h->n_act * esz;
+  a.job[nj++] = rollout_job(static_cast<const char*>(act_dev), ro + lay[RO_ACT].offset, B, act_row, RO_COPY_STEPPED, 0, &blk);
+  if (jets_buf_dev)
+    a.job[nj++] = rollout_job(static_cast<const char*>(jets_buf_dev) + jl[JETS_RWD_JETS].offset, ro + lay[RO_RWD_JETS].offset, B,
+                              (size_t)h->n_act * esz, RO_COPY_ALWAYS, 0, &blk);
+  for (; nj < BCN_RO_NJOB; nj++) {               // off: no workgroup reaches it
+    a.job[nj] = RolloutJob{};
+    a.job[nj].blk0 = blk;
+  }
+  a.batch = (unsigned)B;
+  a.nbk = (unsigned)((B + BCN_RO_NT - 1) / BCN_RO_NT);
+  a.ncp = blk;
+  a.T = T;
+  a.f64 = h->dtype == BCN_F64;
+  DeviceGuard g(h->device);
+  return rollout_record_launch(a, static_cast<hipStream_t>(stream));
+}
+int bcn_rollout_gae(bcn_env_t h, void* ro_buf_dev, const void* values_dev, const void* last_value_dev, const void* final_values_dev,
+                    int T, int flags, int cols, double gamma, double lam, void* stream) {
+  if (!h || !ro_buf_dev || !values_dev || !last_value_dev) { bcn_set_error("bcn_rollout_gae: null handle/buffer"); return BCN_ERR_ARG; }
+  if (!snap_ptr_ok(ro_buf_dev)) { bcn_set_error("bcn_rollout_gae: buffers must be 16-byte aligned"); return BCN_ERR_ARG; }
+  bcn_snapshot_seg lay[BCN_RO_NSEG];
+  if (rollout_build("bcn_rollout_gae", h, T, flags, lay, BCN_RO_NSEG, nullptr) < 0) return BCN_ERR_ARG;
+  if (cols != 1 && !((flags & BCN_RO_JETS) && cols == h->n_act)) {
+    bcn_set_error("bcn_rollout_gae: cols = %d; 1, or the jet count with BCN_RO_JETS", cols);
+    return BCN_ERR_ARG;
+  }
+  if (!(gamma >= 0.0 && gamma <= 1.0) || !(lam >= 0.0 && lam <= 1.0)) {
+    bcn_set_error("bcn_rollout_gae: gamma %g and lam %g must lie in [0, 1]", gamma, lam);
+    return BCN_ERR_ARG;
+  }
+  char* ro = static_cast<char*>(ro_buf_dev);
+  RolloutGaeArgs a;
+  a.cursor = reinterpret_cast<const int32_t*>(ro + lay[RO_CURSOR].offset);
+  a.rwd = ro + lay[cols == 1 ? RO_RWD : RO_RWD_JETS].offset;
+  a.done = reinterpret_cast<const uint8_t*>(ro + lay[RO_DONE].offset); a.trunc = reinterpret_cast<const uint8_t*>(ro + lay[RO_TRUNC].offset);
+  a.valid = reinterpret_cast<const uint8_t*>(ro + lay[RO_VALID].offset);
+  a.values = values_dev; a.last_value = last_value_dev; a.final_values = final_values_dev;
+  a.adv = ro + lay[RO_ADV].offset; a.ret = ro + lay[RO_RET].offset;
+  a.batch = (unsigned)h->batch; a.cols = (unsigned)cols; a.ncols = a.batch * a.cols;
+  a.T = T;
+  a.f64 = h->dtype == BCN_F64;
+  a.gamma = gamma; a.lam = lam;
+  DeviceGuard g(h->device);
+  return rollout_gae_launch(a, static_cast<hipStream_t>(stream));
 }
 const char* bcn_kernel_name(bcn_env_t h) { return h ? h->kernel_name() : ""; }
 int bcn_kernel_shape(bcn_env_t h, int* cells_per_thread, int* threads) {

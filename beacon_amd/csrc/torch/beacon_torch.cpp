@@ -6,6 +6,11 @@
 //   beacon::shkadov_jet_rewards(int handle, Tensor out_buf, Tensor jets_buf, int with_stats) -> ()
 //   beacon::normalize(int handle, Tensor out_buf, Tensor norm_buf, Tensor? ep_buf, Tensor? mask, int kind, int training, float gamma, float eps,
 //                     float clip_obs, float clip_rwd) -> ()
+//   beacon::rollout_begin(int handle, Tensor ro_buf, Tensor out_buf, Tensor? norm_buf) -> ()
+//   beacon::rollout_record(int handle, Tensor out_buf, Tensor ro_buf, Tensor? act, Tensor? ep_buf, Tensor? norm_buf, Tensor? jets_buf, Tensor? mask,
+//                          int T, int flags) -> ()
+//   beacon::rollout_gae(int handle, Tensor ro_buf, Tensor values, Tensor last_value, Tensor? final_values, int T, int flags, int cols, float gamma,
+//                       float lam) -> ()
 // Each op is ONE dispatcher call that takes device tensors, reads torch's current HIP stream in C++ and forwards to the
 // bcn_* entry point of libbeacon_hip.so -- no ctypes marshalling, no Python-side stream query (what the per-call host cost of
 // the ctypes binding was made of: scripts/host_cost.py), and an op CUDA-graph capture and fake-tensor tracing can see (Meta kernels below).  The ops
@@ -245,6 +250,59 @@ void normalize(int64_t h_, const Tensor& out_buf, const Tensor& norm_buf, OptT e
   check(bcn_normalize(h, o, n, e, m, (int)kind, training != 0, gamma, eps, clip_obs, clip_rwd, stream_of(norm_buf)), "bcn_normalize");
 }
 
+// ---- rollout storage and GAE (include/beacon_hip.h: bcn_rollout_begin / bcn_rollout_record / bcn_rollout_gae) --------------
+// the rollout buffer of T steps under `flags`: its exact size, with the message of the library for a T or flags it refuses
+inline uint8_t* rollout_buf(const Tensor& t, bcn_env_t h, int64_t T, int64_t flags) {
+  TORCH_CHECK(h, "rollout: null handle");
+  TORCH_CHECK(T >= 1 && T <= INT32_MAX && flags >= 0 && flags <= INT32_MAX, "rollout: T = ", T, ", flags = ", flags);
+  const size_t n = bcn_rollout_bytes(h, (int)T, (int)flags);
+  TORCH_CHECK(n > 0, "libbeacon_hip: ", bcn_last_error());
+  return bytes_of(t, h, (int64_t)n, "ro_buf");
+}
+void rollout_begin(int64_t h_, const Tensor& ro_buf, const Tensor& out_buf, OptT norm_buf) {
+  bcn_env_t h = H(h_);
+  TORCH_CHECK(h, "rollout_begin: null handle");
+  on_device(ro_buf, h, "ro_buf");                // T is not known here: at least the cursor and obs[0], obs[1] (T = 1, no flags)
+  TORCH_CHECK(ro_buf.scalar_type() == at::kByte && ro_buf.numel() >= (int64_t)bcn_rollout_bytes(h, 1, 0), "ro_buf: uint8 tensor of at least ",
+              bcn_rollout_bytes(h, 1, 0), " bytes expected");
+  const uint8_t* o = bytes_of(out_buf, h, out_buf_bytes(h), "out_buf");
+  const uint8_t* n = norm_buf.has_value() ? bytes_of(*norm_buf, h, (int64_t)bcn_normalize_bytes(h), "norm_buf") : nullptr;
+  check(bcn_rollout_begin(h, ro_buf.data_ptr(), o, n, stream_of(ro_buf)), "bcn_rollout_begin");
+}
+void rollout_record(int64_t h_, const Tensor& out_buf, const Tensor& ro_buf, OptT act, OptT ep_buf, OptT norm_buf, OptT jets_buf, OptT mask,
+                    int64_t T, int64_t flags) {
+  bcn_env_t h = H(h_);
+  uint8_t* r = rollout_buf(ro_buf, h, T, flags);
+  const uint8_t* o = bytes_of(out_buf, h, out_buf_bytes(h), "out_buf");
+  const void* a = nullptr;
+  if (act.has_value()) {                         // element type and row length: those of the act segment
+    bcn_snapshot_seg lay[3];
+    TORCH_CHECK(bcn_rollout_layout(h, (int)T, (int)flags, lay, 3) > 0, "libbeacon_hip: ", bcn_last_error());
+    a = lay[2].elem == BCN_SNAP_I32 ? static_cast<const void*>(i32(*act, h, lay[2].row_elems, "act")) : dpr(act, h, lay[2].row_elems, "act");
+  }
+  const uint8_t* e = ep_buf.has_value() ? bytes_of(*ep_buf, h, (int64_t)bcn_episode_bytes(h), "ep_buf") : nullptr;
+  const uint8_t* n = norm_buf.has_value() ? bytes_of(*norm_buf, h, (int64_t)bcn_normalize_bytes(h), "norm_buf") : nullptr;
+  const uint8_t* j = nullptr;
+  if (jets_buf.has_value()) {
+    TORCH_CHECK(bcn_env_kind(h) == BCN_SHKADOV, "jets_buf: the handle is not a shkadov env");
+    j = bytes_of(*jets_buf, h, (int64_t)bcn_shkadov_jets_bytes(h), "jets_buf");
+  }
+  const uint8_t* m = mask.has_value() ? u8(*mask, h, 1, "mask") : nullptr;
+  check(bcn_rollout_record(h, o, r, a, e, n, j, m, (int)T, (int)flags, stream_of(ro_buf)), "bcn_rollout_record");
+}
+void rollout_gae(int64_t h_, const Tensor& ro_buf, const Tensor& values, const Tensor& last_value, OptT final_values, int64_t T, int64_t flags,
+                 int64_t cols, double gamma, double lam) {
+  bcn_env_t h = H(h_);
+  uint8_t* r = rollout_buf(ro_buf, h, T, flags);
+  TORCH_CHECK(cols == 1 || ((flags & BCN_RO_JETS) && cols == bcn_n_act(h)), "cols: ", cols, "; 1, or the jet count with BCN_RO_JETS");
+  rows(values, h, T * cols, "values");
+  rows(last_value, h, cols, "last_value");
+  if (final_values.has_value()) rows(*final_values, h, T * cols, "final_values");
+  check(bcn_rollout_gae(h, r, dp(values, h, true, "values"), dp(last_value, h, true, "last_value"), dpo(final_values, h, true, "final_values"),
+                        (int)T, (int)flags, (int)cols, gamma, lam, stream_of(ro_buf)),
+        "bcn_rollout_gae");
+}
+
 // Meta (fake-tensor) kernels: the ops return nothing and their outputs keep their shapes, so tracing needs no more than this.
 void reset2_meta(int64_t, const Tensor&) {}
 void reset3_meta(int64_t, OptT, const Tensor&) {}
@@ -258,6 +316,9 @@ void snapshot_load_meta(int64_t, const Tensor&, int64_t, OptT, OptT, const Tenso
 void episode_track_meta(int64_t, const Tensor&, const Tensor&, OptT) {}
 void shkadov_jet_rewards_meta(int64_t, const Tensor&, const Tensor&, int64_t) {}
 void normalize_meta(int64_t, const Tensor&, const Tensor&, OptT, OptT, int64_t, int64_t, double, double, double, double) {}
+void rollout_begin_meta(int64_t, const Tensor&, const Tensor&, OptT) {}
+void rollout_record_meta(int64_t, const Tensor&, const Tensor&, OptT, OptT, OptT, OptT, OptT, int64_t, int64_t) {}
+void rollout_gae_meta(int64_t, const Tensor&, const Tensor&, const Tensor&, OptT, int64_t, int64_t, int64_t, double, double) {}
 
 }  // namespace
 
@@ -292,6 +353,11 @@ TORCH_LIBRARY(beacon, m) {
   m.def("shkadov_jet_rewards(int handle, Tensor out_buf, Tensor(a!) jets_buf, int with_stats) -> ()");
   m.def("normalize(int handle, Tensor out_buf, Tensor(a!) norm_buf, Tensor? ep_buf, Tensor? mask, int kind, int training, float gamma, "
         "float eps, float clip_obs, float clip_rwd) -> ()");
+  m.def("rollout_begin(int handle, Tensor(a!) ro_buf, Tensor out_buf, Tensor? norm_buf) -> ()");
+  m.def("rollout_record(int handle, Tensor out_buf, Tensor(a!) ro_buf, Tensor? act, Tensor? ep_buf, Tensor? norm_buf, Tensor? jets_buf, "
+        "Tensor? mask, int T, int flags) -> ()");
+  m.def("rollout_gae(int handle, Tensor(a!) ro_buf, Tensor values, Tensor last_value, Tensor? final_values, int T, int flags, int cols, "
+        "float gamma, float lam) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(beacon, CUDA, m) {
@@ -315,6 +381,9 @@ TORCH_LIBRARY_IMPL(beacon, CUDA, m) {
   m.impl("episode_track", &episode_track);
   m.impl("shkadov_jet_rewards", &shkadov_jet_rewards);
   m.impl("normalize", &normalize);
+  m.impl("rollout_begin", &rollout_begin);
+  m.impl("rollout_record", &rollout_record);
+  m.impl("rollout_gae", &rollout_gae);
 }
 
 TORCH_LIBRARY_IMPL(beacon, Meta, m) {
@@ -338,4 +407,7 @@ TORCH_LIBRARY_IMPL(beacon, Meta, m) {
   m.impl("episode_track", &episode_track_meta);
   m.impl("shkadov_jet_rewards", &shkadov_jet_rewards_meta);
   m.impl("normalize", &normalize_meta);
+  m.impl("rollout_begin", &rollout_begin_meta);
+  m.impl("rollout_record", &rollout_record_meta);
+  m.impl("rollout_gae", &rollout_gae_meta);
 }

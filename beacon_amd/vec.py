@@ -101,6 +101,7 @@ _WARM_OPS = ("shkadov_reset_random",)                                         # 
 _JET_OPS = ("shkadov_jet_rewards",)                                           # shkadov (csrc/shkadov_jets.hip)
 _ALL_OPS = _OPS + _ODE_OPS + _STATE_OPS + _EPISODE_OPS + _WARM_OPS + _JET_OPS
 _NORM_OPS = ("normalize",)                                                    # every env (csrc/normalize.hip)
+_ROLLOUT_OPS = ("rollout_begin", "rollout_record", "rollout_gae")             # every env (csrc/rollout.hip); resolved at the first attach
 
 
 def _op_table():
@@ -113,6 +114,17 @@ def _op_table():
 def _c_table(lib):
     """{name: bcn_<name> of libbeacon_hip.so}: the same entry points through ctypes, resolved once per env."""
     return {n: getattr(lib, "bcn_" + n) for n in _ALL_OPS + _NORM_OPS}
+
+
+def _rollout_tables(lib, with_ops):
+    """({name: torch op} or None, {name: bcn_<name>}) of _ROLLOUT_OPS: kept out of _op_table / _c_table, merged into an env's tables
+    when a rollout is first attached (VecEnv.rollout)."""
+    ops = None
+    if with_ops:
+        from . import torch_ext
+        ext = torch_ext.load()
+        ops = None if ext is None else {n: getattr(ext, n).default for n in _ROLLOUT_OPS}
+    return ops, {n: getattr(lib, "bcn_" + n) for n in _ROLLOUT_OPS}
 
 
 class Snapshot(object):
@@ -174,10 +186,11 @@ class _SegBuffer(object):
     NAMES, C_FUNCS, ROWS_2D = (), (), ()
     SHAPE_KEY, NOUN = "obs_dim", "observations"
 
-    def __init__(self, env):
+    def __init__(self, env, layout_args=()):
+        """layout_args: what the pair takes between the handle and the segment array besides (Rollout: T, flags)."""
         segs = (_lib.SnapshotSeg * 16)()
-        k = getattr(env.lib, self.C_FUNCS[0])(env.h, segs, 16)
-        nbytes = getattr(env.lib, self.C_FUNCS[1])(env.h)
+        k = getattr(env.lib, self.C_FUNCS[0])(env.h, *(tuple(layout_args) + (segs, 16)))
+        nbytes = getattr(env.lib, self.C_FUNCS[1])(env.h, *layout_args)
         if k != len(self.NAMES) or nbytes == 0:
             raise _lib.BeaconHipError("libbeacon_hip: %s" % env.lib.bcn_last_error().decode())
         self.batch, self.tdtype = env.batch, env.tdtype
@@ -309,6 +322,126 @@ class Normalizer(_SegBuffer):
         return self
 
 
+class RolloutOverflow(RuntimeError):
+    """A step was recorded into a Rollout that already held its T steps (Rollout.check)."""
+
+
+class Rollout(_SegBuffer):
+    """The transitions of up to T steps of one VecEnv, kept on the device by the launch that follows every step while the rollout
+    is attached (VecEnv.rollout; csrc/rollout.hip), and the advantages and returns computed from them (compute_gae): `buf`, one
+    uint8 tensor in the layout of bcn_rollout_layout (include/beacon_hip.h), and typed no-copy views of its segments:
+      cursor     int32 [4]: [0] steps recorded so far, [1] sticky overflow flag
+      obs        [T + 1, B, obs_dim]: obs[0] from begin(); step t writes obs[t + 1] = what the step returned (post-reset rows under
+                 step_autoreset; norm_obs while normalising)
+      act        [T, B, act_dim] in the env dtype, or int32 [T, B] for the discrete envs: the actions handed to the step (a step
+                 called with actions=None records zeros)
+      rwd        [T, B] (norm_rwd while normalising); status int32 [T, B]; done, trunc uint8 [T, B]: the terminal step's
+      valid      uint8 [T, B]: 1 where the replica was stepped (no mask, or mask byte != 0)
+      final_obs  [T, B, obs_dim] (final_obs=True; else [T, B, 0]): under step_autoreset, rows where episodes.finished hold the
+                 terminal observation (norm_final_obs while normalising); the other rows are left as they are
+      rwd_jets   [T, B, n_jets] for a VecShkadov with set_jet_rewards() on at attach time (else [T, B, 0])
+      adv, ret   [T, B cols], written by compute_gae
+    The slot a step writes comes from `cursor` on the device, never from the host: an eager loop, a one-step graph replayed T
+    times and a T-step graph are the same launches and fill slots 0 .. T - 1.  A record into a full rollout writes no slot and
+    raises the overflow flag, which check() reports.  A replica a mask skips gets valid = 0, rwd = 0, done = trunc = 0; its
+    obs[t + 1] row is its unchanged current row; its act and final_obs rows are not written.
+    Bookkeeping (_SegBuffer): in no Snapshot, snapshot_signature() unchanged, restore() / fork() leave it alone.  Not covered:
+    ShardedVecEnv and the single-env mirrors (beacon_amd/envs.py), as for the other bookkeeping buffers."""
+
+    NAMES = ("cursor", "obs", "act", "rwd", "status", "done", "trunc", "valid", "final_obs", "rwd_jets", "adv", "ret")
+    C_FUNCS = ("bcn_rollout_layout", "bcn_rollout_bytes")
+    ROWS_2D = ("obs", "act", "final_obs", "rwd_jets")        # [planes, B, row_elems] also where a row is one element long
+
+    def __init__(self, env, T, final_obs=True):
+        import weakref
+        if isinstance(T, bool) or not isinstance(T, (int, np.integer)) or int(T) < 1:
+            raise ValueError("Rollout: T must be an integer >= 1, got %r" % (T,))
+        self.T = int(T)
+        jets = bool(getattr(env, "_jets_on", False))
+        self.flags = (_lib.RO_FINAL_OBS if final_obs else 0) | (_lib.RO_JETS if jets else 0)
+        self.n_jets = int(env.n_actions) if jets else 0
+        self._env = weakref.ref(env)
+        super().__init__(env, (self.T, self.flags))
+
+    def view(self, name):
+        """Typed view (no copy) of one segment, the step axis in front; KeyError for an unknown name.  "adv" / "ret": as the last
+        compute_gae laid them out ([T, B] before the first)."""
+        if name in ("adv", "ret"):
+            return self.gae_views(getattr(self, "cols", 1))[name == "ret"]
+        seg, v = _seg_view(self.buf, self.layout, name, self.batch, self.tdtype, self.ROWS_2D)
+        if not seg["planes"]:
+            return v
+        if name in self.ROWS_2D and seg["elem"] == _lib.SNAP_REAL:
+            return v.view(int(seg["planes"]), self.batch, int(seg["row_elems"]))
+        return v.view(int(seg["planes"]), self.batch)
+
+    def gae_views(self, cols=1):
+        """(adv, ret) as [T, B cols] views: where compute_gae with that many columns per replica writes them (cols: 1, or n_jets
+        for per_jet=True)."""
+        out = []
+        for name in ("adv", "ret"):
+            v = _seg_view(self.buf, self.layout, name, self.batch, self.tdtype)[1].reshape(-1)
+            out.append(v[:self.T * self.batch * cols].view(self.T, self.batch * cols))
+        return tuple(out)
+
+    def clear(self):
+        """Zero every segment, the cursor included.  No host synchronisation."""
+        self.buf.zero_()
+        return self
+
+    def begin(self):
+        """Start a rollout: cursor = 0, overflow = 0, obs[0] = what the env's reset() / step() currently return (norm_obs while
+        normalising).  ONE launch, no host synchronisation; it can be captured.  The other segments keep their contents and are
+        overwritten slot by slot.  Returns self."""
+        env = self._env()
+        if env is None:
+            raise RuntimeError("Rollout.begin: the env of this rollout is gone")
+        env._call("rollout_begin", self.buf, env.out_buf, env._norm.buf if env._norm_on else None)
+        return self
+
+    def check(self):
+        """The one host read: (steps recorded, False); raises RolloutOverflow when a step was recorded into the full rollout
+        (that step wrote nothing; begin() clears the flag)."""
+        n, over = self.cursor[:2].cpu().tolist()
+        if over:
+            raise RolloutOverflow("Rollout.check: a step was recorded behind the last of %d slots (it wrote nothing); begin() starts over" % self.T)
+        return int(n), False
+
+    def compute_gae(self, values, last_value, final_values=None, gamma=0.99, lam=0.95, per_jet=False):
+        """Generalised advantage estimation over the recorded steps, ONE launch with a lane per column (csrc/rollout.hip), no host
+        synchronisation.  values [T, B cols], last_value [B cols], final_values [T, B cols] or None: contiguous device tensors of
+        the env dtype (any shape with those element counts); cols = 1, or n_jets with per_jet=True (which needs the rwd_jets
+        segment and takes the rewards from it).  The number of recorded steps n is read from the cursor on the device; rows
+        t >= n of adv / ret are not written.  Per column, t = n - 1 .. 0, nv = last_value, gae = 0:
+          valid = 0:  adv = 0, ret = values[t]; nv and gae pass through (a skipped step is transparent)
+          else        fin = done | trunc; boot = final_values[t] if final_values is given and trunc is set, else 0 (the time limit
+                      sets done = trunc = 1 and bootstraps; shkadov's blow-up sets done alone and is terminal);
+                      delta = rwd[t] + gamma (boot if fin else nv) - values[t]; gae = delta + (0 if fin else gamma lam gae);
+                      adv[t] = gae, ret[t] = gae + values[t], nv = values[t]
+        in float64 whatever the env dtype, rounded once on store.  Only rows of final_values where trunc is set are used: the others may hold anything.
+        ValueError for a wrong shape, dtype or device.  Returns (adv, ret), [T, B cols] views that `adv` / `ret` name from then on."""
+        env = self._env()
+        if env is None:
+            raise RuntimeError("Rollout.compute_gae: the env of this rollout is gone")
+        if per_jet and not self.flags & _lib.RO_JETS:
+            raise ValueError("Rollout.compute_gae: per_jet=True needs the rwd_jets segment (set_jet_rewards() on when the rollout is attached)")
+        cols = self.n_jets if per_jet else 1
+        n = self.batch * cols
+        for name, t, numel in (("values", values, self.T * n), ("last_value", last_value, n), ("final_values", final_values, self.T * n)):
+            if t is None and name == "final_values":
+                continue
+            if (not torch.is_tensor(t) or t.dtype != self.tdtype or t.device != self.buf.device or t.numel() != numel
+                    or not t.is_contiguous()):
+                raise ValueError("Rollout.compute_gae: %s must be a contiguous %s tensor of %d elements on %s"
+                                 % (name, dtype_name(self.tdtype), numel, self.buf.device))
+        if not (0.0 <= float(gamma) <= 1.0 and 0.0 <= float(lam) <= 1.0):
+            raise ValueError("Rollout.compute_gae: gamma and lam must lie in [0, 1]")
+        env._call("rollout_gae", self.buf, values, last_value, final_values, self.T, self.flags, cols, float(gamma), float(lam))
+        self.cols = cols
+        self.adv, self.ret = self.gae_views(cols)
+        return self.adv, self.ret
+
+
 class ParamsWarning(UserWarning):
     """A 2D env whose default kernel is a register-resident one received per-replica parameters: it steps through the generic
     kernel until clear_params() (VecEnv.set_params).  set_params_kernel("fast") on the env selects the register-resident kernels
@@ -326,6 +459,8 @@ class VecEnv(object):
     _norm = None             # set_normalize: the Normalizer, allocated by the first call and kept
     _norm_on = False         # ... whether the normalising launches follow every reset and step
     _mask = None             # the replica mask in force in the library (_apply_mask, _masked); None: none
+    _rollout = None          # rollout: the Rollout attached (a recording launch follows every step); None: none, nothing extra runs
+    _rollout_kept = None     # ... the last one allocated, kept across rollout(None)
 
     def __init__(self, batch, device="cuda:0", dtype="f32"):
         if not torch.cuda.is_available():
@@ -400,7 +535,7 @@ class VecEnv(object):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _call(self, name, *args):
-        """The entry point `name` (one of _OPS, _ODE_OPS, _STATE_OPS, _EPISODE_OPS, _WARM_OPS, _JET_OPS, _NORM_OPS) through the binding in force: the torch op, or
+        """The entry point `name` (one of _OPS, _ODE_OPS, _STATE_OPS, _EPISODE_OPS, _WARM_OPS, _JET_OPS, _NORM_OPS, _ROLLOUT_OPS) through the binding in force: the torch op, or
         bcn_<name> through ctypes.  `args`: what both take between the handle and the stream, in their common order -- tensors
         (None: a null pointer), ints and floats; the op reads torch's current stream itself, ctypes gets it appended."""
         if self._ops is not None:
@@ -631,6 +766,8 @@ class VecEnv(object):
         """Switch this env between the two bindings of the C ABI: the torch.library ops (default when the extension is built)
         and ctypes.  Returns whether the ops are in use.  Results do not depend on it (tests/test_gpu_parity.py)."""
         self._ops = _op_table() if on else None
+        if self._rollout_kept is not None:
+            self._merge_rollout_ops()
         return self._ops is not None
 
     def set_option(self, name, value):
@@ -798,7 +935,8 @@ class VecEnv(object):
           1. the step kernel;
           2. _after_step: the per-jet rewards read the film, so they come in front of the masked reset, which overwrites it;
           3. with `ep`: the bookkeeping launch and the env's own reset under ep.finished (the caller's _masked clears that mask);
-          4. the normalisation LAST: it counts the reset rows of obs, and normalises ep.final_obs without counting it."""
+          4. the normalisation LAST: it counts the reset rows of obs, and normalises ep.final_obs without counting it;
+          5. with a rollout attached (rollout), the recording launch behind all of them: it stores what the step returns."""
         self._step(actions, noise)
         self._after_step()
         if ep is not None:
@@ -806,6 +944,9 @@ class VecEnv(object):
             self._reset_finished(ep)
         if self._norm_on:
             self._normalize("step", stepped, ep)
+        if self._rollout is not None:
+            self._record(self._rollout, stepped, ep)
+        if self._norm_on:
             return self._norm.norm_obs, self._norm.norm_rwd, self.done, self.trunc, ep
         return self.obs, self.rwd, self.done, self.trunc, ep
 
@@ -864,6 +1005,57 @@ class VecEnv(object):
         if self._rotate:
             self._next_outputs(carry=mask is not None)
         return self._masked(mask, lambda m: self._enqueue_step(actions, noise, m, ep))
+
+    # -- rollout storage --------------------------------------------------------------------
+    def rollout(self, T, final_obs=True):
+        """Attach on-device rollout storage for T steps and return it (Rollout; csrc/rollout.hip).  While attached, step(),
+        step_autoreset() and every step a capture() records enqueue ONE recording launch (and the one lane that advances the
+        cursor) LAST -- behind the masked reset and the normalisation -- which stores the step's observations, actions, reward,
+        status, flags, validity and, under step_autoreset() with final_obs=True, the terminal observations of the replicas that
+        finished, into the slot the device cursor names; reset() records nothing.  No host synchronisation, nothing allocated
+        after the attach.  The loop:
+            ro = env.rollout(T); ro.begin()
+            for t in range(T): env.step_autoreset(policy(ro.obs[t]))
+            ro.compute_gae(critic(ro.obs)[:-1], critic(ro.obs)[-1], final_values=critic(ro.final_obs))
+        Unlike episodes.final_obs, which keeps the LAST terminal observation of a replica, ro.final_obs keeps the one of every
+        step, so a rollout that crosses two episode ends of one replica can bootstrap both.
+        The buffer is allocated by the first call and reused by later calls with the same T, final_obs and jet setting (a
+        VecShkadov with set_jet_rewards() on gets the rwd_jets segment; the setting is read at attach time).  rollout(None)
+        detaches -- the default, in which every call launches exactly what it always did -- keeps the buffer and returns it.
+        With StepGraph, keep_steps=False plus a rollout is the lean form: the per-step copies of keep_steps store a subset of
+        what the rollout holds.  A graph records whether a rollout was attached at capture().
+        The rollout is bookkeeping, like `episodes`: it is in no Snapshot, snapshot_signature() does not change, restore() /
+        fork() leave it where it is.  ShardedVecEnv does not offer this, the single-env mirrors neither."""
+        if T is None:
+            self._rollout = None
+            return self._rollout_kept
+        jets = bool(getattr(self, "_jets_on", False))
+        ro = self._rollout_kept
+        want = (_lib.RO_FINAL_OBS if final_obs else 0) | (_lib.RO_JETS if jets else 0)
+        if ro is None or (ro.T, ro.flags) != (int(T), want):
+            ro = Rollout(self, T, final_obs)
+        if self._rollout_kept is None:
+            self._rollout_kept = ro
+            self._merge_rollout_ops()
+        self._rollout_kept = self._rollout = ro
+        return ro
+
+    def _merge_rollout_ops(self):
+        """_ROLLOUT_OPS into this env's tables of both bindings (they are in neither _op_table() nor _c_table())."""
+        ops, cfn = _rollout_tables(self.lib, self._ops is not None)
+        if self._ops is not None:
+            if ops is None:
+                raise RuntimeError("the torch extension in use lacks the rollout ops: rebuild it (beacon_amd/torch_ext.py)")
+            self._ops = dict(self._ops, **ops)
+        self._cfn = dict(self._cfn, **cfn)
+
+    def _record(self, ro, stepped, ep):
+        """the recording launch of one step: the sources are the normaliser's, the episode buffer's and the per-jet buffer's exactly
+        when those are in play"""
+        k = self._keep                    # what _step handed the kernel: the converted actions (with the noise, for the envs that take it)
+        jets = getattr(self, "_jets", None) if (ro.flags & _lib.RO_JETS and getattr(self, "_jets_on", False)) else None
+        self._call("rollout_record", self.out_buf, ro.buf, k[0] if isinstance(k, tuple) else k, None if ep is None else ep.buf,
+                   self._norm.buf if self._norm_on else None, None if jets is None else jets.buf, stepped, ro.T, ro.flags)
 
     # -- running normalisation --------------------------------------------------------------
     def set_normalize(self, on=True, gamma=0.99, eps=1e-8, clip_obs=10.0, clip_rwd=10.0, training=True):
@@ -940,7 +1132,9 @@ class VecEnv(object):
         autoreset=True records step_autoreset() instead: per step the step kernel, the bookkeeping launch and the masked reset, so
         a replayed rollout crosses episode ends.  obs_seq[k] then holds the post-reset observations, done_seq / trunc_seq the
         terminal flags, and `episodes` accumulates across replays (its final_obs holds the LAST terminal observation of each
-        replica).  The default records exactly the step() calls."""
+        replica).  The default records exactly the step() calls.
+        With a rollout attached (rollout) every recorded step is followed by the recording launch, and keep_steps keeps its
+        default: keep_steps=False plus a rollout is the lean form, begin() between replays starts the next rollout."""
         return StepGraph(self, actions, noise, n_steps, keep_steps, autoreset)
 
     def reset_done(self):

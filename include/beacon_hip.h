@@ -552,6 +552,53 @@ BCN_API size_t bcn_normalize_bytes(bcn_env_t h);
 BCN_API int bcn_normalize_layout(bcn_env_t h, bcn_snapshot_seg* segs, int max_segs);
 BCN_API int bcn_normalize(bcn_env_t h, const void* out_buf_dev, void* norm_buf_dev, const void* ep_buf_dev, const uint8_t* mask_dev,
                           int kind, int training, double gamma, double eps, double clip_obs, double clip_rwd, void* stream);
+/* Rollout storage and generalised advantage estimation: what an on-policy trainer keeps after every step and computes after every
+ * rollout, on the device (the reference has no counterpart: its trainers keep Python lists).  No host synchronisation, no host read,
+ * no allocation, no atomics: every call can be captured into a graph, and the same inputs give the same bits every time.  The
+ * rollout buffer belongs to the caller (bcn_rollout_bytes(h, T, flags) bytes, 16-byte aligned, zeroed before its first use); its
+ * segments, in this order, every start a multiple of 16 bytes, for T steps of the handle's B replicas:
+ *   cursor int32 [4]                    [0] steps recorded so far, [1] sticky overflow flag; planes = 0
+ *   obs real [T + 1][B][n_obs]          obs[0]: the observations bcn_rollout_begin found; obs[t + 1]: those step t returned
+ *   act [T][B][n_act] real, or [T][B] int32 for the envs with discrete actions (mixing, lorenz)
+ *   rwd real [T][B], status int32 [T][B], done, trunc, valid uint8 [T][B]
+ *   final_obs real [T][B][n_obs]        with BCN_RO_FINAL_OBS: rows of the replicas that finished in step t
+ *   rwd_jets real [T][B][n_jets]        with BCN_RO_JETS (shkadov): the per-jet rewards of step t
+ *   adv, ret real [T][B cols]           written by bcn_rollout_gae; room for cols = n_jets with BCN_RO_JETS, else 1
+ * bcn_rollout_layout writes them as bcn_snapshot_seg and returns their number, 12 (only the first max_segs are written; 0 and
+ * bcn_last_error on a bad argument): planes = T (obs: T + 1) arrays of B rows of row_elems elements one behind the other; a segment
+ * whose flag is off has row_elems = 0 and takes no bytes, so the names and their order are fixed.
+ * bcn_rollout_begin: cursor = 0, overflow = 0, obs[0] = the obs of out_buf_dev, or norm_obs of norm_buf_dev (bcn_normalize) when one
+ * is passed.  ONE launch.
+ * bcn_rollout_record, behind a step (and behind bcn_episode_track, the masked reset and bcn_normalize when those run), with
+ * t = cursor[0] read on the device: t >= T writes no slot and sets the overflow flag; otherwise, for every replica b,
+ *   on = mask_dev == NULL || mask_dev[b] != 0 (uint8[B]; the mask of bcn_set_mask plays no part);
+ *   rwd[t][b] = on ? rwd[b] : 0; done / trunc[t][b] = on ? done / trunc[b] : 0; valid[t][b] = on; status[t][b] = status[b];
+ *   obs[t + 1][b] = obs[b] (a replica that was not stepped still holds its row);
+ *   act[t][b] = act_dev[b] where on (act_dev: the element type and row length of the act segment; NULL records zeros);
+ *   final_obs[t][b] = final_obs[b] of ep_buf_dev where its finished[b] != 0 (BCN_RO_FINAL_OBS and ep_buf_dev given);
+ *   rwd_jets[t][b] = rwd_jets[b] of jets_buf_dev (bcn_shkadov_jet_rewards; needs BCN_RO_JETS);
+ * and cursor[0] = t + 1.  With norm_buf_dev, obs, rwd and final_obs are norm_obs, norm_rwd and norm_final_obs of that buffer.  TWO
+ * launches: the record, in which every workgroup reads the cursor and none writes it, and one lane that advances it.
+ * bcn_rollout_gae: with n = min(cursor[0], T) read on the device, for every column c of [B cols] (cols = 1: rwd; cols = n_jets, which
+ * needs BCN_RO_JETS: rwd_jets; the flags are those of replica c / cols), nv = last_value[c], gae = 0, and t = n - 1 ... 0:
+ *   valid[t] == 0:  adv[t] = 0; ret[t] = values[t]; nv and gae pass through
+ *   else            fin = done[t] | trunc[t]; boot = final_values_dev != NULL && trunc[t] ? final_values[t] : 0;
+ *                   delta = rwd[t] + gamma (fin ? boot : nv) - values[t]; gae = delta + (fin ? 0 : gamma lam gae);
+ *                   adv[t] = gae; ret[t] = gae + values[t]; nv = values[t]
+ * in float64 whatever the handle's dtype, rounded once on store; rows t >= n of adv and ret are not written, and rows of
+ * final_values without trunc are not used (they may hold anything).  values_dev, final_values_dev: real [T][B cols]; last_value_dev: real [B cols].  adv and
+ * ret are [T][B cols] from the start of their segments.  ONE launch, a lane per column.
+ * BCN_ERR_ARG (bcn_rollout_bytes / _layout: 0), and nothing dereferenced, for a NULL handle or buffer, a misaligned buffer, T < 1,
+ * unknown flags, BCN_RO_JETS on another env than shkadov, another cols, gamma or lam outside [0, 1].  The size of the buffers is the
+ * caller's to get right (the torch ops check it). */
+enum { BCN_RO_FINAL_OBS = 1, BCN_RO_JETS = 2 };
+BCN_API size_t bcn_rollout_bytes(bcn_env_t h, int T, int flags);
+BCN_API int bcn_rollout_layout(bcn_env_t h, int T, int flags, bcn_snapshot_seg* segs, int max_segs);
+BCN_API int bcn_rollout_begin(bcn_env_t h, void* ro_buf_dev, const void* out_buf_dev, const void* norm_buf_dev, void* stream);
+BCN_API int bcn_rollout_record(bcn_env_t h, const void* out_buf_dev, void* ro_buf_dev, const void* act_dev, const void* ep_buf_dev,
+                               const void* norm_buf_dev, const void* jets_buf_dev, const uint8_t* mask_dev, int T, int flags, void* stream);
+BCN_API int bcn_rollout_gae(bcn_env_t h, void* ro_buf_dev, const void* values_dev, const void* last_value_dev, const void* final_values_dev,
+                            int T, int flags, int cols, double gamma, double lam, void* stream);
 /* name of the kernel the last *_step dispatched, e.g. "ns2d_fast_sched" (before the first step: the
  * variant's plain kernel); for profiles */
 BCN_API const char* bcn_kernel_name(bcn_env_t h);
