@@ -294,9 +294,16 @@ BCN_API int bcn_set_fast_plugin_params(bcn_env_t h, void* launch_fn);
  * stream -- once per action step (burgers.py:127), once per timestep (shkadov.py:204) -- and the *_step entry points take those
  * draws as noise_dev, so that a caller can reproduce the reference's stream.  A trainer that only needs noise of that law leaves
  * noise_dev NULL after this call: the step kernel then draws uniform(-sigma, sigma) itself (Philox4x32-10 keyed by `seed`, counter =
- * (replica_offset + replica index, the replica's own count of such steps, timestep)) -- no extra launch, no host work, fresh values
+ * (replica_offset + replica index, the replica's own count of such steps, timestep, 0)) -- no extra launch, no host work, fresh values
  * when a captured graph replays.  sigma = 0 (the default) restores "NULL = no noise".  replica_offset: global index of this handle's
- * replica 0 (sharded batches).  Resets the replicas' draw counters.  BCN_ERR_ARG for envs without inlet noise. */
+ * replica 0 (sharded batches).  Resets the replicas' draw counters.  BCN_ERR_ARG for envs without inlet noise.
+ *   The value: key = (low, high 32-bit word of `seed`); with w0, w1 the first two output words, r = (w0 >> 8) 2^-24 (BCN_F32) or
+ *   ((w0 << 21) ^ (w1 >> 11)) 2^-53 (BCN_F64), and the draw is (2 r - 1) sigma in the handle's precision.
+ *   The draw counter: a step with noise_dev NULL and sigma > 0 advances the counter of every replica it steps by one; a replica
+ *   that bcn_set_mask leaves out keeps its counter, and so does every step with an explicit noise_dev.  bcn_burgers_reset and
+ *   bcn_shkadov_reset leave the counters alone, masked or not -- only this call sets them back to 0 -- so the episode after a reset
+ *   goes on in the stream where the last one stopped (bcn_shkadov_reset_random ticks them as described there).
+ *   tests/noise_ref.py restates the stream on the host; tests/test_gpu_noise.py holds the kernels to it bit for bit. */
 BCN_API int bcn_set_noise(bcn_env_t h, double sigma, uint64_t seed, int64_t replica_offset);
 /* Solver options of the 2D envs (no reference counterpart), by name:
  *   "conv_plan"   which Jacobi sweeps evaluate the residual err = sum((phi - phin)^2) of rayleigh.py:448-449 / mixing.py:457-458
