@@ -103,5 +103,13 @@ struct DevBuf {
     if (e != hipSuccess) { bcn_set_error("hipMalloc(%zu): %s", n, hipGetErrorString(e)); return BCN_ERR_HIP; }
     return BCN_OK;
   }
+  // n elements of T, zeroed; *out = the typed pointer
+  template <typename T> int zalloc(size_t n, T** out) {
+    const int rc = alloc(n * sizeof(T));
+    if (rc) return rc;
+    BCN_HIP(hipMemset(p, 0, bytes));
+    *out = static_cast<T*>(p);
+    return BCN_OK;
+  }
   void release() { if (p) (void)hipFree(p); p = nullptr; }
 };

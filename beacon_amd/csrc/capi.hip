@@ -10,6 +10,7 @@
 
 #include "env1d.h"
 #include "ns2d.h"
+#include "ns2d_sched.h"
 #include "ode_env.h"
 #include "params.h"
 #include "snapshot.h"
@@ -100,12 +101,10 @@ struct NS2DEnv : bcn_env_s {
   bool guard_holds() const { return a.nx >= 48 && a.ny >= 48; }
 
   int init() {
-    const size_t per = (size_t)batch * a.ncell * sizeof(real);
+    const size_t n = (size_t)batch * a.ncell, per = n * sizeof(real);
     int rc;
-    if ((rc = fields.alloc(6 * per))) return rc;
-    BCN_HIP(hipMemset(fields.p, 0, 6 * per));
-    real* f = static_cast<real*>(fields.p);
-    const size_t n = (size_t)batch * a.ncell;
+    real* f;
+    if ((rc = fields.zalloc(6 * n, &f))) return rc;
     a.u = f; a.v = f + n; a.p = f + 2 * n; a.S = f + 3 * n; a.us = f + 4 * n; a.vs = f + 5 * n;
     const bool in_lds = ns2d_generic_lds_bytes(a.ncell, sizeof(real)) > (2 * 16 + 64) * sizeof(real);
     if (!in_lds) {
@@ -113,39 +112,23 @@ struct NS2DEnv : bcn_env_s {
       real* w = static_cast<real*>(work.p);
       a.g0 = w; a.g1 = w + n; a.g2 = w + 2 * n;
     }
-    if ((rc = obs_hist.alloc((size_t)batch * a.n_obs * sizeof(real)))) return rc;
-    BCN_HIP(hipMemset(obs_hist.p, 0, obs_hist.bytes));
-    a.obs_hist = static_cast<real*>(obs_hist.p);
-    if ((rc = a_last.alloc((size_t)batch * (a.n_sgts > 0 ? a.n_sgts : 1) * sizeof(real)))) return rc;
-    BCN_HIP(hipMemset(a_last.p, 0, a_last.bytes));
-    a.a_last = static_cast<real*>(a_last.p);
-    if ((rc = ia_last.alloc((size_t)batch * sizeof(int32_t)))) return rc;
-    BCN_HIP(hipMemset(ia_last.p, 0, ia_last.bytes));
-    a.ia_last = static_cast<int32_t*>(ia_last.p);
-    if ((rc = stpbuf.alloc((size_t)batch * sizeof(int32_t)))) return rc;
-    BCN_HIP(hipMemset(stpbuf.p, 0, stpbuf.bytes));
-    stp = a.stp = static_cast<int32_t*>(stpbuf.p);
-    if ((rc = sweepbuf.alloc((size_t)batch * (a.ndt_act > 0 ? a.ndt_act : 1) * sizeof(int32_t)))) return rc;
-    BCN_HIP(hipMemset(sweepbuf.p, 0, sweepbuf.bytes));
-    a.sweeps_int = static_cast<int32_t*>(sweepbuf.p);
-    if ((rc = statusbuf.alloc((size_t)batch * sizeof(int32_t)))) return rc;
-    BCN_HIP(hipMemset(statusbuf.p, 0, statusbuf.bytes));
-    status_int = static_cast<int32_t*>(statusbuf.p);
-    if ((rc = orderbuf.alloc((size_t)batch * sizeof(int32_t)))) return rc;
-    a.order_out = static_cast<int32_t*>(orderbuf.p);
-    {   // [ SchedCtl + progress[B] | pad to 16 | cyc[B][4] ]: zeroed by one memset per step
-      const size_t ctl = (128 + (size_t)batch * sizeof(uint32_t) + 15) / 16 * 16;
-      a.sched_bytes = ctl + (size_t)batch * 4 * sizeof(unsigned long long);
-      if ((rc = schedbuf.alloc(a.sched_bytes))) return rc;
-      BCN_HIP(hipMemset(schedbuf.p, 0, a.sched_bytes));
-      a.sched_ctl = schedbuf.p;
-      a.cyc = reinterpret_cast<unsigned long long*>(static_cast<char*>(schedbuf.p) + ctl);
-    }
+    if ((rc = obs_hist.zalloc((size_t)batch * a.n_obs, &a.obs_hist))) return rc;
+    if ((rc = a_last.zalloc((size_t)batch * (a.n_sgts > 0 ? a.n_sgts : 1), &a.a_last))) return rc;
+    if ((rc = ia_last.zalloc(batch, &a.ia_last))) return rc;
+    if ((rc = stpbuf.zalloc(batch, &a.stp))) return rc;
+    stp = a.stp;
+    if ((rc = sweepbuf.zalloc((size_t)batch * (a.ndt_act > 0 ? a.ndt_act : 1), &a.sweeps_int))) return rc;
+    if ((rc = statusbuf.zalloc(batch, &status_int))) return rc;
+    if ((rc = orderbuf.zalloc(batch, &a.order_out))) return rc;
+    const SchedLayout sl = ns2d_sched_layout(batch);   // zeroed by one memset per step
+    char* sched;
+    if ((rc = schedbuf.zalloc(sl.total, &sched))) return rc;
+    a.sched_ctl = sched;
+    a.sched_bytes = sl.total;
+    a.cyc = reinterpret_cast<unsigned long long*>(sched + sl.cyc_offset);
     fast_ok = ns2d_fast_supported<real>(a);
     if (fast_ok && (a.fscr_stride = ns2d_fast_scratch_elems<real>(a)) > 0) {
-      if ((rc = fscrbuf.alloc((size_t)batch * a.fscr_stride * sizeof(real)))) return rc;
-      BCN_HIP(hipMemset(fscrbuf.p, 0, fscrbuf.bytes));
-      a.fscr = static_cast<real*>(fscrbuf.p);
+      if ((rc = fscrbuf.zalloc((size_t)batch * a.fscr_stride, &a.fscr))) return rc;
     }
     variant = fast_ok ? 1 : 0;
     // both precisions: the extrapolating plan with PROVEN landings (plan 3: every stop sweep is the reference's, ns2d_fast_impl.h).
@@ -243,10 +226,8 @@ struct NS2DEnv : bcn_env_s {
     if (scratch_elems > 0) {
       DeviceGuard g(device);
       fscrbuf.release();
-      int rc = fscrbuf.alloc((size_t)batch * scratch_elems * sizeof(real));
+      int rc = fscrbuf.zalloc((size_t)batch * scratch_elems, &a.fscr);
       if (rc) return rc;
-      BCN_HIP(hipMemset(fscrbuf.p, 0, fscrbuf.bytes));
-      a.fscr = static_cast<real*>(fscrbuf.p);
       a.fscr_stride = scratch_elems;
     }
     plugin = reinterpret_cast<plugin_fn>(fn);
@@ -361,24 +342,15 @@ struct Env1D : bcn_env_s {
 
   int init() {
     int rc;
-    const size_t per = (size_t)batch * a.n * sizeof(real);
-    if ((rc = fields.alloc(4 * per))) return rc;
-    BCN_HIP(hipMemset(fields.p, 0, 4 * per));
-    real* f = static_cast<real*>(fields.p);
     const size_t n = (size_t)batch * a.n;
+    real* f;
+    if ((rc = fields.zalloc(4 * n, &f))) return rc;
     a.f0 = f; a.f1 = f + n; a.f2 = f + 2 * n; a.f3 = f + 3 * n;
-    if ((rc = a_last.alloc((size_t)batch * nact * sizeof(real)))) return rc;
-    if ((rc = a_prev.alloc((size_t)batch * nact * sizeof(real)))) return rc;
-    BCN_HIP(hipMemset(a_last.p, 0, a_last.bytes));
-    BCN_HIP(hipMemset(a_prev.p, 0, a_prev.bytes));
-    a.a_last = static_cast<real*>(a_last.p);
-    a.a_prev = static_cast<real*>(a_prev.p);
-    if ((rc = stpbuf.alloc((size_t)batch * sizeof(int32_t)))) return rc;
-    BCN_HIP(hipMemset(stpbuf.p, 0, stpbuf.bytes));
-    stp = a.stp = static_cast<int32_t*>(stpbuf.p);
-    if ((rc = nctrbuf.alloc((size_t)batch * sizeof(uint32_t)))) return rc;
-    BCN_HIP(hipMemset(nctrbuf.p, 0, nctrbuf.bytes));
-    a.nctr = static_cast<uint32_t*>(nctrbuf.p);
+    if ((rc = a_last.zalloc((size_t)batch * nact, &a.a_last))) return rc;
+    if ((rc = a_prev.zalloc((size_t)batch * nact, &a.a_prev))) return rc;
+    if ((rc = stpbuf.zalloc(batch, &a.stp))) return rc;
+    stp = a.stp;
+    if ((rc = nctrbuf.zalloc(batch, &a.nctr))) return rc;
     a.nsigma = 0; a.nseed_lo = 0; a.nseed_hi = 0; a.noff = 0;
     return BCN_OK;
   }
@@ -469,15 +441,10 @@ struct OdeEnv : bcn_env_s {
 
   int init() {
     int rc;
-    if ((rc = st.alloc((size_t)batch * nreal * sizeof(real)))) return rc;
-    BCN_HIP(hipMemset(st.p, 0, st.bytes));
-    a.st = static_cast<real*>(st.p);
-    if ((rc = iubuf.alloc((size_t)batch * sizeof(int32_t)))) return rc;
-    BCN_HIP(hipMemset(iubuf.p, 0, iubuf.bytes));
-    a.iu = static_cast<int32_t*>(iubuf.p);
-    if ((rc = stpbuf.alloc((size_t)batch * sizeof(int32_t)))) return rc;
-    BCN_HIP(hipMemset(stpbuf.p, 0, stpbuf.bytes));
-    stp = a.stp = static_cast<int32_t*>(stpbuf.p);
+    if ((rc = st.zalloc((size_t)batch * nreal, &a.st))) return rc;
+    if ((rc = iubuf.zalloc(batch, &a.iu))) return rc;
+    if ((rc = stpbuf.zalloc(batch, &a.stp))) return rc;
+    stp = a.stp;
     a.batch = batch; a.n_obs = n_obs;
     // observation rows through LDS for float64 (48 / 64 B rows), direct per-lane stores for float32: measured A/B/A/B at B = 2^20
     // (DESIGN.md §10): lorenz float64 30.8 / 34.5 us per step staged / direct, float32 19.8 / 19.0; vortex float32 42.4 / 40.9,

@@ -56,7 +56,7 @@ struct NS2DArgs {
   const int32_t* order;     // blockIdx -> replica, or NULL for identity
   int32_t* order_out;       // rank kernel output
   int32_t* sweeps_int;      // handle-owned [B][ndt_act] when the caller passes no sweeps buffer
-  void* sched_ctl;          // handle-owned control block of the ticketed chunk scheduler (64 + 4B bytes), followed by
+  void* sched_ctl;          // handle-owned control block of the ticketed chunk scheduler (ns2d_sched.h: ns2d_sched_layout), followed by
   unsigned long long* cyc;  // [B][4] of the last step: shader-clock cycles inside the Jacobi loop / in the whole replica, late stops, repeated timesteps (bcn_get_counters)
   size_t sched_bytes;       // bytes of sched_ctl + cyc: zeroed by one memset in front of every step launch
   int sched_q;              // timesteps per chunk

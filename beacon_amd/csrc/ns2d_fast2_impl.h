@@ -56,6 +56,8 @@ struct Fast2Geom {
   static constexpr int SZ = SX * SY;
   // LDS map (elements): exchange [2][NW][2 sides][2 rows][64] | errp 64 | sact 64 | red 32 | U V S
   static constexpr int EXCH = 2 * NW * 4 * 64;
+  // ns2d_fast2_sched's two words: the end of the `red` row (block_sum uses red[0..NW), the transport sink red[16..17])
+  static constexpr int SCHED_WORDS = EXCH + 128 + 24;
   static constexpr size_t lds_elems() { return GF ? (size_t)EXCH + 160 + 2 * (size_t)R * NT : (size_t)EXCH + 160 + 3 * (size_t)SZ; }
   static constexpr size_t scratch_elems() { return GF ? 3 * (size_t)SZ + 16 : 0; }   // + 16: the transport wave's sink
 };
@@ -985,43 +987,21 @@ __global__ __launch_bounds__(((NX + R - 1) / R) * 64) void ns2d_fast2_sched(NS2D
                                                                           int nchunk BCN_PRM_KPARAM) {
   using G = Fast2Geom<NX, NY, R, GF>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  // two words at the end of the `red` scratch row (block_sum uses red[0..NW), the transport sink red[16..17])
-  unsigned int* s_words = reinterpret_cast<unsigned int*>(reinterpret_cast<real*>(smem) + G::EXCH + 128 + 24);
+  unsigned int* s_words = reinterpret_cast<unsigned int*>(reinterpret_cast<real*>(smem) + G::SCHED_WORDS);
   ns2d_sched_loop<real>(A, ctl, batch, nchunk, s_words, [&](int b, int it0, int it1, bool first, bool last) {
     fast2_unit<real, NX, NY, R, KIND, EQ, GF>(A, b, it0, it1, first, last, smem BCN_PRM_KARG);
   });
 }
 
+// ns2d_sched.h: uniform chunks of 20 timesteps (100x100: 37.7 ms against 38.2 at 10; long chunks first measured slower here)
+constexpr SchedPolicy kFast2Policy = {"ns2d_fast2_step", "ns2d_fast2_sched", 20, false, nullptr};
+
 template <typename real, int NX, int NY, int R, int KIND, bool EQ, int GF>
 int launch_fast2_eq(const NS2DArgs<real>& a, int batch, hipStream_t s BCN_PRM_PARAM) {
   using G = Fast2Geom<NX, NY, R, GF>;
-  const size_t lds = G::lds_elems() * sizeof(real);
   if (GF && (!a.fscr || a.fscr_stride < G::scratch_elems())) { bcn_set_error("fast2 path: field scratch missing"); return BCN_ERR_UNSUPPORTED; }
-  NS2DArgs<real> c = a;
-  if (!c.sweeps) c.sweeps = c.sweeps_int;
-  const SchedParams sp = ns2d_sched_params(a);
-  const int q = sp.q_set ? sp.q : 20;   // 100x100: 20 timesteps per chunk measured best (37.7 vs 38.2 ms at 10)
-  if (sp.mode == 2 && batch > sp.grid && a.ndt_act >= 2 * q && a.sched_ctl) {
-    auto ks = ns2d_fast2_sched<real, NX, NY, R, KIND, EQ, GF>;
-    static unsigned long long set2 = 0;
-    if (ns2d_first_on_device(set2)) BCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ks), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int nchunk = a.ndt_act / q;   // uniform chunks (the long-chunks-first order of ns2d_fast_impl.h measured slower here)
-    c.sched_nbig = 0;
-    c.sched_q = q;
-    BCN_HIP(hipMemsetAsync(a.sched_ctl, 0, a.sched_bytes, s));
-    hipLaunchKernelGGL(ks, dim3(sp.grid), dim3(G::NT), lds, s, c, static_cast<SchedCtl*>(a.sched_ctl), batch, nchunk BCN_PRM_LAUNCH);
-    BCN_HIP(hipGetLastError());
-    if (a.host) a.host->launched = "ns2d_fast2_sched";
-    return BCN_OK;
-  }
-  if (a.sched_ctl) BCN_HIP(hipMemsetAsync(a.sched_ctl, 0, a.sched_bytes, s));   // cycle counters
-  auto k = ns2d_fast2_step<real, NX, NY, R, KIND, EQ, GF>;
-  static unsigned long long set = 0;
-  if (ns2d_first_on_device(set)) BCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k, dim3(batch), dim3(G::NT), lds, s, c BCN_PRM_LAUNCH);
-  BCN_HIP(hipGetLastError());
-  if (a.host) a.host->launched = "ns2d_fast2_step";
-  return BCN_OK;
+  return ns2d_sched_launch<ns2d_fast2_step<real, NX, NY, R, KIND, EQ, GF>, ns2d_fast2_sched<real, NX, NY, R, KIND, EQ, GF>>(
+      kFast2Policy, a, batch, s, G::NT, G::lds_elems() * sizeof(real) BCN_PRM_ARG);
 }
 
 template <typename real, int NX, int NY, int R, int KIND, int GF = 0>

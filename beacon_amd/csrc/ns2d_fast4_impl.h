@@ -57,7 +57,8 @@ struct Fast4Geom {
   static constexpr int P = SX | 1;                  // LDS pitch of a natural-layout array (odd)
   static constexpr int CPL = (NX + BCN_WAVE - 1) / BCN_WAVE;  // columns per lane of the transport walk
   static constexpr int HROWS = BCN_WAVE * RPL;      // one edge column in the exchange buffer (lane-major)
-  static constexpr int FIXED = 2 * 32 + 64 + 16;    // reduction scratch [2][2][16] + conditioned actions + the scheduler's two words
+  static constexpr int SCHED_WORDS = 2 * 32 + 64;   // ns2d_fast4_sched's two words, behind the reduction scratch [2][2][16] and the conditioned actions
+  static constexpr int FIXED = SCHED_WORDS + 16;
   static constexpr int HAL = 2 * NW * 2 * HROWS;    // [parity][wave][west|east][HROWS]
   static constexpr int WARR = P * (NY + 2);
   static constexpr int LDS_ELEMS_MAX(int esz) { return 160 * 1024 / esz; }
@@ -946,43 +947,21 @@ __global__ __launch_bounds__((Fast4Geom<NX, NY, R, RPL>::NT)) void ns2d_fast4_st
 template <typename real, int NX, int NY, int R, int RPL, int KIND, bool EQ>
 __global__ __launch_bounds__((Fast4Geom<NX, NY, R, RPL>::NT)) void ns2d_fast4_sched(NS2DArgs<real> A, SchedCtl* ctl, int batch, int nchunk BCN_PRM_KPARAM) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  unsigned int* s_words = reinterpret_cast<unsigned int*>(reinterpret_cast<real*>(smem) + 128);
+  unsigned int* s_words = reinterpret_cast<unsigned int*>(reinterpret_cast<real*>(smem) + Fast4Geom<NX, NY, R, RPL>::SCHED_WORDS);
   ns2d_sched_loop<real>(A, ctl, batch, nchunk, s_words, [&](int b, int it0, int it1, bool first, bool last) {
     fast4_unit<real, NX, NY, R, RPL, KIND, EQ>(A, b, it0, it1, first, last, smem BCN_PRM_KARG);
   });
 }
 
+// ns2d_sched.h: uniform chunks of 20 timesteps
+constexpr SchedPolicy kFast4Policy = {"ns2d_fast4_step", "ns2d_fast4_sched", 20, false, nullptr};
+
 template <typename real, int NX, int NY, int R, int RPL, int KIND, bool EQ>
 int launch_fast4_eq(const NS2DArgs<real>& a, int batch, hipStream_t s BCN_PRM_PARAM) {
   using G = Fast4Geom<NX, NY, R, RPL>;
-  const size_t lds = (size_t)G::lds_elems(sizeof(real)) * sizeof(real);
   if (!f4_fields_ok(a, (size_t)G::NCELL)) return BCN_ERR_UNSUPPORTED;   // (the caller falls back to the generic kernel)
-  NS2DArgs<real> c = a;
-  if (!c.sweeps) c.sweeps = c.sweeps_int;
-  const SchedParams sp = ns2d_sched_params(a);
-  const int q = sp.q_set ? sp.q : 20;   // timesteps per chunk
-  if (sp.mode == 2 && batch > sp.grid && a.ndt_act >= 2 * q && a.sched_ctl) {
-    // more replicas than CUs: persistent workgroups share the replicas' timesteps chunk by chunk, so that a CU is not
-    // stuck with the sum of whichever two replicas' sweep counts it was dealt
-    auto ks = ns2d_fast4_sched<real, NX, NY, R, RPL, KIND, EQ>;
-    static unsigned long long set2 = 0;
-    if (ns2d_first_on_device(set2)) BCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ks), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    c.sched_nbig = 0;
-    c.sched_q = q;
-    BCN_HIP(hipMemsetAsync(a.sched_ctl, 0, a.sched_bytes, s));
-    hipLaunchKernelGGL(ks, dim3(sp.grid), dim3(G::NT), lds, s, c, static_cast<SchedCtl*>(a.sched_ctl), batch, a.ndt_act / q BCN_PRM_LAUNCH);
-    BCN_HIP(hipGetLastError());
-    if (a.host) a.host->launched = "ns2d_fast4_sched";
-    return BCN_OK;
-  }
-  if (a.sched_ctl) BCN_HIP(hipMemsetAsync(a.sched_ctl, 0, a.sched_bytes, s));   // cycle counters
-  auto k = ns2d_fast4_step<real, NX, NY, R, RPL, KIND, EQ>;
-  static unsigned long long set = 0;
-  if (ns2d_first_on_device(set)) BCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k, dim3(batch), dim3(G::NT), lds, s, c BCN_PRM_LAUNCH);
-  BCN_HIP(hipGetLastError());
-  if (a.host) a.host->launched = "ns2d_fast4_step";
-  return BCN_OK;
+  return ns2d_sched_launch<ns2d_fast4_step<real, NX, NY, R, RPL, KIND, EQ>, ns2d_fast4_sched<real, NX, NY, R, RPL, KIND, EQ>>(
+      kFast4Policy, a, batch, s, G::NT, (size_t)G::lds_elems(sizeof(real)) * sizeof(real) BCN_PRM_ARG);
 }
 
 template <typename real, int NX, int NY, int R, int RPL, int KIND>

@@ -88,7 +88,8 @@ struct FastGeom {
   // columns only where LDS is short (GF == 2: two float64 fields in LDS)
   static constexpr int XC = (GF == 2) ? 2 : 4;
   static constexpr int EXCH = 2 * NW * XC * 64;             // [2 buffers][NW][XC][64]
-  static constexpr int MISC = EXCH + 224 + 16;              // + 16: scheduler words (ns2d_fast_sched)
+  static constexpr int SCHED_WORDS = EXCH + 224;            // ns2d_fast_sched's two words, behind errp / sact / red (no static __shared__ in front of the dynamic region)
+  static constexpr int MISC = SCHED_WORDS + 16;
   static constexpr int FRONT = ((MISC > 63 * SY + 1 ? MISC : 63 * SY + 1) + 15) / 16 * 16;
   static constexpr int BACK = (NY + 3 * PD + 2) * SY;   // the transport wave prefetches two blocks of PD diagonals ahead
   static constexpr int FRONTG = (63 * SY + 1 + 15) / 16 * 16;          // front pad of the global variant
@@ -1270,9 +1271,7 @@ __global__ __launch_bounds__((FastGeom<NX, NY, R, GF>::NT)) void ns2d_fast_step(
 template <typename real, int NX, int NY, int R, int KIND, bool EQ, int GF>
 __global__ __launch_bounds__((FastGeom<NX, NY, R, GF>::NT)) void ns2d_fast_sched(NS2DArgs<real> A, SchedCtl* ctl, int batch, int nchunk BCN_PRM_KPARAM) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  // two words behind fast_body's scalars (no static __shared__ in front of the dynamic region)
-  unsigned int* s_words = reinterpret_cast<unsigned int*>(reinterpret_cast<real*>(smem) +
-                                                          FastGeom<NX, NY, R, GF>::EXCH + 224);
+  unsigned int* s_words = reinterpret_cast<unsigned int*>(reinterpret_cast<real*>(smem) + FastGeom<NX, NY, R, GF>::SCHED_WORDS);
   ns2d_sched_loop<real>(A, ctl, batch, nchunk, s_words, [&](int b, int it0, int it1, bool first, bool last) {
     fast_unit<real, NX, NY, R, KIND, EQ, GF>(A, b, it0, it1, first, last, smem BCN_PRM_KARG);
   });
@@ -1302,55 +1301,19 @@ __global__ __launch_bounds__(1024) void ns2d_rank_by_work(const int32_t* sweeps,
   }
 }
 
+void fast_rank(const int32_t* sweeps, int ndt, int q, int batch, int32_t* order, const uint8_t* mask, hipStream_t s) {
+  hipLaunchKernelGGL(ns2d_rank_by_work, dim3(1), dim3(1024), 0, s, sweeps, ndt, q, batch, order, mask);
+}
+
+// ns2d_sched.h: chunks of 10 timesteps, long ones first; the only family with the LPT split
+constexpr SchedPolicy kFastPolicy = {"ns2d_fast_step", "ns2d_fast_sched", 10, true, fast_rank};
+
 template <typename real, int NX, int NY, int R, int KIND, bool EQ, int GF>
 int launch_fast_eq(const NS2DArgs<real>& a, int batch, hipStream_t s BCN_PRM_PARAM) {
   using G = FastGeom<NX, NY, R, GF>;
   if (GF && (!a.fscr || a.fscr_stride < G::scratch_elems())) { bcn_set_error("fast path: field scratch missing"); return BCN_ERR_UNSUPPORTED; }
-  const size_t lds = G::template lds_bytes<real>();
-  auto k = ns2d_fast_step<real, NX, NY, R, KIND, EQ, GF>;
-  static unsigned long long attr_set = 0;
-  if (ns2d_first_on_device(attr_set)) {
-    BCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
-  NS2DArgs<real> c = a;
-  if (!c.sweeps) c.sweeps = c.sweeps_int;
-  const SchedParams sp = ns2d_sched_params(a);
-  const int mode = sp.mode, sched_grid = sp.grid, SQ = sp.q;
-  if (mode == 2 && batch > sched_grid && a.ndt_act >= 2 * SQ && a.sched_ctl) {
-    auto ks = ns2d_fast_sched<real, NX, NY, R, KIND, EQ, GF>;
-    static unsigned long long attr_set2 = 0;
-    if (ns2d_first_on_device(attr_set2)) {
-      BCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ks), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
-    int nchunk = 0;
-    ns2d_sched_chunks(a.ndt_act, SQ, (a.host ? a.host->sched_tail : 0), &c.sched_nbig, &nchunk);
-    c.sched_q = SQ; c.order = nullptr; c.first_chunk = 1; c.last_chunk = 1; c.it_begin = 0; c.it_end = a.ndt_act;
-    BCN_HIP(hipMemsetAsync(a.sched_ctl, 0, a.sched_bytes, s));
-    hipLaunchKernelGGL(ks, dim3(sched_grid), dim3(G::NT), lds, s, c, static_cast<SchedCtl*>(a.sched_ctl), batch, nchunk BCN_PRM_LAUNCH);
-    BCN_HIP(hipGetLastError());
-    if (a.host) a.host->launched = "ns2d_fast_sched";
-    return BCN_OK;
-  }
-  // split only when replicas outnumber the CUs (otherwise every replica starts at once and
-  // the order cannot matter); BCN_LPT_MIN_BATCH / bcn_set_sched override the threshold (tests)
-  const int min_batch = sp.lpt_min_batch;
-  constexpr int Q = 10;
-  const bool split = mode >= 1 && batch >= min_batch && batch <= 2048 && a.ndt_act >= 4 * Q;
-  c.first_chunk = 1; c.order = nullptr; c.it_begin = 0;
-  if (a.sched_ctl) BCN_HIP(hipMemsetAsync(a.sched_ctl, 0, a.sched_bytes, s));   // cycle counters
-  if (!split) {
-    c.it_end = a.ndt_act; c.last_chunk = 1;
-    hipLaunchKernelGGL(k, dim3(batch), dim3(G::NT), lds, s, c BCN_PRM_LAUNCH);
-  } else {
-    c.it_end = Q; c.last_chunk = 0;
-    hipLaunchKernelGGL(k, dim3(batch), dim3(G::NT), lds, s, c BCN_PRM_LAUNCH);
-    hipLaunchKernelGGL(ns2d_rank_by_work, dim3(1), dim3(1024), 0, s, c.sweeps, a.ndt_act, Q, batch, c.order_out, c.mask);
-    c.first_chunk = 0; c.last_chunk = 1; c.it_begin = Q; c.it_end = a.ndt_act; c.order = c.order_out;
-    hipLaunchKernelGGL(k, dim3(batch), dim3(G::NT), lds, s, c BCN_PRM_LAUNCH);
-  }
-  BCN_HIP(hipGetLastError());
-  if (a.host) a.host->launched = "ns2d_fast_step";
-  return BCN_OK;
+  return ns2d_sched_launch<ns2d_fast_step<real, NX, NY, R, KIND, EQ, GF>, ns2d_fast_sched<real, NX, NY, R, KIND, EQ, GF>>(
+      kFastPolicy, a, batch, s, G::NT, G::template lds_bytes<real>() BCN_PRM_ARG);
 }
 
 template <typename real, int NX, int NY, int R, int KIND, int GF = 0>

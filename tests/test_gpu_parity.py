@@ -998,6 +998,61 @@ def test_tall_grid_ticket_scheduler_matches_the_plain_launch(kind):
     assert int(out[0][0][1][0].max()) > int(out[0][0][1][0].min())      # the replicas do differ in their sweep counts
 
 
+@pytest.mark.parametrize("rows", [1, 2, 4])
+def test_chunk_policy_of_every_kernel_family_matches_the_plain_launch(rows):
+    """What a kernel family states as its SchedPolicy (ns2d_sched.h) -- chunk length, long chunks first or uniform, the LPT
+    split -- must never change a result: float32, B = 8 with distinct actions, two action steps of 45 timesteps (no chunk
+    length used here divides 45) under 3 persistent workgroups drawing chunks of 7, with the default tail, sched_tail = 1
+    (one row per lane: chunks of 14, 14, 7, 10 timesteps, i.e. long chunks and a remainder chunk; the other families ignore the
+    option: 6 uniform chunks) and sched_tail = 100 (uniform everywhere), and, where the family has it, under the two-launch LPT
+    split.  obs, rewards, sweep counts, u, v, T and the interior of p equal the plain launch's bit for bit (p's ghost cells:
+    test_rayleigh_fast_schedulers_match_single_launch).  rows 1: rayleigh 50x50; 2: mixing 100x100; 4: rayleigh 50x150."""
+    B = 8
+    name = {1: "ns2d_fast", 2: "ns2d_fast2", 4: "ns2d_fast4"}[rows]
+    rng = np.random.default_rng(11)
+    if rows == 2:
+        acts = np.stack([rng.permutation(np.arange(B) % 4) for _ in range(2)])
+    else:
+        acts = rng.uniform(-1, 1, (2, B, 10))
+    runs = [("plain", (0,), None, name + "_step"), ("tail default", (2, 3, 7, 0), None, name + "_sched"),
+            ("tail 1", (2, 3, 7, 0), 1, name + "_sched"), ("tail 100", (2, 3, 7, 0), 100, name + "_sched")]
+    if rows == 1:
+        runs.append(("split", (1, 0, 0, 2), None, name + "_step"))
+    out = {}
+    for tag, sched, tail, kernel in runs:
+        if rows == 1:
+            env = V.VecRayleigh(B, DEV, "f32", E.packaged_init("rayleigh"))
+        elif rows == 2:
+            env = V.VecMixing(B, DEV, "f32")
+        else:
+            env = V.VecRayleigh(B, DEV, "f32", None, L=1.0, H=3.0)
+        env.set_ndt_act(45)
+        assert env.set_variant(1) == 1
+        env.set_sched(*sched)
+        if tail is not None:
+            env.set_option("sched_tail", tail)
+        env.reset()
+        if rows == 4:
+            x, y = (np.arange(env.nx + 2) - 0.5) / env.nx, (np.arange(env.ny + 2) - 0.5) / env.ny
+            st0 = np.zeros((4, env.nx + 2, env.ny + 2))
+            st0[3] = (0.5 - y)[None, :] + 0.08 * np.sin(2 * np.pi * x)[:, None] * np.sin(np.pi * y)[None, :]
+            env.set_state(np.tile(ref_to_dev(st0)[None], (B, 1, 1, 1)))
+        res = []
+        for a in acts:
+            obs, rwd, _, _, _ = env.step(a)
+            env.check_status()
+            assert env.kernel_name == kernel, (tag, env.kernel_name)
+            res += [obs.clone(), rwd.clone(), env.sweeps.clone()]
+        st = env.get_state()
+        out[tag] = res + [st[:, 0].clone(), st[:, 1].clone(), st[:, 3].clone(), st[:, 2, 1:-1, 1:-1].clone()]
+        env.close()
+    sw = out["plain"][5]
+    assert len({tuple(r.tolist()) for r in sw}) > 1                     # the replicas do differ in their sweep counts
+    for tag, _, _, _ in runs[1:]:
+        for k, (x0, x1) in enumerate(zip(out["plain"], out[tag])):
+            assert torch.equal(x0, x1), (tag, k)
+
+
 @pytest.mark.parametrize("dtype", ["f32", "f64"])
 def test_speculative_first_evaluation_never_changes_a_result(dtype):
     """ns2d_fast_impl.h starts a Jacobi solve with spec_start/8 of the previous timestep's sweep count as double sweeps
