@@ -57,7 +57,9 @@ class _Single(object):
     def _obs_view(self, t):
         """rayleigh.py:243-262 / mixing.py:237-258: get_obs() fills the env's own history array `self.obs`
         [n_obs_steps, 3, nx_obs_pts, ny_obs_pts] in place and returns np.reshape(self.obs, [-1]) -- a VIEW: an observation a
-        caller kept from the previous step shows the new values after the next one.  Same here: one array per env, refilled."""
+        caller kept from the previous step shows the new values after the next one.  Same here: one array per episode, refilled.
+        reset_fields() allocates a FRESH array (rayleigh.py:119, mixing.py:105), so a terminal observation kept from the last
+        step() survives the next reset(): rayleigh.reset() and mixing.reset() drop `self.obs` before they come here."""
         new = self._np(t)[0]
         if getattr(self, "obs", None) is None:
             self.obs = np.zeros((self.n_obs_steps, 3, self.nx_obs_pts, self.ny_obs_pts))
@@ -95,6 +97,7 @@ class rayleigh(_Single):
         self.a = [0.0] * self.n_sgts
         self.stp_plot = 0
         self.nu = np.empty((0, 2))                # (stp, Nusselt) per step since reset (rayleigh.py:124)
+        self.obs = None                           # a new history array per episode (rayleigh.py:119)
         return self._obs_view(obs), None
 
     def step(self, a=None):
@@ -162,6 +165,7 @@ class mixing(_Single):
         obs, _ = self.vec.reset()
         self.a = 1
         self.stp_plot = 0
+        self.obs = None                           # a new history array per episode (mixing.py:105)
         return self._obs_view(obs), None
 
     def step(self, a=None):

@@ -2962,6 +2962,27 @@ def test_jit_no_plugin_of_the_test_grids_was_refused():
     assert not bad, bad
 
 
+def test_jit_no_plugin_in_the_cache_holds_a_dpp_hazard():
+    """The plugins compiled on THIS box (the fuzz grids, any test grid that was not prebuilt) are instantiations no CPU test saw,
+    each with its own register allocation around the hand-written DPP statements: the static wait-state scan of
+    tests/isa_hazards.py (VALU write -> DPP read of the same VGPR: 2 wait states; v_cmpx -> DPP: 5) over every shared object of
+    beacon_amd/_jit/, as files -- nothing is launched, no plugin is opened; at most 8 child processes that open no GPU.  It stands
+    behind the tests above so that their plugins exist."""
+    import glob
+    import isa_hazards as H
+    from beacon_amd import jit
+    tool = H.objdump()
+    if tool is None:
+        pytest.skip("no llvm-objdump next to hipcc: nothing to disassemble with")
+    paths = sorted(glob.glob(os.path.join(jit.JIT_DIR, "*.so")))
+    assert len(paths) >= len(jit.TEST_GRIDS) + len(jit.EXTRA_BUILDS)
+    reports = H.scan_files(paths, tool)
+    print()
+    print(H.format_summary(reports))
+    assert len(reports) == len(paths) and all(r["dpp"] > 0 for r in reports)
+    assert not H.all_findings(reports), "\n".join(H.all_findings(reports))
+
+
 def test_jit_self_check_refuses_a_broken_plugin_and_keeps_the_generic_kernel():
     """A deliberately wrong plugin (csrc/jit/ns2d_jit.hip built with -DBCN_JIT_BREAK: the kernel runs with 1.5 dt) must not be
     attached: the first env that asks for it compares it with the generic kernel, warns, leaves a `.bad` marker, and steps on
@@ -3202,6 +3223,13 @@ def test_2d_env_observations_are_views_of_the_envs_history_array():
         assert np.array_equal(o0, o1) and not np.array_equal(o0, kept)      # the kept handle moved with the env
         n = 3 * env.nx_obs_pts * env.ny_obs_pts
         assert np.array_equal(o1[2 * n:3 * n], kept[3 * n:])                 # history shifted by one slot (newest last)
+        # step -> reset: reset_fields() allocates a FRESH self.obs (rayleigh.py:119, mixing.py:105), so the observation a caller
+        # kept from the last step() of an episode (the terminal one) survives the next reset()
+        last = o1.copy()
+        o2, _ = env.reset()
+        assert np.array_equal(o1, last)                                      # the kept array is unchanged ...
+        assert not np.shares_memory(o1, env.obs) and np.shares_memory(o2, env.obs)      # ... and no longer the env's own
+        assert not np.array_equal(o2, last)                                  # the new episode's observation went elsewhere
         env.close()
 
 
