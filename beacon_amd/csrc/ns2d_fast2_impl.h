@@ -33,6 +33,7 @@
 #endif
 #include "bcn_dpp.h"
 #include "ns2d.h"
+#include "ns2d_cells.h"
 #include "ns2d_device.h"
 #include "ns2d_prm.h"
 #include "ns2d_sched.h"
@@ -399,25 +400,8 @@ __device__ __forceinline__ void fast2_body(const NS2DArgs<real>& A, char* smem, 
           const real pc = p[a][k];
           const real pW = (k > 0) ? p[a][k > 0 ? k - 1 : 0] : (a == 0 ? pWh0 : pWh1);
           const real pS = (a == 0) ? from_below(p[1][k], p[1][k]) : p[0][k];
-          {
-            real uE = real(0.5) * (uE_ + uc), uW = real(0.5) * (uc + uW_);
-            real uN2 = real(0.5) * (uN_ + uc), uS2 = real(0.5) * (uc + uS_);
-            real vN2 = real(0.5) * (vN_ + vw[sW][r + 1]), vS2 = real(0.5) * (vc + vW_);
-            real conv = (uE * uE - uW * uW) * rdx + (uN2 * vN2 - uS2 * vS2) * rdy;
-            real diff = ((uE_ - 2 * uc + uW_) * rdx2 + (uN_ - 2 * uc + uS_) * rdy2) * A.kmom;
-            real pres = (pc - pW) * rdx;
-            usk[a] = (i >= 2) ? uc + dt * (diff - conv - pres) : real(0);
-          }
-          {
-            real vE = real(0.5) * (vE_ + vc), vW = real(0.5) * (vc + vW_);
-            real uE = real(0.5) * (uE_ + uw[sE][r - 1]), uW = real(0.5) * (uc + uS_);
-            real vN2 = real(0.5) * (vN_ + vc), vS2 = real(0.5) * (vc + vS_);
-            real conv = (uE * vE - uW * vW) * rdx + (vN2 * vN2 - vS2 * vS2) * rdy;
-            real diff = ((vE_ - 2 * vc + vW_) * rdx2 + (vN_ - 2 * vc + vS_) * rdy2) * A.kmom;
-            real pres = (pc - pS) * rdy;
-            const real buoy = (KIND == 0) ? Tl[i * SY + j] : real(0);
-            vsk[a] = (j >= 2) ? vc + dt * (diff - conv - pres + buoy) : real(0);
-          }
+          ns2d_pred_cell<real, KIND>(uc, uE_, uW_, uN_, uS_, uw[sE][r - 1], vc, vE_, vW_, vN_, vS_, vw[sW][r + 1], pc, pW, pS, i, j, dt, rdx, rdy, rdx2, rdy2, A.kmom,
+                                     Tl, SY, j, usk[a], vsk[a]);
         }
         // the pending column k-1 (not the strip's first one) goes to memory now: the wave-wide loads of that column have
         // returned (their data went into column k-2 .. k), and the loads in flight are of columns >= k+2.  The fence keeps
@@ -472,25 +456,8 @@ __device__ __forceinline__ void fast2_body(const NS2DArgs<real>& A, char* smem, 
           const real pW = (k > 0) ? p[a][k > 0 ? k - 1 : 0] : (a == 0 ? pWh0 : pWh1);
           // south neighbour of the lower row lives in the lane below (its upper row)
           const real pS = (a == 0) ? from_below(p[1][k], p[1][k]) : p[0][k];
-          {
-            real uE = real(0.5) * (uE_ + uc), uW = real(0.5) * (uc + uW_);
-            real uN2 = real(0.5) * (uN_ + uc), uS2 = real(0.5) * (uc + uS_);
-            real vN2 = real(0.5) * (vN_ + vN[k]), vS2 = real(0.5) * (vc + vW_);
-            real conv = (uE * uE - uW * uW) * rdx + (uN2 * vN2 - uS2 * vS2) * rdy;
-            real diff = ((uE_ - 2 * uc + uW_) * rdx2 + (uN_ - 2 * uc + uS_) * rdy2) * A.kmom;
-            real pres = (pc - pW) * rdx;
-            us[a][k] = (i >= 2) ? uc + dt * (diff - conv - pres) : real(0);
-          }
-          {
-            real vE = real(0.5) * (vE_ + vc), vW = real(0.5) * (vc + vW_);
-            real uE = real(0.5) * (uE_ + uS[k + 1]), uW = real(0.5) * (uc + uS_);
-            real vN2 = real(0.5) * (vN_ + vc), vS2 = real(0.5) * (vc + vS_);
-            real conv = (uE * vE - uW * vW) * rdx + (vN2 * vN2 - vS2 * vS2) * rdy;
-            real diff = ((vE_ - 2 * vc + vW_) * rdx2 + (vN_ - 2 * vc + vS_) * rdy2) * A.kmom;
-            real pres = (pc - pS) * rdy;
-            const real buoy = (KIND == 0) ? Tl[i * SY + j] : real(0);
-            vs[a][k] = (j >= 2) ? vc + dt * (diff - conv - pres + buoy) : real(0);
-          }
+          ns2d_pred_cell<real, KIND>(uc, uE_, uW_, uN_, uS_, uS[k + 1], vc, vE_, vW_, vN_, vS_, vN[k], pc, pW, pS, i, j, dt, rdx, rdy, rdx2, rdy2, A.kmom,
+                                     Tl, 0, i * SY + j, us[a][k], vs[a][k]);
         }
       }
     }
@@ -657,21 +624,17 @@ __device__ __forceinline__ void fast2_body(const NS2DArgs<real>& A, char* smem, 
           const float rg = 1.f / (float)(itp - 1 - k_prev);                                          \
           if (plan == 1) {                                                                    \
             const float room_u = l2u - l2tol_u, rho_u = (l2u - l2u_prev) * rg;                       \
-            if (room_u > 0.f) j = (rho_u < 0.f) ? (int)fminf(room_u / -rho_u, (float)JMAX) : JMAX;   \
+            j = ns2d_plan_steps(room_u, rho_u, JMAX);                                                \
           } else {                                                                                   \
             float l2tl = l2tol_w;                                                                    \
             if (A.conv_plan == 3) {   /* the slow-mode guard of the landing this skip ends in; this sweep, itp, is the last evaluated one */ \
-              const float e0 = (float)slow_k[0], fi = (float)itp;                                    \
-              const float t0 = 1.f + 2.f * exp2f(e0 + fi * (float)slow_k[1]), t1 = 1.f + 2.f * exp2f(e0 + fi * (float)slow_k[3]); \
-              const float g = fminf(fminf((float)slow_k[2] * t0 * t0, (float)slow_k[4] * t1 * t1) * 1.001f, (float)BCN_CONV_GUARD); \
+            const float g = ns2d_slow_guard<real>(slow_k, itp);                                                                              \
               tolL = A.tol * (real)g;                                                                \
               l2tl = __log2f((float)tolL * 1.003f);                                                  \
             }                                                                                        \
             const float room_w = l2w - l2tl, rho_w = (l2w - l2w_prev) * rg;                          \
-            int jw = 0;                                                                              \
-            if (room_w > 0.f) jw = (rho_w < 0.f) ? (int)fminf(room_w / -rho_w, (float)JMAX) : JMAX;  \
-            j = jw - 1 - (jw >> 4) + A.plan_overshoot;                                                                  \
-            j = j > 0 ? j : 0;                                                                       \
+            const int jw = ns2d_plan_steps(room_w, rho_w, JMAX);                                     \
+            j = ns2d_plan_trim(jw, A.plan_overshoot);                                                \
           }                                                                                          \
         }                                                                                            \
         j = __builtin_amdgcn_readfirstlane(j);                                                       \
@@ -761,9 +724,7 @@ __device__ __forceinline__ void fast2_body(const NS2DArgs<real>& A, char* smem, 
           const int c = (i0 + k) * SY + j0 + a;
           const real uE = Ul[c + SY], uW = Ul[c], vN = Vl[c + 1], vS = Vl[c];
           const real T0 = Tl[c], TE = Tl[c + SY], TN = Tl[c + 1];
-          const real expl = A.ksc * ((TE - 2 * T0) * rdx2 + (TN - 2 * T0) * rdy2) -
-                            (uE * real(0.5) * (TE + T0) - uW * real(0.5) * T0) * rdx -
-                            (vN * real(0.5) * (TN + T0) - vS * real(0.5) * T0) * rdy;
+          const real expl = ns2d_transport_expl<real>(uE, uW, vN, vS, T0, TE, TN, A.ksc, rdx2, rdy2, rdx, rdy);
           Ak[a] = T0 + dt * expl;
         }
         // The stores below must stay BEHIND both rows' loads above: the upper row's TN is row j0 + 2 -- the lower row of the
@@ -794,9 +755,7 @@ __device__ __forceinline__ void fast2_body(const NS2DArgs<real>& A, char* smem, 
           const int c = (i0 + k) * SY + j0 + a;
           const real uE = Ul[c + SY], uW = Ul[c], vN = Vl[c + 1], vS = Vl[c];
           const real T0 = Tl[c], TE = Tl[c + SY], TN = Tl[c + 1];
-          const real expl = A.ksc * ((TE - 2 * T0) * rdx2 + (TN - 2 * T0) * rdy2) -
-                            (uE * real(0.5) * (TE + T0) - uW * real(0.5) * T0) * rdx -
-                            (vN * real(0.5) * (TN + T0) - vS * real(0.5) * T0) * rdy;
+          const real expl = ns2d_transport_expl<real>(uE, uW, vN, vS, T0, TE, TN, A.ksc, rdx2, rdy2, rdx, rdy);
           Ac[a][k] = T0 + dt * expl;
           if constexpr (PARX) {
             if (active && (a == 0 || act1))

@@ -37,6 +37,7 @@
 
 #include "bcn_dpp.h"
 #include "ns2d.h"
+#include "ns2d_cells.h"
 #include "ns2d_device.h"
 #include "ns2d_prm.h"
 #include "ns2d_sched.h"
@@ -461,22 +462,12 @@ __device__ __forceinline__ void fast4_unit(const NS2DArgs<real>& BCN_PRM_A, cons
       const real pc = q.p[0];
       us_o = 0; vs_o = 0;
       if (ok && i >= 2) {
-        real uE = real(0.5) * (uE_ + uc), uW = real(0.5) * (uc + uW_);
-        real uN = real(0.5) * (uN_ + uc), uS = real(0.5) * (uc + uS_);
-        real vN = real(0.5) * (vN_ + q.v[5]), vS = real(0.5) * (vc + vW_);
-        real conv = (uE * uE - uW * uW) * A.rdx + (uN * vN - uS * vS) * A.rdy;
-        real diff = ((uE_ - 2 * uc + uW_) * A.rdx2 + (uN_ - 2 * uc + uS_) * A.rdy2) * A.kmom;
-        real pres = (pc - q.p[1]) * A.rdx;
-        us_o = uc + A.dt * (diff - conv - pres);
+        const NS2DRhs<real> ru = ns2d_pred_u<real>(uc, uE_, uW_, uN_, uS_, vc, vW_, vN_, q.v[5], pc, q.p[1], A.rdx, A.rdy, A.rdx2, A.rdy2, A.kmom);
+        us_o = uc + A.dt * (ru.diff - ru.conv - ru.pres);
       }
       if (ok && j >= 2) {
-        real vE = real(0.5) * (vE_ + vc), vW = real(0.5) * (vc + vW_);
-        real uE = real(0.5) * (uE_ + q.u[5]), uW = real(0.5) * (uc + uS_);
-        real vN = real(0.5) * (vN_ + vc), vS = real(0.5) * (vc + vS_);
-        real conv = (uE * vE - uW * vW) * A.rdx + (vN * vN - vS * vS) * A.rdy;
-        real diff = ((vE_ - 2 * vc + vW_) * A.rdx2 + (vN_ - 2 * vc + vS_) * A.rdy2) * A.kmom;
-        real pres = (pc - q.p[2]) * A.rdy;
-        vs_o = vc + A.dt * (diff - conv - pres + q.s);
+        const NS2DRhs<real> rv = ns2d_pred_v<real>(uc, uE_, uS_, q.u[5], vc, vE_, vW_, vN_, vS_, pc, q.p[2], A.rdx, A.rdy, A.rdx2, A.rdy2, A.kmom);
+        vs_o = vc + A.dt * (rv.diff - rv.conv - rv.pres + q.s);
       }
     };
     if constexpr (CPL <= 2) {
@@ -832,11 +823,9 @@ __device__ __forceinline__ void fast4_unit(const NS2DArgs<real>& BCN_PRM_A, cons
         [&](const F4Tr<real>& q, int j, int i, bool ok) {
           const real uE = q.uE, uW = q.uW, vN = q.vN, vS = q.vS;
           const real Tc_ = q.Tc, TE = q.TE, TN = q.TN;
-          real expl = A.ksc * ((TE - 2 * Tc_) * A.rdx2 + (TN - 2 * Tc_) * A.rdy2) -
-                      (uE * real(0.5) * (TE + Tc_) - uW * real(0.5) * Tc_) * A.rdx -
-                      (vN * real(0.5) * (TN + Tc_) - vS * real(0.5) * Tc_) * A.rdy;
-          real aw = A.dt * (A.ksc * A.rdx2 + real(0.5) * uW * A.rdx);
-          real as = A.dt * (A.ksc * A.rdy2 + real(0.5) * vS * A.rdy);
+          real expl = ns2d_transport_expl<real>(uE, uW, vN, vS, Tc_, TE, TN, A.ksc, A.rdx2, A.rdy2, A.rdx, A.rdy);
+          real aw = ns2d_transport_coef<real>(A.dt, A.ksc, A.rdx2, uW, A.rdx);
+          real as = ns2d_transport_coef<real>(A.dt, A.ksc, A.rdy2, vS, A.rdy);
           real xv = Tc_ + A.dt * expl;
           if (i == 1) { xv = xv + aw * q.TW; aw = 0; }   // west ghost (old BC value) folded in: same operation order
           if (ok) {

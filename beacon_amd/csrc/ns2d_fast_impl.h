@@ -27,6 +27,7 @@
 
 #include "bcn_dpp.h"
 #include "ns2d.h"
+#include "ns2d_cells.h"
 #include "ns2d_device.h"
 #include "ns2d_prm.h"
 #include "ns2d_sched.h"
@@ -447,24 +448,10 @@ __device__ __forceinline__ void fast_body(const NS2DArgs<real>& A, const int w, 
   // one cell of the predictor (rayleigh.py:370-407) without the buoyancy term: u* (complete) and X of v*
   auto pred = [&](const int i, real uc, real uE_, real uW_, real uN_, real uS_, real uSE_, real vc, real vE_, real vW_, real vN_,
                   real vS_, real vNW_, real pc, real pW, real pS, real& us_out, real& vx_out) {
-    {
-      real uE = real(0.5) * (uE_ + uc), uW = real(0.5) * (uc + uW_);
-      real uN2 = real(0.5) * (uN_ + uc), uS2 = real(0.5) * (uc + uS_);
-      real vN2 = real(0.5) * (vN_ + vNW_), vS2 = real(0.5) * (vc + vW_);
-      real conv = (uE * uE - uW * uW) * rdx + (uN2 * vN2 - uS2 * vS2) * rdy;
-      real diff = ((uE_ - 2 * uc + uW_) * rdx2 + (uN_ - 2 * uc + uS_) * rdy2) * A.kmom;
-      real pres = (pc - pW) * rdx;
-      us_out = (i >= 2 && (!DEADC || i <= NX) && active) ? uc + dt * (diff - conv - pres) : real(0);
-    }
-    {
-      real vE = real(0.5) * (vE_ + vc), vW = real(0.5) * (vc + vW_);
-      real uE = real(0.5) * (uE_ + uSE_), uW = real(0.5) * (uc + uS_);
-      real vN2 = real(0.5) * (vN_ + vc), vS2 = real(0.5) * (vc + vS_);
-      real conv = (uE * vE - uW * vW) * rdx + (vN2 * vN2 - vS2 * vS2) * rdy;
-      real diff = ((vE_ - 2 * vc + vW_) * rdx2 + (vN_ - 2 * vc + vS_) * rdy2) * A.kmom;
-      real pres = (pc - pS) * rdy;
-      vx_out = diff - conv - pres;
-    }
+    const NS2DRhs<real> ru = ns2d_pred_u<real>(uc, uE_, uW_, uN_, uS_, vc, vW_, vN_, vNW_, pc, pW, rdx, rdy, rdx2, rdy2, A.kmom);
+    us_out = (i >= 2 && (!DEADC || i <= NX) && active) ? uc + dt * (ru.diff - ru.conv - ru.pres) : real(0);
+    const NS2DRhs<real> rv = ns2d_pred_v<real>(uc, uE_, uS_, uSE_, vc, vE_, vW_, vN_, vS_, pc, pS, rdx, rdy, rdx2, rdy2, A.kmom);
+    vx_out = rv.diff - rv.conv - rv.pres;
   };
   // velocity boundary conditions (rayleigh.py:180-202, the u, v part): they read interior values the corrector has
   // finished and write ghost cells / wall faces that neither the corrector nor the transport step reads
@@ -899,21 +886,17 @@ __device__ __forceinline__ void fast_body(const NS2DArgs<real>& A, const int w, 
           const float rg = 1.f / (float)(itp - 1 - k_prev);                                  \
           if (plan == 1) {                                                            \
             const float room_u = l2u - l2tol_u, rho_u = (l2u - l2u_prev) * rg;               \
-            if (room_u > 0.f) j = (rho_u < 0.f) ? (int)fminf(room_u / -rho_u, (float)JMAX) : JMAX; \
+            j = ns2d_plan_steps(room_u, rho_u, JMAX);                                        \
           } else {                                                                           \
             float l2tl = l2tol_w;                                                            \
             if (A.conv_plan == 3) {   /* the slow-mode guard of the landing this skip ends in; this sweep, itp, is the last evaluated one */ \
-              const float e0 = (float)slow_k[0], fi = (float)itp;                            \
-              const float t0 = 1.f + 2.f * exp2f(e0 + fi * (float)slow_k[1]), t1 = 1.f + 2.f * exp2f(e0 + fi * (float)slow_k[3]); \
-              const float g = fminf(fminf((float)slow_k[2] * t0 * t0, (float)slow_k[4] * t1 * t1) * 1.001f, (float)BCN_CONV_GUARD); \
+            const float g = ns2d_slow_guard<real>(slow_k, itp);                                                                              \
               tolL = A.tol * (real)g;                                                        \
               l2tl = __log2f((float)tolL * 1.003f);                                          \
             }                                                                                \
             const float room_w = l2w - l2tl, rho_w = (l2w - l2w_prev) * rg;                  \
-            int jw = 0;                                                                      \
-            if (room_w > 0.f) jw = (rho_w < 0.f) ? (int)fminf(room_w / -rho_w, (float)JMAX) : JMAX; \
-            j = jw - 1 - (jw >> 4) + A.plan_overshoot;                                                          \
-            j = j > 0 ? j : 0;                                                               \
+            const int jw = ns2d_plan_steps(room_w, rho_w, JMAX);                             \
+            j = ns2d_plan_trim(jw, A.plan_overshoot);                                        \
           }                                                                                  \
         }                                                                                    \
         j = __builtin_amdgcn_readfirstlane(j);                                               \
@@ -1003,23 +986,19 @@ __device__ __forceinline__ void fast_body(const NS2DArgs<real>& A, const int w, 
         if (plan == 1) {                                                                     \
           const float l2u1 = __log2f((float)read_lane(esum, 47)), l2u2 = __log2f((float)read_lane(esum, 63)); \
           const float room_u = l2u2 - l2tol_u, rho_u = l2u2 - l2u1;                          \
-          if (room_u > 0.f) j = (rho_u < 0.f) ? (int)fminf(room_u / -rho_u, (float)JMAX) : JMAX; \
+          j = ns2d_plan_steps(room_u, rho_u, JMAX);                                          \
         } else {                                                                             \
           const float l2w1 = __log2f((float)err1), l2w2 = __log2f((float)err2);              \
           float l2tl = l2tol_w;                                                              \
           if (A.conv_plan == 3) {   /* the slow-mode guard of the landing this skip ends in; the last evaluated sweep is itp */ \
-            const float e0 = (float)slow_k[0], fi = (float)itp;                              \
-            const float t0 = 1.f + 2.f * exp2f(e0 + fi * (float)slow_k[1]), t1 = 1.f + 2.f * exp2f(e0 + fi * (float)slow_k[3]); \
-            const float g = fminf(fminf((float)slow_k[2] * t0 * t0, (float)slow_k[4] * t1 * t1) * 1.001f, (float)BCN_CONV_GUARD); \
+          const float g = ns2d_slow_guard<real>(slow_k, itp);                                                                   \
             tolL = A.tol * (real)g;                                                          \
             l2tl = __log2f((float)tolL * 1.003f);                                            \
           }                                                                                  \
           const float room_w = l2w2 - l2tl, rho_w = l2w2 - l2w1;                             \
           if (SPEC && tid == 0) slow_k[5] = (real)-rho_w;   /* the decay per sweep, for the next solve's opening */ \
-          int jw = 0;                                                                        \
-          if (room_w > 0.f) jw = (rho_w < 0.f) ? (int)fminf(room_w / -rho_w, (float)JMAX) : JMAX; \
-          j = jw - 1 - (jw >> 4) + A.plan_overshoot;                                         \
-          j = j > 0 ? j : 0;                                                                 \
+          const int jw = ns2d_plan_steps(room_w, rho_w, JMAX);                                 \
+          j = ns2d_plan_trim(jw, A.plan_overshoot);                                            \
         }                                                                                    \
         j = __builtin_amdgcn_readfirstlane(j) & ~1;                                          \
         k_prev = itp;                                                                        \
@@ -1178,9 +1157,7 @@ __device__ __forceinline__ void fast_body(const NS2DArgs<real>& A, const int w, 
         } else {
           T0 = Tl[c]; TE = Tl[c + SY]; TN = Tl[c + 1];
         }
-        const real expl = A.ksc * ((TE - 2 * T0) * rdx2 + (TN - 2 * T0) * rdy2) -
-                          (uE * real(0.5) * (TE + T0) - uW * real(0.5) * T0) * rdx -
-                          (vN * real(0.5) * (TN + T0) - vS * real(0.5) * T0) * rdy;
+        const real expl = ns2d_transport_expl<real>(uE, uW, vN, vS, T0, TE, TN, A.ksc, rdx2, rdy2, rdx, rdy);
         Ac[k] = T0 + dt * expl;
       }
       if (it + 1 < it_end && status == 0) {

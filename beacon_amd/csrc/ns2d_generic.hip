@@ -19,6 +19,7 @@
 #include <stdlib.h>
 
 #include "ns2d.h"
+#include "ns2d_cells.h"
 #include "ns2d_device.h"
 #include "params.h"
 
@@ -331,11 +332,9 @@ __global__ __launch_bounds__(NT) void ns2d_generic_step(NS2DArgs<real> A, const 
         const int c = j * sx + i;
         const real uE = u[c + 1], uW = u[c], vN = v[c + sx], vS = v[c];
         const real Tc_ = S[c], TE = S[c + 1], TN = S[c + sx];
-        real expl = A.ksc * ((TE - 2 * Tc_) * A.rdx2 + (TN - 2 * Tc_) * A.rdy2) -
-                    (uE * real(0.5) * (TE + Tc_) - uW * real(0.5) * Tc_) * A.rdx -
-                    (vN * real(0.5) * (TN + Tc_) - vS * real(0.5) * Tc_) * A.rdy;
-        real aw = A.dt * (A.ksc * A.rdx2 + real(0.5) * uW * A.rdx);
-        real as = A.dt * (A.ksc * A.rdy2 + real(0.5) * vS * A.rdy);
+        real expl = ns2d_transport_expl<real>(uE, uW, vN, vS, Tc_, TE, TN, A.ksc, A.rdx2, A.rdy2, A.rdx, A.rdy);
+        real aw = ns2d_transport_coef<real>(A.dt, A.ksc, A.rdx2, uW, A.rdx);
+        real as = ns2d_transport_coef<real>(A.dt, A.ksc, A.rdy2, vS, A.rdy);
         // the explicit part is written after the barrier below (Z aliases phi, read above only)
         X[c] = Tc_ + A.dt * expl;
         Y[c] = aw;

@@ -16,7 +16,16 @@ under test and expects the same table: the plain units kept their code.  --asm-d
 compiles the parameter units (ns2d_fast_prm.hip, ns2d_fast_prm_f64.hip, ns2d_fast2_prm.hip) and the parameter plugins of
 PLUGIN_GRIDS as well and writes every table-reading kernel next to its plain sibling: VGPRs, SGPRs, scratch bytes, occupancy
 (the figures of -Rpass-analysis=kernel-resource-usage, read from the assembly's metadata and its "; Occupancy:" comments), the
-number of instruction lines, and the scalar loads of the unit (s_load_*: the table reads are among them)."""
+number of instruction lines, and the scalar loads of the unit (s_load_*: the table reads are among them).
+
+    python scripts/params_fast_kernels.py --compare PARENT_ROOT [--jobs N] [--only TEXT] [--asm-dir DIR] [--out FILE.md]
+
+compiles every object of compare_objects() -- the generic unit, the register-resident units and their parameter twins, the plugin
+grids of COMPARE_GRIDS and the parameter plugins of jit.PRM_TEST_GRIDS -- for this tree (--root) and for the checkout at
+PARENT_ROOT (a `git worktree` of the parent commit) and reports, per object and per kernel symbol, `identical` or the resource
+rows that differ: whole-file identity first, else per-function bodies with their local labels renumbered.  What a refactoring of
+the kernel sources that must not change the code is checked with.  --only: the objects whose name contains TEXT; with --asm-dir
+the parent's files already there (DIR/parent) are reused.  Exit status 1 unless every kernel is identical."""
 import argparse
 import importlib.util
 import json
@@ -29,6 +38,11 @@ import tempfile
 UNITS = ("ns2d_fast.hip", "ns2d_fast_f64.hip", "ns2d_fast2.hip")
 # one plugin grid per family (beacon_amd/jit.py: TEST_GRIDS): rows 1, rows 2, rows 4
 PLUGIN_GRIDS = ((75, 50, False, 0), (100, 110, False, 1), (50, 150, False, 0))
+# --compare: every unit that includes the 2D cell arithmetic, and plugin grids per family -- one row per lane (float32, float64,
+# float64 with dead columns), two rows (mixing, float64 odd ny on the global scratch, float64 mixing), the hybrid
+COMPARE_UNITS = ("ns2d_generic.hip",) + UNITS + ("ns2d_fast_prm.hip", "ns2d_fast_prm_f64.hip", "ns2d_fast2_prm.hip")
+COMPARE_GRIDS = ((75, 50, False, 0), (75, 50, True, 0), (52, 50, True, 0), (100, 110, False, 1), (50, 75, True, 0),
+                 (100, 105, True, 1), (50, 150, False, 0), (50, 150, True, 0), (100, 200, False, 1))
 
 
 def _load(root, name):
@@ -152,16 +166,87 @@ def table_of(root, asm_dir):
     return out
 
 
+def compare_objects(jit):
+    """[(name, compile(build, out_path) -> normalised assembly)] of --compare"""
+    objs = [(u, lambda b, o, u=u: unit_asm(b, u, o)) for u in COMPARE_UNITS]
+    for grids, extra, tail in ((COMPARE_GRIDS, None, ""), (jit.PRM_TEST_GRIDS, {"BCN_JIT_PRM": 1}, " prm")):
+        for g in grids:
+            objs.append((plugin_key(g) + tail, lambda b, o, g=g, extra=extra: plugin_asm(b, plugin_defs(jit.choose, *g, extra=extra), o)))
+    return objs
+
+
+def function_bodies(text):
+    """{kernel symbol: its instructions, local labels renumbered in order of appearance}"""
+    out = {}
+    for name in kernel_table(text):
+        body = re.search(r"^%s:[^\n]*\n(.*?)^\.Lfunc_end" % re.escape(name), text, flags=re.M | re.S).group(1)
+        seen = {}
+        out[name] = re.sub(r"\.L[A-Za-z_]+\d+(?:_\d+)?", lambda m: seen.setdefault(m.group(0), ".L%d" % len(seen)), body)
+    return out
+
+
+def compare(root, parent, asm_dir, jobs, only):
+    """(markdown report, all identical) of this tree against the checkout at `parent`"""
+    from concurrent.futures import ThreadPoolExecutor
+    here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if here not in sys.path:
+        sys.path.insert(0, here)
+    from beacon_amd import jit
+    objs = [o for o in compare_objects(jit) if only is None or only in o[0]]
+    sides = {"parent": _load(parent, "build"), "this": _load(root, "build")}
+    for side in sides:
+        os.makedirs(os.path.join(asm_dir, side), exist_ok=True)
+
+    def one(job):
+        side, (name, fn) = job
+        path = os.path.join(asm_dir, side, name.replace(" ", "_") + ".s")
+        if side == "parent" and os.path.exists(path):
+            return normalise(open(path).read())
+        return fn(sides[side], path)
+    jobs_ = [(side, o) for o in objs for side in ("parent", "this")]
+    with ThreadPoolExecutor(max_workers=max(1, min(jobs, 16))) as ex:
+        texts = dict(zip(((s, o[0]) for s, o in jobs_), ex.map(one, jobs_)))
+    lines = ["| object | kernel | code |", "|---|---|---|"]
+    same = True
+    for name, _ in objs:
+        t0, t1 = texts[("parent", name)], texts[("this", name)]
+        k0, k1 = kernel_table(t0), kernel_table(t1)
+        b0, b1 = (None, None) if t0 == t1 else (function_bodies(t0), function_bodies(t1))
+        lines.append("| %s | whole file, %d kernels | %s |" % (name, len(k1), "identical" if t0 == t1 else "differs"))
+        for k in sorted(set(k0) | set(k1)):
+            if k not in k0 or k not in k1:
+                verdict = "only in the parent" if k in k0 else "only in this tree"
+            elif t0 == t1 or b0[k] == b1[k]:
+                verdict = "identical"
+            else:
+                verdict = "DIFFERS: " + ", ".join("%s %d -> %d" % (f, k0[k][f], k1[k][f]) for f in ("vgpr", "sgpr", "scratch", "lds", "insts"))
+            same = same and verdict == "identical"
+            lines.append("| %s | `%s` | %s |" % (name, k, verdict))
+    lines.append("")
+    lines.append("%d objects: %s" % (len(objs), "every kernel identical to the parent's" if same else "NOT all identical"))
+    return "\n".join(lines) + "\n", same
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     ap.add_argument("--out", default=None)
     ap.add_argument("--asm-dir", default=None)
     ap.add_argument("--resources", default=None, help="write the plain / parameter resource table (markdown rows) to this file")
+    ap.add_argument("--compare", default=None, metavar="PARENT_ROOT", help="report, per kernel, whether this tree's code is the parent checkout's")
+    ap.add_argument("--jobs", type=int, default=8, help="--compare: compiles at a time (at most 16)")
+    ap.add_argument("--only", default=None, help="--compare: only the objects whose name contains this text")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         asm_dir = a.asm_dir or tmp
         os.makedirs(asm_dir, exist_ok=True)
+        if a.compare:
+            report, same = compare(os.path.abspath(a.root), os.path.abspath(a.compare), asm_dir, a.jobs, a.only)
+            if a.out:
+                with open(a.out, "w") as fh:
+                    fh.write(report)
+            sys.stdout.write(report)
+            sys.exit(0 if same else 1)
         if a.resources:
             with open(a.resources, "w") as fh:
                 fh.write(resources(os.path.abspath(a.root), asm_dir))
