@@ -4,7 +4,9 @@
 
 namespace bcn_dpp {
 
-// ---- DPP primitives (verified on gfx950 by scripts/dpp_test.hip) ----------------------------
+// ---- DPP primitives.  What stands behind them: tests/test_isa_hazards_host.py (the wait states in front of every DPP read, in
+// the disassembly of every built kernel) and, on gfx950, the float32 kernels against the float64 oracle -- from rest in
+// tests/test_gpu_parity.py, from energetic asymmetric flow in tests/test_gpu_energetic.py ----------------------------
 template <int CTRL, int RM, int BM, bool BC>
 __device__ __forceinline__ float dpp(float oldv, float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, oldv),

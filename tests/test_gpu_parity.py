@@ -2823,7 +2823,8 @@ F32[("jit_oracle", 4, 1)] = f32tol(1.5e-5, 9.8e-6, 1.4e-3, 8.8e-6, 9.3e-6, 1.9e-
 
 
 def _oracle_replica(kind, L, H, kw, ndt, st0, a):
-    """One replica through the float64 C oracle: (fields [4, nx+2, ny+2], obs, rwd, sweeps per timestep)."""
+    """One replica through the float64 C oracle: (fields [4, nx+2, ny+2], obs, rwd, sweeps per timestep).  mixing: from reset(),
+    or from st0 where one is given."""
     if kind == 0:
         o = O.rayleigh(init=False, L=L, H=H, **kw)
         o.cfg.ndt_act = ndt
@@ -2834,6 +2835,8 @@ def _oracle_replica(kind, L, H, kw, ndt, st0, a):
         o = O.mixing(L=L, H=H, **kw)
         o.cfg.ndt_act = ndt
         o.reset()
+        if st0 is not None:
+            o.st[:4] = st0
         ob, rw, _, _, _ = o.step(int(a))
     return np.array(o.st[:4], dtype=np.float64), np.array(ob, dtype=np.float64), float(rw), np.array(o.itp, dtype=np.int64)
 
