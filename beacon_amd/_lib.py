@@ -77,6 +77,13 @@ class SnapshotSeg(C.Structure):
                 ("row_elems", C.c_int64)]
 
 
+class RenderCfg(C.Structure):
+    """bcn_render_cfg: what a frame shows (plane, scale or width / height, strip, ranges)."""
+    _fields_ = [("plane", C.c_int32), ("scale", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("strip", C.c_int32),
+                ("has_range", C.c_int32), ("lo", C.c_double), ("hi", C.c_double), ("ref", C.c_double)]
+
+
+PLANES = {"scalar": 0, "u": 1, "v": 2, "p": 3}           # include/beacon_hip.h: BCN_PLANE_*
 SNAP_REAL, SNAP_I32, SNAP_U32, SNAP_U8 = 0, 1, 2, 3      # include/beacon_hip.h: BCN_SNAP_*
 SNAP_F64, SNAP_I64 = 4, 5                                # (bcn_episode_layout only)
 RO_FINAL_OBS, RO_JETS = 1, 2                             # include/beacon_hip.h: BCN_RO_*
@@ -149,6 +156,8 @@ SIGNATURES = {
     "bcn_rollout_begin": (C.c_int, [vp, vp, vp, vp, vp]),
     "bcn_rollout_record": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]),
     "bcn_rollout_gae": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, vp]),
+    "bcn_render_shape": (C.c_int, [vp, C.POINTER(RenderCfg), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bcn_render": (C.c_int, [vp, C.POINTER(RenderCfg), vp, vp, C.c_int, vp, vp]),
     "bcn_n_params": (C.c_int, [vp]),
     "bcn_param_name": (C.c_char_p, [vp, C.c_int]),
     "bcn_set_params": (C.c_int, [vp, C.POINTER(C.c_double), vp]),

@@ -52,7 +52,10 @@ FILE_FLAGS = {"ns2d_fast.hip": ["-fno-slp-vectorize", "-ffp-contract=on", "-O2"]
               "ode_f64.hip": ["-ffp-contract=off"],
               # the GAE recurrence in the operation order its documentation states, one rounding per operation (the float64 NumPy
               # restatement in the tests is the same sequence)
-              "rollout.hip": ["-ffp-contract=off"]}
+              "rollout.hip": ["-ffp-contract=off"],
+              # the frame kernels equal their NumPy restatement byte for byte: one rounding per operation, and the float division the
+              # correctly rounded one whatever the toolchain's default becomes
+              "render.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]}
 
 
 # the on-demand kernels (beacon_amd/jit.py: csrc/jit/ns2d_jit.hip, any family, any precision): the flags their verification and

@@ -18,6 +18,7 @@
 #include "shkadov_jets.h"
 #include "normalize.h"
 #include "rollout.h"
+#include "render.h"
 
 static thread_local char g_err[512] = "";
 
@@ -846,6 +847,67 @@ void params_table(bcn_env_t h, const double* values, std::vector<char>& out) {
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// frames (render.h): what a frame of this handle shows, from the handle's own arrays and a bcn_render_cfg
+// ------------------------------------------------------------------------------------------
+// Checks the cfg against the handle and fills everything of the argument block but the caller's pointers.  The defaults are the
+// reference's axes; the narrowed range must still be a range (the kernels divide by hi - lo in the env's type).
+template <typename real>
+int render_fill(const char* who, bcn_env_t h, const bcn_render_cfg* c, RenderArgs& a) {
+  a = RenderArgs{};
+  a.batch = h->batch; a.f64 = h->dtype == BCN_F64;
+  double lo = c->lo, hi = c->hi, ref = c->ref;
+  int panel_h = 0;
+  if (h->kind == BCN_RAYLEIGH || h->kind == BCN_MIXING) {
+    auto* e = static_cast<NS2DEnv<real>*>(h);
+    if (c->plane < BCN_PLANE_SCALAR || c->plane > BCN_PLANE_P) { bcn_set_error("%s: plane %d; BCN_PLANE_SCALAR, _U, _V or _P", who, c->plane); return BCN_ERR_ARG; }
+    if (c->scale < 1) { bcn_set_error("%s: scale %d; at least 1", who, c->scale); return BCN_ERR_ARG; }
+    if ((long long)e->a.nx * c->scale > BCN_RENDER_MAX_W) { bcn_set_error("%s: %d cells x scale %d: a frame row holds at most %d pixels", who, e->a.nx, c->scale, BCN_RENDER_MAX_W); return BCN_ERR_ARG; }
+    if ((long long)e->a.ny * c->scale > (1 << 20)) { bcn_set_error("%s: %d cells x scale %d pixel rows", who, e->a.ny, c->scale); return BCN_ERR_ARG; }
+    if (!c->has_range) {
+      if (c->plane != BCN_PLANE_SCALAR) { bcn_set_error("%s: the planes u, v, p have no default range: set has_range, lo, hi", who); return BCN_ERR_ARG; }
+      lo = h->kind == BCN_RAYLEIGH ? (double)e->a.Tc : 0.0;          // rayleigh.py / mixing.py render(): vmin, vmax of imshow
+      hi = h->kind == BCN_RAYLEIGH ? (double)e->a.Th : (double)e->a.C0;
+    }
+    const real* plane[4] = {e->a.S, e->a.u, e->a.v, e->a.p};
+    a.field = plane[c->plane]; a.rep_stride = (size_t)e->a.ncell;
+    a.nx = e->a.nx; a.ny = e->a.ny; a.scale = c->scale;
+    a.W = a.nx * a.scale; panel_h = a.ny * a.scale;
+    if (h->kind == BCN_RAYLEIGH) { a.ctrl = e->a.a_last; a.n_ctrl = e->a.n_sgts; }
+    else { a.ctrl = e->a.ia_last; a.ctrl_int = 1; a.n_ctrl = 4; }
+  } else if (h->kind == BCN_BURGERS || h->kind == BCN_SHKADOV || h->kind == BCN_SLOSHING) {
+    auto* e = static_cast<Env1D<real>*>(h);
+    const int W = c->width == 0 ? 512 : c->width, H = c->height == 0 ? 128 : c->height;
+    if (W < 1 || W > BCN_RENDER_MAX_W || H < 1 || H > BCN_RENDER_MAX_H) {
+      bcn_set_error("%s: %d x %d pixels; 1 .. %d wide, 1 .. %d high", who, W, H, BCN_RENDER_MAX_W, BCN_RENDER_MAX_H);
+      return BCN_ERR_ARG;
+    }
+    if (!c->has_range) {
+      if (h->kind == BCN_BURGERS) {       // burgers.py render(): u_target -+ 2 sigma; sigma is the noise setting of the handle
+        if (!(e->a.nsigma > 0)) { bcn_set_error("%s: burgers has a default range only with inlet noise (bcn_set_noise): set has_range, lo, hi, ref", who); return BCN_ERR_ARG; }
+        lo = (double)e->a.u_target - 2.0 * (double)e->a.nsigma; hi = (double)e->a.u_target + 2.0 * (double)e->a.nsigma; ref = (double)e->a.u_target;
+      } else if (h->kind == BCN_SHKADOV) { lo = 0.0; hi = 2.0; ref = 1.0; }
+      else { lo = 0.25; hi = 1.75; ref = 1.0; }
+    }
+    a.line = 1;
+    a.field = e->a.f0 + (h->kind == BCN_SLOSHING ? 1 : 0);   // sloshing: h[1 .. nx] between the ghost cells
+    a.rep_stride = (size_t)e->a.n; a.ns = e->a.nx;
+    a.W = W; panel_h = H;
+    a.ctrl = e->a.a_last; a.n_ctrl = e->nact;
+    if (!isfinite(ref)) { bcn_set_error("%s: ref %g is not finite", who, ref); return BCN_ERR_ARG; }
+  } else {
+    bcn_set_error("%s: lorenz and vortex keep no trajectory on the device: nothing to draw", who);
+    return BCN_ERR_UNSUPPORTED;
+  }
+  if (!isfinite(lo) || !isfinite(hi) || !(hi > lo) || !((real)hi > (real)lo)) { bcn_set_error("%s: range (%g, %g): hi must exceed lo, also in the handle's precision", who, lo, hi); return BCN_ERR_ARG; }
+  const int strip = c->strip < 0 ? panel_h / 8 : c->strip;
+  if (strip > BCN_RENDER_MAX_H) { bcn_set_error("%s: strip of %d rows; at most %d", who, strip, BCN_RENDER_MAX_H); return BCN_ERR_ARG; }
+  if (a.n_ctrl < 1 || a.n_ctrl > BCN_RENDER_MAX_CTRL) { bcn_set_error("%s: %d controls; 1 .. %d", who, a.n_ctrl, BCN_RENDER_MAX_CTRL); return BCN_ERR_ARG; }
+  a.H = panel_h; a.strip = strip;
+  a.lo = lo; a.hi = hi; a.ref = ref;
+  return BCN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1430,6 +1492,28 @@ int bcn_rollout_gae(bcn_env_t h, void* ro_buf_dev, const void* values_dev, const
   a.gamma = gamma; a.lam = lam;
   DeviceGuard g(h->device);
   return rollout_gae_launch(a, static_cast<hipStream_t>(stream));
+}
+// ---- frames (render.h) ------------------------------------------------------------------------------
+int bcn_render_shape(bcn_env_t h, const bcn_render_cfg* cfg, int* H_px, int* W_px) {
+  if (!h || !cfg || !H_px || !W_px) { bcn_set_error("bcn_render_shape: null handle/argument"); return BCN_ERR_ARG; }
+  RenderArgs a;
+  const int rc = BCN_BY_DTYPE(h->dtype, render_fill, "bcn_render_shape", h, cfg, a);
+  if (rc) return rc;
+  *H_px = a.H + a.strip; *W_px = a.W;
+  return BCN_OK;
+}
+int bcn_render(bcn_env_t h, const bcn_render_cfg* cfg, const uint8_t* lut_dev, const int32_t* replicas_dev, int n, uint8_t* rgb_dev, void* stream) {
+  if (!h || !cfg) { bcn_set_error("bcn_render: null handle/cfg"); return BCN_ERR_ARG; }
+  RenderArgs a;
+  const int rc = BCN_BY_DTYPE(h->dtype, render_fill, "bcn_render", h, cfg, a);
+  if (rc) return rc;
+  if (n < 0 || (!replicas_dev && n != h->batch)) { bcn_set_error("bcn_render: n = %d frames; n >= 0, and the batch (%d) without an index list", n, h->batch); return BCN_ERR_ARG; }
+  if (n > 0 && !rgb_dev) { bcn_set_error("bcn_render: null frame buffer"); return BCN_ERR_ARG; }
+  if (!a.line && (!lut_dev || (reinterpret_cast<uintptr_t>(lut_dev) & 3) != 0)) { bcn_set_error("bcn_render: the field panel needs a 4-byte aligned colour table"); return BCN_ERR_ARG; }
+  if ((reinterpret_cast<uintptr_t>(replicas_dev) & 3) != 0) { bcn_set_error("bcn_render: the index list must be 4-byte aligned"); return BCN_ERR_ARG; }
+  a.lut = lut_dev; a.replicas = replicas_dev; a.n = n; a.rgb = rgb_dev;
+  DeviceGuard g(h->device);
+  return render_launch(a, static_cast<hipStream_t>(stream));
 }
 const char* bcn_kernel_name(bcn_env_t h) { return h ? h->kernel_name() : ""; }
 int bcn_kernel_shape(bcn_env_t h, int* cells_per_thread, int* threads) {

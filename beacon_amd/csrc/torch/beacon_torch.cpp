@@ -11,6 +11,8 @@
 //                          int T, int flags) -> ()
 //   beacon::rollout_gae(int handle, Tensor ro_buf, Tensor values, Tensor last_value, Tensor? final_values, int T, int flags, int cols, float gamma,
 //                       float lam) -> ()
+//   beacon::render(int handle, Tensor rgb, Tensor? lut, Tensor? replicas, int plane, int scale, int width, int height, int strip, int has_range,
+//                  float lo, float hi, float ref) -> ()
 // Each op is ONE dispatcher call that takes device tensors, reads torch's current HIP stream in C++ and forwards to the
 // bcn_* entry point of libbeacon_hip.so -- no ctypes marshalling, no Python-side stream query (what the per-call host cost of
 // the ctypes binding was made of: scripts/host_cost.py), and an op CUDA-graph capture and fake-tensor tracing can see (Meta kernels below).  The ops
@@ -303,6 +305,41 @@ void rollout_gae(int64_t h_, const Tensor& ro_buf, const Tensor& values, const T
         "bcn_rollout_gae");
 }
 
+// ---- frames (include/beacon_hip.h: bcn_render) ---------------------------------------------------------------------------
+// rgb: uint8 [n, H_px, W_px, 3] for the shape bcn_render_shape gives; lut: uint8 [256, 3]; replicas: int32 [n] (None: n is the batch)
+void render(int64_t h_, const Tensor& rgb, OptT lut, OptT replicas, int64_t plane, int64_t scale, int64_t width, int64_t height, int64_t strip,
+            int64_t has_range, double lo, double hi, double ref) {
+  bcn_env_t h = H(h_);
+  TORCH_CHECK(h, "render: null handle");
+  for (int64_t v : {plane, scale, width, height, strip}) TORCH_CHECK(v >= INT32_MIN && v <= INT32_MAX, "render: argument ", v, " out of range");
+  bcn_render_cfg cfg;
+  cfg.plane = (int32_t)plane; cfg.scale = (int32_t)scale; cfg.width = (int32_t)width; cfg.height = (int32_t)height; cfg.strip = (int32_t)strip;
+  cfg.has_range = has_range != 0; cfg.lo = lo; cfg.hi = hi; cfg.ref = ref;
+  int H_px = 0, W_px = 0;
+  check(bcn_render_shape(h, &cfg, &H_px, &W_px), "bcn_render_shape");
+  on_device(rgb, h, "rgb");
+  TORCH_CHECK(rgb.scalar_type() == at::kByte, "rgb: uint8 tensor expected");
+  TORCH_CHECK(rgb.dim() == 4 && rgb.size(1) == H_px && rgb.size(2) == W_px && rgb.size(3) == 3, "rgb: [n, ", H_px, ", ", W_px, ", 3] expected, got ",
+              rgb.sizes());
+  const int64_t n = rgb.size(0);
+  TORCH_CHECK(n <= INT32_MAX, "rgb: ", n, " frames");
+  const int32_t* idx = nullptr;
+  if (replicas.has_value()) {
+    on_device(*replicas, h, "replicas");
+    TORCH_CHECK(replicas->scalar_type() == at::kInt && replicas->numel() == n, "replicas: int32 tensor of ", n, " indices expected");
+    idx = replicas->data_ptr<int32_t>();
+  } else {
+    TORCH_CHECK(n == bcn_batch(h), "rgb: ", n, " frames for a batch of ", bcn_batch(h), " need replicas");
+  }
+  const uint8_t* table = nullptr;
+  if (lut.has_value()) {
+    on_device(*lut, h, "lut");
+    TORCH_CHECK(lut->scalar_type() == at::kByte && lut->numel() == 768, "lut: uint8 [256, 3] expected");
+    table = lut->data_ptr<uint8_t>();
+  }
+  check(bcn_render(h, &cfg, table, idx, (int)n, rgb.data_ptr<uint8_t>(), stream_of(rgb)), "bcn_render");
+}
+
 // Meta (fake-tensor) kernels: the ops return nothing and their outputs keep their shapes, so tracing needs no more than this.
 void reset2_meta(int64_t, const Tensor&) {}
 void reset3_meta(int64_t, OptT, const Tensor&) {}
@@ -319,6 +356,7 @@ void normalize_meta(int64_t, const Tensor&, const Tensor&, OptT, OptT, int64_t, 
 void rollout_begin_meta(int64_t, const Tensor&, const Tensor&, OptT) {}
 void rollout_record_meta(int64_t, const Tensor&, const Tensor&, OptT, OptT, OptT, OptT, OptT, int64_t, int64_t) {}
 void rollout_gae_meta(int64_t, const Tensor&, const Tensor&, const Tensor&, OptT, int64_t, int64_t, int64_t, double, double) {}
+void render_meta(int64_t, const Tensor&, OptT, OptT, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, double, double, double) {}
 
 }  // namespace
 
@@ -358,6 +396,8 @@ TORCH_LIBRARY(beacon, m) {
         "Tensor? mask, int T, int flags) -> ()");
   m.def("rollout_gae(int handle, Tensor(a!) ro_buf, Tensor values, Tensor last_value, Tensor? final_values, int T, int flags, int cols, "
         "float gamma, float lam) -> ()");
+  m.def("render(int handle, Tensor(a!) rgb, Tensor? lut, Tensor? replicas, int plane, int scale, int width, int height, int strip, "
+        "int has_range, float lo, float hi, float ref) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(beacon, CUDA, m) {
@@ -384,6 +424,7 @@ TORCH_LIBRARY_IMPL(beacon, CUDA, m) {
   m.impl("rollout_begin", &rollout_begin);
   m.impl("rollout_record", &rollout_record);
   m.impl("rollout_gae", &rollout_gae);
+  m.impl("render", &render);
 }
 
 TORCH_LIBRARY_IMPL(beacon, Meta, m) {
@@ -410,4 +451,5 @@ TORCH_LIBRARY_IMPL(beacon, Meta, m) {
   m.impl("rollout_begin", &rollout_begin_meta);
   m.impl("rollout_record", &rollout_record_meta);
   m.impl("rollout_gae", &rollout_gae_meta);
+  m.impl("render", &render_meta);
 }

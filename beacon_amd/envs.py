@@ -31,7 +31,7 @@ def packaged_init(name):
 
 
 class _Single(object):
-    metadata = {"render.modes": ["human"]}
+    metadata = {"render.modes": ["human", "rgb_array"]}
 
     def _np(self, t):
         return t.detach().cpu().numpy().astype(np.float64)
@@ -43,7 +43,13 @@ class _Single(object):
     _render = None      # function of beacon_amd.render
 
     def render(self, mode="human", show=False, dump=True):
-        """Host-side frame + text dumps in the reference's render/ layout (beacon_amd/render.py)."""
+        """Host-side frame + text dumps in the reference's render/ layout (beacon_amd/render.py).  mode="rgb_array" (Gym's
+        convention) instead returns the frame the device paints (VecEnv.renderer) as a uint8 [H, W, 3] NumPy array and writes
+        no file; every other mode does the former."""
+        if mode == "rgb_array":
+            if getattr(self, "_rgb", None) is None:
+                self._rgb = self.vec.renderer()
+            return self._rgb.draw()[0].cpu().numpy()
         from . import render as R
         getattr(R, self._render)(self, show, dump)
 

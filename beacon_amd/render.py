@@ -10,6 +10,21 @@ import os
 import numpy as np
 
 
+# the eleven ColorBrewer RdBu anchors (red to blue), the data behind matplotlib's "RdBu"
+_RDBU = ((103, 0, 31), (178, 24, 43), (214, 96, 77), (244, 165, 130), (253, 219, 199), (247, 247, 247), (209, 229, 240),
+         (146, 197, 222), (67, 147, 195), (33, 102, 172), (5, 48, 97))
+
+
+def colormap_lut():
+    """The default colour table of the device frames (VecEnv.renderer), uint8 [256, 3]: RdBu reversed -- the reference's
+    cmap='RdBu_r' -- as linear interpolation of the anchors over 256 points in float64, (x * 255) truncated.  Within one level of
+    matplotlib's own table; matplotlib is not needed."""
+    a = np.asarray(_RDBU[::-1], dtype=np.float64) / 255.0
+    x = np.linspace(0.0, 1.0, 256)
+    xa = np.linspace(0.0, 1.0, len(a))
+    return np.stack([(np.interp(x, xa, a[:, k]) * 255.0).astype(np.uint8) for k in range(3)], axis=1)
+
+
 def _plt():
     try:
         import matplotlib

@@ -1,6 +1,6 @@
 """The thin PyTorch-ROCm extension over the C ABI: torch.library ops `torch.ops.beacon.<env>_{step,reset}`.
 
-csrc/torch/beacon_torch.cpp (host code, g++) registers seventeen ops (the fourteen reset / step ops, snapshot_save / snapshot_load and episode_track) that take device tensors, read torch's current HIP stream
+csrc/torch/beacon_torch.cpp (host code, g++) registers its ops (the reset / step ops of every env and the state, bookkeeping and render ops: the list at the top of the source) that take device tensors, read torch's current HIP stream
 in C++ and call the bcn_* entry points of libbeacon_hip.so (include/beacon_hip.h).  beacon_amd.vec uses them for reset() /
 step() when this library is present -- one dispatcher call per step instead of seven c_void_p conversions and a Python-side
 stream query -- and falls back to the ctypes binding of the SAME C ABI when it is not (no g++ / no torch headers): either

@@ -102,6 +102,7 @@ _JET_OPS = ("shkadov_jet_rewards",)                                           # 
 _ALL_OPS = _OPS + _ODE_OPS + _STATE_OPS + _EPISODE_OPS + _WARM_OPS + _JET_OPS
 _NORM_OPS = ("normalize",)                                                    # every env (csrc/normalize.hip)
 _ROLLOUT_OPS = ("rollout_begin", "rollout_record", "rollout_gae")             # every env (csrc/rollout.hip); resolved at the first attach
+_RENDER_OPS = ("render",)                                                     # the grid envs (csrc/render.hip); resolved by the first renderer()
 
 
 def _op_table():
@@ -125,6 +126,73 @@ def _rollout_tables(lib, with_ops):
         ext = torch_ext.load()
         ops = None if ext is None else {n: getattr(ext, n).default for n in _ROLLOUT_OPS}
     return ops, {n: getattr(lib, "bcn_" + n) for n in _ROLLOUT_OPS}
+
+
+def _render_tables(lib, with_ops):
+    """({name: torch op} or None, {name: bcn_<name>}) of _RENDER_OPS, as _rollout_tables: merged into an env's tables by its first
+    renderer()."""
+    ops = None
+    if with_ops:
+        from . import torch_ext
+        ext = torch_ext.load()
+        ops = None if ext is None or not hasattr(ext, "render") else {n: getattr(ext, n).default for n in _RENDER_OPS}
+    return ops, {n: getattr(lib, "bcn_" + n) for n in _RENDER_OPS}
+
+
+class Renderer(object):
+    """RGB frames of `n` replicas of one VecEnv, drawn on the device (VecEnv.renderer; csrc/render.hip; the pixel rules:
+    include/beacon_hip.h, bcn_render).  Owns `replicas` (int32 [n] on the device, or None: every replica in order), `lut` (uint8
+    [256, 3], the field panel's colour table) and `frames`, uint8 [n, H_px, W_px, 3]; `shape` is (H_px, W_px).  Bookkeeping, like a
+    Rollout: in no Snapshot; it reads the env's handle at every draw(), so it survives set_ndt_act."""
+
+    def __init__(self, env, cfg, replicas, lut):
+        self.env, self.cfg = env, cfg
+        H, W = C.c_int(0), C.c_int(0)
+        _lib.check(env.lib.bcn_render_shape(env.h, C.byref(cfg), C.byref(H), C.byref(W)))
+        self.shape = (int(H.value), int(W.value))
+        self.replicas = None
+        if replicas is not None:
+            if torch.is_tensor(replicas) and replicas.device.type == "cuda":      # not read on the host: the kernel skips bad indices
+                idx = replicas
+            else:
+                host = np.asarray(replicas.cpu() if torch.is_tensor(replicas) else replicas, dtype=np.int64).reshape(-1)
+                if host.size and (host.min() < 0 or host.max() >= env.batch):
+                    raise ValueError("renderer: replica indices must lie in [0, %d)" % env.batch)
+                idx = torch.as_tensor(host)
+            self.replicas = idx.to(device=env.device, dtype=torch.int32).reshape(-1).contiguous()
+        self.n = env.batch if self.replicas is None else int(self.replicas.numel())
+        self.lut = None
+        if env._panel == "field":
+            if lut is None:
+                from .render import colormap_lut
+                lut = colormap_lut()
+            t = torch.as_tensor(np.asarray(lut.cpu() if torch.is_tensor(lut) else lut))
+            if t.dtype != torch.uint8 or tuple(t.shape) != (256, 3):
+                raise ValueError("renderer: lut must be a uint8 [256, 3] table")
+            self.lut = t.to(env.device).contiguous()
+        self.frames = torch.empty((self.n,) + self.shape + (3,), dtype=torch.uint8, device=env.device)
+        c = cfg
+        self._scalars = (int(c.plane), int(c.scale), int(c.width), int(c.height), int(c.strip), int(c.has_range), float(c.lo), float(c.hi),
+                         float(c.ref))
+
+    def draw(self, out=None):
+        """Enqueue ONE launch on the current stream that paints the replicas' present state and return the frames: the renderer's own
+        `frames` (nothing is allocated: fit for torch.cuda.graph and for a loop next to step()), or `out`, a contiguous uint8
+        [n, H_px, W_px, 3] device tensor of the caller.  No host synchronisation."""
+        env = self.env
+        if not getattr(env, "h", None) or not env.h.value:
+            raise RuntimeError("Renderer.draw: the env it was made for is closed")
+        buf = self.frames
+        if out is not None:
+            if (not torch.is_tensor(out) or out.dtype != torch.uint8 or out.device != env.device or tuple(out.shape) != tuple(buf.shape)
+                    or not out.is_contiguous()):
+                raise ValueError("Renderer.draw: out must be a contiguous uint8 %s tensor on %s" % (tuple(buf.shape), env.device))
+            buf = out
+        if env._ops is not None:
+            env._ops["render"](env.h.value, buf, self.lut, self.replicas, *self._scalars)
+        else:
+            _lib.check(env._cfn["render"](env.h, C.byref(self.cfg), _ptr(self.lut), _ptr(self.replicas), self.n, _ptr(buf), env._stream()))
+        return buf
 
 
 class Snapshot(object):
@@ -461,6 +529,8 @@ class VecEnv(object):
     _mask = None             # the replica mask in force in the library (_apply_mask, _masked); None: none
     _rollout = None          # rollout: the Rollout attached (a recording launch follows every step); None: none, nothing extra runs
     _rollout_kept = None     # ... the last one allocated, kept across rollout(None)
+    _panel = None            # renderer: "field" (rayleigh, mixing), "line" (burgers, shkadov, sloshing), None: nothing to draw
+    _render_merged = False   # ... whether _RENDER_OPS are in this env's tables
 
     def __init__(self, batch, device="cuda:0", dtype="f32"):
         if not torch.cuda.is_available():
@@ -768,6 +838,8 @@ class VecEnv(object):
         self._ops = _op_table() if on else None
         if self._rollout_kept is not None:
             self._merge_rollout_ops()
+        if self._render_merged:
+            self._merge_render_ops()
         return self._ops is not None
 
     def set_option(self, name, value):
@@ -1137,6 +1209,77 @@ class VecEnv(object):
         default: keep_steps=False plus a rollout is the lean form, begin() between replays starts the next rollout."""
         return StepGraph(self, actions, noise, n_steps, keep_steps, autoreset)
 
+    # -- frames -----------------------------------------------------------------------------
+    def _render_range(self):
+        """(lo, hi, ref) of the reference's render(): the colour range of the field panel / the axes of the line panel."""
+        raise NotImplementedError
+
+    def _render_cfg(self, scale, width, height, strip, field, vmin, vmax, ref):
+        """The bcn_render_cfg of a renderer() call, checked on the host before the library or the device is touched."""
+        who = type(self).__name__ + ".renderer"
+        if self._panel is None:
+            raise ValueError("%s: this env keeps no trajectory on the device: there is nothing to draw" % who)
+        if field not in _lib.PLANES:
+            raise ValueError("%s: field %r; one of %s" % (who, field, ", ".join(sorted(_lib.PLANES))))
+        if (vmin is None) != (vmax is None):
+            raise ValueError("%s: vmin and vmax go together" % who)
+        if self._panel == "field":
+            if int(scale) < 1:
+                raise ValueError("%s: scale = %r; an integer >= 1" % (who, scale))
+            if vmin is None and field != "scalar":
+                raise ValueError("%s: field %r has no default range: pass vmin and vmax" % (who, field))
+        else:
+            if field != "scalar":
+                raise ValueError("%s: field %r belongs to the 2D envs" % (who, field))
+            if int(width) < 1 or int(height) < 1:
+                raise ValueError("%s: width and height must be >= 1" % who)
+        lo, hi, r = self._render_range()
+        if vmin is not None:
+            lo, hi = float(vmin), float(vmax)
+        if ref is not None:
+            r = float(ref)
+        if not (math.isfinite(lo) and math.isfinite(hi) and math.isfinite(r) and hi > lo):
+            raise ValueError("%s: range (%r, %r), ref %r: finite values with vmax > vmin" % (who, lo, hi, r))
+        if strip is not None and int(strip) < 0:
+            raise ValueError("%s: strip = %r rows; >= 0, or None for an eighth of the panel" % (who, strip))
+        return _lib.RenderCfg(plane=_lib.PLANES[field], scale=int(scale), width=int(width), height=int(height),
+                              strip=-1 if strip is None else int(strip), has_range=1, lo=lo, hi=hi, ref=r)
+
+    def renderer(self, replicas=None, scale=1, width=512, height=128, strip=None, field="scalar", vmin=None, vmax=None, lut=None,
+                 ref=None):
+        """A Renderer: uint8 RGB frames [n, H_px, W_px, 3] of the replicas `replicas` (a list / array / tensor of indices, in that
+        order; None: all), painted on the device from the state the step kernels leave -- ONE launch per draw(), no download
+        (csrc/render.hip; the pixel rules: include/beacon_hip.h, bcn_render).
+          rayleigh, mixing     the field panel: `field` ("scalar": T / C, or "u", "v", "p") with every cell `scale` x `scale` pixels, top
+                               row = top of the domain, coloured through `lut` (uint8 [256, 3]; None: render.colormap_lut(), RdBu_r)
+                               over (vmin, vmax) -- default (Tc, Th) / (0, C0) as in the reference; u, v, p need a range
+          burgers u, shkadov h, sloshing h   the line panel, `width` x `height` pixels over (vmin, vmax) with the level `ref` in grey --
+                               default the reference's axes: u_target -+ 2 sigma and u_target; (0, 2) and 1; (0.25, 1.75) and 1; a
+                               replica with a non-finite sample shows red columns
+          under it             `strip` rows of control bars (None: an eighth of the panel; 0: none): the stored action, red up for
+                               positive and blue down for negative; shkadov's jets take equal cells, not their place along the film
+        draw() enqueues the launch and returns the renderer's own buffer, so it allocates nothing and can be recorded inside
+        torch.cuda.graph or called in a loop next to step().  ValueError, before anything touches the device, for scale < 1, an
+        unknown field, u / v / p without a range, vmax <= vmin, and for the ODE envs (lorenz, vortex)."""
+        cfg = self._render_cfg(scale, width, height, strip, field, vmin, vmax, ref)
+        if not self._render_merged:
+            self._merge_render_ops()
+        return Renderer(self, cfg, replicas, lut)
+
+    def _merge_render_ops(self):
+        """_RENDER_OPS into this env's tables of both bindings, as _merge_rollout_ops."""
+        ops, cfn = _render_tables(self.lib, self._ops is not None)
+        if self._ops is not None:
+            if ops is None:
+                raise RuntimeError("the torch extension in use lacks the render op: rebuild it (beacon_amd/torch_ext.py)")
+            self._ops = dict(self._ops, **ops)
+        self._cfn = dict(self._cfn, **cfn)
+        self._render_merged = True
+
+    def render_rgb(self, **kw):
+        """One-shot convenience: renderer(**kw).draw() -- a fresh buffer per call; keep a Renderer for a loop."""
+        return self.renderer(**kw).draw()
+
     def reset_done(self):
         """Auto-reset: re-initialise the replicas whose last step() returned done (their rows of
         `obs` become the reset observation).  Entirely on the device, no host synchronisation."""
@@ -1214,6 +1357,7 @@ class _VecNS2D(VecEnv):
 
     _kind = 0                # BCN_RAYLEIGH / BCN_MIXING
     _params_kernel = "generic"
+    _panel = "field"
 
     def set_ndt_act(self, n):
         """Test hook: shorten the action step (the goldens for big grids use ndt_act=5).  The handle is built anew."""
@@ -1273,6 +1417,9 @@ class VecRayleigh(_VecNS2D):
     (init=False: all-zero fields)."""
 
     PARAMS = ("ra",)
+
+    def _render_range(self):
+        return float(self.Tc), float(self.Th), 0.0               # rayleigh.py:306-308
 
     def __init__(self, batch, device="cuda:0", dtype="f32", init_fields=None,
                  L=1.0, H=1.0, n_sgts=10, ra=1.0e4):
@@ -1374,6 +1521,9 @@ class VecMixing(_VecNS2D):
 
     action_is_int = True
 
+    def _render_range(self):
+        return 0.0, float(self.C0), 0.0                          # mixing.py:296-298
+
     def __init__(self, batch, device="cuda:0", dtype="f32", L=1.0, H=1.0, re=100.0, pe=10000.0,
                  side=0.5, C0=1.0):
         self._derive(L, H, re, pe, side, C0)
@@ -1435,6 +1585,10 @@ class VecBurgers(VecEnv):
     PARAMS = ("u_target", "amp")
 
     needs_noise = True
+    _panel = "line"
+
+    def _render_range(self):
+        return self.u_target - 2 * self.sigma, self.u_target + 2 * self.sigma, float(self.u_target)   # burgers.py:184-189
 
     def __init__(self, batch, device="cuda:0", dtype="f32", u_target=0.5, amp=10.0, sigma=0.1,
                  ctrl_pos=1.0, L=2.0, nx=500, seed=0):
@@ -1494,10 +1648,14 @@ class VecShkadov(VecEnv):
     PARAMS = ("delta",)
 
     needs_noise = True
+    _panel = "line"
     rand_steps = None        # set_random_init: None = every reset restarts from the film itself
     _jets = None             # set_jet_rewards: the JetStats, allocated by the first call and kept
     _jets_on = False         # ... whether the per-jet launch follows every step
     _jets_stats = 0          # ... and whether it keeps the per-jet returns (the kernel's with_stats)
+
+    def _render_range(self):
+        return 0.0, 2.0, 1.0                                     # shkadov.py:287-291
 
     def __init__(self, batch, device="cuda:0", dtype="f32", init_fields=None, L0=150.0, n_jets=5,
                  jet_pos=150.0, jet_space=10.0, delta=0.1, t_act=20.0, seed=0):
@@ -1690,6 +1848,10 @@ class VecSloshing(VecEnv):
     """sloshing/sloshing.py:16-320.  `init_fields`: [2, nx+2] (h_init, q_init incl. ghosts)."""
 
     PARAMS = ("amp", "alpha", "g")
+    _panel = "line"
+
+    def _render_range(self):
+        return 0.25, 1.75, 1.0                                   # sloshing.py:266-270
 
     def __init__(self, batch, device="cuda:0", dtype="f32", init_fields=None, L=2.5, amp=5.0,
                  alpha=0.0005, g=9.81):

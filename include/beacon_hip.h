@@ -606,6 +606,54 @@ BCN_API int bcn_rollout_record(bcn_env_t h, const void* out_buf_dev, void* ro_bu
                                const void* norm_buf_dev, const void* jets_buf_dev, const uint8_t* mask_dev, int T, int flags, void* stream);
 BCN_API int bcn_rollout_gae(bcn_env_t h, void* ro_buf_dev, const void* values_dev, const void* last_value_dev, const void* final_values_dev,
                             int T, int flags, int cols, double gamma, double lam, void* stream);
+/* Frames: what the reference's render() draws (rayleigh.py:278-341, mixing.py:267-359, burgers.py:169-213, shkadov.py:267-350,
+ * sloshing.py:247-295), for any subset of the batch, as uint8 RGB frames [n][H_px][W_px][3] (HWC, contiguous) in a caller-owned
+ * device buffer: ONE kernel launch on `stream` that reads the handle's persistent state -- one plane of the fields and the stored
+ * action -- and writes nothing but the frames; no host synchronisation, no host read, no allocation, no atomics, so it can be
+ * captured into a graph next to *_step.  Frame f shows replica replicas_dev[f] (int32 [n] on the device; an index outside [0, B)
+ * leaves its frame untouched and forms no address), or replica f with replicas_dev NULL, which needs n == B.  lorenz and vortex keep
+ * no trajectory on the device: BCN_ERR_UNSUPPORTED.
+ * The rules below use only operations that round alike on host and device -- one subtraction, one IEEE division, one product with
+ * a power of two or with H, truncation, integers -- in the handle's dtype, with lo, hi, ref narrowed to it first; tests/render_ref.py
+ * restates them in NumPy and tests/test_gpu_render.py holds the kernels to it byte for byte.
+ *   bin(t, n) = 0 for t <= 0, n - 1 for t >= 1, else min(int(t n), n - 1).
+ * Field panel (rayleigh, mixing): W_px = nx scale, H = ny scale.  Panel pixel (r, c) shows cell i = 1 + c / scale, j = ny - r / scale
+ *   (integer divisions) of the plane -- np.rot90(T[1:-1, 1:-1]) under imshow: the top pixel row is the top of the domain, nearest
+ *   neighbour.  t = (value - lo) / (hi - lo); pixel = lut[bin(t, 256)], and (0, 0, 0) for a NaN t.  lut_dev: uint8 [256][3], 4-byte
+ *   aligned (beacon_amd.render.colormap_lut() is RdBu_r, the reference's).  has_range == 0: (Tc, Th) for rayleigh and (0, C0) for
+ *   mixing, the reference's vmin / vmax -- for BCN_PLANE_SCALAR only; u, v and p need a range.
+ * Line panel (burgers u, shkadov h, sloshing h[1 .. nx]; n samples): W_px = width (0: 512), H = height (0: 128).
+ *   row(y) = bin((hi - y) / (hi - lo), H).  Column c covers the samples (c n) / W .. min(((c + 1) n) / W, n - 1), the first sample of
+ *   the next column included: that joins the curve.  Paint order: white; row(ref) in (160, 160, 160); then every row from the
+ *   smallest to the largest row(y_i) of the column's samples in (31, 119, 180).  A column with a non-finite sample is (255, 0, 0)
+ *   over the whole panel height: how a blown-up replica shows.  has_range == 0: the reference's axes -- burgers (u_target - 2 sigma,
+ *   u_target + 2 sigma), ref u_target, with sigma the handle's noise setting (bcn_set_noise; without noise burgers needs a range);
+ *   shkadov (0, 2), ref 1; sloshing (0.25, 1.75), ref 1.
+ * Control strip: `strip` rows under the panel (negative: H / 8; 0: none), white, one cell per control: rayleigh's n_sgts segments,
+ *   mixing's four wall speeds u_t, u_b, v_l, v_r over u_max as get_control assigns them to the stored action index (mixing.py:212-234),
+ *   the one control of burgers and sloshing, shkadov's n_jets jets -- the value the last step stored (a_last; a NaN counts as 0),
+ *   clamped to [-1, 1].  Control k owns the columns [(k W) / n_ctrl, ((k + 1) W) / n_ctrl), c0 to c1, and its bar the middle half of
+ *   them, [c0 + (c1 - c0) / 4, c1 - (c1 - c0) / 4).  With m = strip / 2 and nrow = (int(|c| (2 m)) + 1) / 2 -- |c| m rounded half up --
+ *   the bar takes the strip rows [m - nrow, m) in (255, 0, 0) for c > 0 and [m, m + nrow) in (0, 0, 255) for c < 0, the reference's
+ *   bar colours.  A reset stores zero actions, so nothing is drawn after it -- except for mixing, whose reset stores action 1 as the
+ *   reference's does (mixing.py:102).  Equal cells for shkadov's jets are a simplification: the reference draws each bar at its
+ *   jet's position along the film.
+ * Limits: W_px <= 4096, H <= 16384 for the line panel.  BCN_ERR_ARG, and nothing launched, for a null handle or cfg, an unknown plane,
+ * scale < 1, hi <= lo (also after narrowing) or a non-finite lo, hi, ref, n < 0, n != B without an index list, a null or misaligned
+ * table where one is needed.  bcn_render_shape: the frame's H_px = H + strip and W_px under the same checks. */
+enum { BCN_PLANE_SCALAR = 0, BCN_PLANE_U = 1, BCN_PLANE_V = 2, BCN_PLANE_P = 3 };
+typedef struct {
+  int32_t plane;                  /* field panel: BCN_PLANE_*; line panel: unused */
+  int32_t scale;                  /* field panel: pixels per cell side, >= 1 */
+  int32_t width, height;          /* line panel: pixels; 0 = 512 / 128 */
+  int32_t strip;                  /* rows of the control strip; negative = panel height / 8, 0 = none */
+  int32_t has_range;              /* 0: the reference's range; else lo, hi (and ref) below */
+  double lo, hi;                  /* vmin, vmax of the field panel / ymin, ymax of the line panel */
+  double ref;                     /* line panel: the reference level drawn in grey */
+} bcn_render_cfg;
+BCN_API int bcn_render_shape(bcn_env_t h, const bcn_render_cfg* cfg, int* H_px, int* W_px);
+BCN_API int bcn_render(bcn_env_t h, const bcn_render_cfg* cfg, const uint8_t* lut_dev, const int32_t* replicas_dev, int n, uint8_t* rgb_dev,
+                       void* stream);
 /* name of the kernel the last *_step dispatched, e.g. "ns2d_fast_sched" (before the first step: the
  * variant's plain kernel); for profiles */
 BCN_API const char* bcn_kernel_name(bcn_env_t h);
