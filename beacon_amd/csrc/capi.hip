@@ -10,6 +10,8 @@
 
 #include "env1d.h"
 #include "ns2d.h"
+#include "ns2d_builtin.h"
+#include "ns2d_geom.h"
 #include "ns2d_sched.h"
 #include "ode_env.h"
 #include "params.h"
@@ -28,6 +30,34 @@ __attribute__((visibility("default"))) void bcn_set_error(const char* fmt, ...) 
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
+}
+
+// The two internal queries of ns2d_geom.h (default visibility, like bcn_set_error: for beacon_amd/jit.py, not part of the ABI)
+template <class G>
+static int geometry_of(const G& g, size_t esz, long long out[5]) {
+  if (!g.admissible(esz)) return 0;
+  out[0] = g.nw(), out[1] = g.rl(), out[2] = g.threads(), out[3] = (long long)g.lds_bytes(esz), out[4] = (long long)g.scratch_elems();
+  return 1;
+}
+
+__attribute__((visibility("default"))) int bcn_jit_geometry(int rows, int nx, int ny, int r, int g, int f64, long long out[5]) {
+  const size_t esz = f64 ? 8 : 4;
+  if (!out) return 0;
+  if (rows == 1) return geometry_of(bcn_geom::Rows1{nx, ny, r, g}, esz, out);
+  if (rows == 2) return geometry_of(bcn_geom::Rows2{nx, ny, r, g}, esz, out);
+  if (rows == 4) return geometry_of(bcn_geom::Rows4{nx, ny, r, g}, esz, out);
+  return 0;
+}
+
+__attribute__((visibility("default"))) int bcn_jit_builtin(int i, int out[7]) {
+#define BCN_ROW1(REAL, NX, NY, R, KIND, GF) {sizeof(REAL) == 8, NX, NY, KIND, 1, R, GF},
+#define BCN_ROW2(REAL, NX, NY, R, KIND, GF) {sizeof(REAL) == 8, NX, NY, KIND, 2, R, GF},
+  static const int rows[][7] = {BCN_BUILTIN_FAST(BCN_ROW1) BCN_BUILTIN_FAST2(BCN_ROW2)};
+#undef BCN_ROW1
+#undef BCN_ROW2
+  if (!out || i < 0 || i >= (int)(sizeof(rows) / sizeof(rows[0]))) return 0;
+  for (int k = 0; k < 7; k++) out[k] = rows[i][k];
+  return 1;
 }
 
 namespace {

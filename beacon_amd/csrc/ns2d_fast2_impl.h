@@ -35,6 +35,7 @@
 #include "ns2d.h"
 #include "ns2d_cells.h"
 #include "ns2d_device.h"
+#include "ns2d_geom.h"
 #include "ns2d_prm.h"
 #include "ns2d_sched.h"
 
@@ -42,25 +43,23 @@ namespace {
 
 using namespace bcn_dpp;
 
-// GF = 1 (float64: three float64 fields exceed LDS): u, v, S live in a per-workgroup global scratch (L2-resident), the
-// Poisson rhs in LDS ([cell of the thread][thread]: conflict-free), p and the phi ping-pong in registers.
+// The geometry of a mapping: bcn_geom::Rows2 (ns2d_geom.h) has the arithmetic, the LDS map and what GF means; these are its values
+// as the constants the kernels read.
 template <int NX, int NY, int R, int GF = 0>
 struct Fast2Geom {
-  static_assert(NY <= 128, "two rows per lane");   // odd ny: the last lane's upper row is the ghost row (inactive)
-  static constexpr int NW = (NX + R - 1) / R;
-  static constexpr int RL = NX - (NW - 1) * R;   // columns of the last wave
-  static_assert(NW <= 16 && RL >= 3 && RL <= R, "at most 16 waves, at least 3 columns each");
-  static constexpr int NT = NW * 64;
-  static constexpr int LH = (NY + 1) / 2;  // active lanes
-  static constexpr int SY = NY + 2;
-  static constexpr int SX = NX + 2;
-  static constexpr int SZ = SX * SY;
-  // LDS map (elements): exchange [2][NW][2 sides][2 rows][64] | errp 64 | sact 64 | red 32 | U V S
-  static constexpr int EXCH = 2 * NW * 4 * 64;
-  // ns2d_fast2_sched's two words: the end of the `red` row (block_sum uses red[0..NW), the transport sink red[16..17])
-  static constexpr int SCHED_WORDS = EXCH + 128 + 24;
-  static constexpr size_t lds_elems() { return GF ? (size_t)EXCH + 160 + 2 * (size_t)R * NT : (size_t)EXCH + 160 + 3 * (size_t)SZ; }
-  static constexpr size_t scratch_elems() { return GF ? 3 * (size_t)SZ + 16 : 0; }   // + 16: the transport wave's sink
+  static constexpr bcn_geom::Rows2 g{NX, NY, R, GF};
+  static_assert(g.shape_ok(), "two rows per lane: ny <= 128, at most 16 waves, at least 3 columns each");
+  static constexpr int NW = g.nw();
+  static constexpr int RL = g.rl();
+  static constexpr int NT = g.threads();
+  static constexpr int LH = g.lh();
+  static constexpr int SY = g.sy();
+  static constexpr int SX = g.sx();
+  static constexpr int SZ = g.sz();
+  static constexpr int EXCH = g.exch();
+  static constexpr int SCHED_WORDS = g.sched_words();
+  static constexpr size_t lds_elems() { return g.lds_elems(); }
+  static constexpr size_t scratch_elems() { return g.scratch_elems(); }
 };
 
 // Ordered part of the transport step by ONE wave (out of line, see ns2d_fast.hip).  At step t lane l
@@ -958,6 +957,7 @@ constexpr SchedPolicy kFast2Policy = {"ns2d_fast2_step", "ns2d_fast2_sched", 20,
 template <typename real, int NX, int NY, int R, int KIND, bool EQ, int GF>
 int launch_fast2_eq(const NS2DArgs<real>& a, int batch, hipStream_t s BCN_PRM_PARAM) {
   using G = Fast2Geom<NX, NY, R, GF>;
+  static_assert(G::g.admissible(sizeof(real)), "two rows per lane: this mapping needs more LDS than a workgroup has (160 KB)");
   if (GF && (!a.fscr || a.fscr_stride < G::scratch_elems())) { bcn_set_error("fast2 path: field scratch missing"); return BCN_ERR_UNSUPPORTED; }
   return ns2d_sched_launch<ns2d_fast2_step<real, NX, NY, R, KIND, EQ, GF>, ns2d_fast2_sched<real, NX, NY, R, KIND, EQ, GF>>(
       kFast2Policy, a, batch, s, G::NT, G::lds_elems() * sizeof(real) BCN_PRM_ARG);

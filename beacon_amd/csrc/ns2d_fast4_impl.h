@@ -39,6 +39,7 @@
 #include "ns2d.h"
 #include "ns2d_cells.h"
 #include "ns2d_device.h"
+#include "ns2d_geom.h"
 #include "ns2d_prm.h"
 #include "ns2d_sched.h"
 
@@ -46,33 +47,32 @@ namespace {
 
 using namespace bcn_dpp;
 
+// The geometry of a mapping: bcn_geom::Rows4 (ns2d_geom.h) has the arithmetic and the LDS map; these are its values as the
+// constants the kernels read.
 template <int NX, int NY, int R, int RPL>
 struct Fast4Geom {
-  static constexpr int SX = NX + 2;
-  static constexpr int NCELL = SX * (NY + 2);
-  static constexpr int NW = (NX + R - 1) / R;       // waves = column strips
-  static constexpr int RL = NX - (NW - 1) * R;      // columns of the last strip (1..R)
-  static constexpr int NT = NW * BCN_WAVE;
-  static constexpr int NL = (NY + RPL - 1) / RPL;   // lanes that hold rows (the last one RT + 1 <= RPL of them)
-  static constexpr int RT = (NY - 1) % RPL;         // the top row is row RT of lane NL - 1
-  static constexpr int P = SX | 1;                  // LDS pitch of a natural-layout array (odd)
-  static constexpr int CPL = (NX + BCN_WAVE - 1) / BCN_WAVE;  // columns per lane of the transport walk
-  static constexpr int HROWS = BCN_WAVE * RPL;      // one edge column in the exchange buffer (lane-major)
-  static constexpr int SCHED_WORDS = 2 * 32 + 64;   // ns2d_fast4_sched's two words, behind the reduction scratch [2][2][16] and the conditioned actions
-  static constexpr int FIXED = SCHED_WORDS + 16;
-  static constexpr int HAL = 2 * NW * 2 * HROWS;    // [parity][wave][west|east][HROWS]
-  static constexpr int WARR = P * (NY + 2);
-  static constexpr int LDS_ELEMS_MAX(int esz) { return 160 * 1024 / esz; }
-  // transport: rows per block and number of blocks
-  static constexpr int br_cap(int esz) { return (LDS_ELEMS_MAX(esz) - FIXED - 2) / (3 * P); }
-  static constexpr int nblk(int esz) { return (NY + br_cap(esz) - 1) / br_cap(esz); }
-  static constexpr int br(int esz) { return (NY + nblk(esz) - 1) / nblk(esz); }
-  static constexpr int lds_elems(int esz) {
-    const int jac = FIXED + HAL + WARR, tr = FIXED + 3 * P * br(esz) + 2;
-    return jac > tr ? jac : tr;
-  }
-  static_assert(NL <= BCN_WAVE, "ny <= 64 rows per lane");
-  static_assert(NW >= 2 && NW <= 16 && RL >= 1, "2..16 column strips");
+  static constexpr bcn_geom::Rows4 g{NX, NY, R, RPL};
+  static_assert(BCN_WAVE == bcn_geom::WAVE, "ns2d_geom.h counts lanes in waves of 64");
+  static_assert(g.shape_ok(), "the hybrid: at most 64 lanes of RPL rows, 2..16 column strips");
+  static constexpr int SX = g.sx();
+  static constexpr int NCELL = g.ncell();
+  static constexpr int NW = g.nw();
+  static constexpr int RL = g.rl();
+  static constexpr int NT = g.threads();
+  static constexpr int NL = g.nl();
+  static constexpr int RT = g.rt();
+  static constexpr int P = g.p();
+  static constexpr int CPL = g.cpl();
+  static constexpr int HROWS = g.hrows();
+  static constexpr int SCHED_WORDS = g.sched_words();
+  static constexpr int FIXED = g.fixed();
+  static constexpr int HAL = g.hal();
+  static constexpr int WARR = g.warr();
+  static constexpr int LDS_ELEMS_MAX(int esz) { return g.lds_elems_max(esz); }
+  static constexpr int br_cap(int esz) { return g.br_cap(esz); }
+  static constexpr int nblk(int esz) { return g.nblk(esz); }
+  static constexpr int br(int esz) { return g.br(esz); }
+  static constexpr int lds_elems(int esz) { return g.lds_elems(esz); }
 };
 
 // Cells (i, j), j_lo <= j <= j_hi, with lanes along x and the rows dealt round-robin to the waves, U rows (U * CPL cells) of
@@ -948,6 +948,7 @@ constexpr SchedPolicy kFast4Policy = {"ns2d_fast4_step", "ns2d_fast4_sched", 20,
 template <typename real, int NX, int NY, int R, int RPL, int KIND, bool EQ>
 int launch_fast4_eq(const NS2DArgs<real>& a, int batch, hipStream_t s BCN_PRM_PARAM) {
   using G = Fast4Geom<NX, NY, R, RPL>;
+  static_assert(G::g.admissible(sizeof(real)), "the hybrid: this mapping needs more LDS than a workgroup has (160 KB)");
   if (!f4_fields_ok(a, (size_t)G::NCELL)) return BCN_ERR_UNSUPPORTED;   // (the caller falls back to the generic kernel)
   return ns2d_sched_launch<ns2d_fast4_step<real, NX, NY, R, RPL, KIND, EQ>, ns2d_fast4_sched<real, NX, NY, R, RPL, KIND, EQ>>(
       kFast4Policy, a, batch, s, G::NT, (size_t)G::lds_elems(sizeof(real)) * sizeof(real) BCN_PRM_ARG);

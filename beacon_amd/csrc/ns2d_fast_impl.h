@@ -29,33 +29,10 @@
 #include "ns2d.h"
 #include "ns2d_cells.h"
 #include "ns2d_device.h"
+#include "ns2d_geom.h"
 #include "ns2d_prm.h"
 #include "ns2d_sched.h"
 
-
-#ifndef BCN_R128
-#define BCN_R128 16
-#endif
-#ifndef BCN_R50
-#define BCN_R50 5     // columns per lane of the 50x50 kernels
-#endif
-#ifndef BCN_GFD
-#define BCN_GFD 2   // float64 128x64: 1 = u, v, T in global scratch, 2 = u, v in LDS and T in global scratch
-#endif
-#ifndef BCN_PDG
-#define BCN_PDG 8    // global fields, diagonals ahead.  Round 3 (T through flat pointers): 4 / 8 / 12 -> 52.9 / 52.1 / 51.3 ms per step
-                     // (rayleigh 128x64 float64); round 4 (global pointers): 4 / 8 / 10 / 12 / 16 / 20 -> 53.0 / 51.2 / 51.9 / 52.0 / 51.9 / 61.0.
-                     // (measured depths only: an intermediate round-4 build with generic pointers stopped converging at a depth of 6)
-#endif
-static_assert(BCN_PDG == 4 || BCN_PDG == 8 || BCN_PDG == 10 || BCN_PDG == 12 || BCN_PDG == 16 || BCN_PDG == 20,
-              "BCN_PDG: only the prefetch depths that were measured AND verified against the oracle (4, 8, 10, 12, 16, 20)");
-#ifndef BCN_PDF
-#define BCN_PDF 8    // fields in LDS: diagonals per block of the transport wave (two register sets: it runs PDF..2 PDF diagonals ahead;
-                     // measured 4 / 6 / 8 / 12 / 16: 26.2 / 25.7 / 24.8 / 25.3 / 26.3 k cycles per timestep outside the solve)
-#endif
-#ifndef BCN_R128D
-#define BCN_R128D 16   // columns per lane of the float64 128x64 kernel
-#endif
 
 
 
@@ -63,54 +40,33 @@ namespace {
 
 using namespace bcn_dpp;
 
-// GF ("global fields", float64 at 128x64: 3 x 68.6 KB do not fit LDS): 1 = u, v, T (with the same pads) live in
-// a per-workgroup global scratch and LDS holds only the exchange buffers; 2 = u, v in LDS without pads (the
-// transport wave clamps its skewed reads instead) and only T, with its pads, in the global scratch.
+// The geometry of a mapping: bcn_geom::Rows1 (ns2d_geom.h) has the arithmetic, the LDS map and what GF means; these are its values
+// as the constants the kernels read.
 template <int NX, int NY, int R, int GF = 0>
 struct FastGeom {
-  static_assert(NY <= 64, "lanes run along y");
-  static constexpr int NW = (NX + R - 1) / R;
-  static constexpr int RL = NX - (NW - 1) * R;   // columns of the last wave (a second instantiation of the body when < R)
-  static_assert(NW <= 16 && RL >= 3 && RL <= R, "at most 16 waves, at least 3 columns each");
-  static constexpr int NT = NW * 64;
-  static constexpr int SY = NY + 2;
-  static constexpr int SX = NX + 2;
-  // +16: lanes >= NY read (never write) past the array; a multiple of 64 elements, so that the transport wave fetches
-  // u and v of a cell (the same index in two consecutive arrays) with ONE ds_read2st64_b32
-  // GF == 2 with a narrow last strip: ONE body serves every strip (fast_body: DEADC), the last one R columns wide like the
-  // others with RL of them live; its dead columns read (never write) up to R - RL + 1 columns past the east ghost column
-  static constexpr int DEADPAD = (GF == 2 && RL != R) ? (R - RL + 2) * SY : 0;
-  static constexpr int SZ = (SX * SY + 16 + DEADPAD + 63) / 64 * 64;
-  static constexpr int PD = GF ? BCN_PDG : BCN_PDF;   // transport prefetch depth (diagonals); deeper for global fields
-  // LDS map (elements): [ exchange 2*NW*2*64 | errp 128 | sact 64 | red 32 | sched 16 | .. FRONT ) U V T [ BACK )
-  // The transport wave reads cell (t-lane+1, lane+1) for every lane without range checks: columns
-  // -62..NX+NY+PD fall into FRONT / the neighbouring arrays / BACK, always inside this allocation.
-  // columns per strip in the exchange buffer: 0, 1, R-2, R-1 (depth-2 halos: two sweeps per barrier), or the two edge
-  // columns only where LDS is short (GF == 2: two float64 fields in LDS)
-  static constexpr int XC = (GF == 2) ? 2 : 4;
-  static constexpr int EXCH = 2 * NW * XC * 64;             // [2 buffers][NW][XC][64]
-  static constexpr int SCHED_WORDS = EXCH + 224;            // ns2d_fast_sched's two words, behind errp / sact / red (no static __shared__ in front of the dynamic region)
-  static constexpr int MISC = SCHED_WORDS + 16;
-  static constexpr int FRONT = ((MISC > 63 * SY + 1 ? MISC : 63 * SY + 1) + 15) / 16 * 16;
-  static constexpr int BACK = (NY + 3 * PD + 2) * SY;   // the transport wave prefetches two blocks of PD diagonals ahead
-  static constexpr int FRONTG = (63 * SY + 1 + 15) / 16 * 16;          // front pad of the global variant
-  static constexpr int MISCA = (MISC + 15) / 16 * 16;
-  static constexpr size_t base_elems() {
-    return GF == 1 ? (size_t)MISCA : GF == 2 ? (size_t)MISCA + 2 * (size_t)SZ : (size_t)FRONT + 3 * (size_t)SZ + BACK;
-  }
-  // While wave 0 walks the ordered part of the transport step, the other waves compute the next timestep's predictor -- and,
-  // where LDS has room for it, wave 0's strip as well: p of strip 0 in, u*, and the v* increment without buoyancy out,
-  // [3][R][64] elements behind everything else (fast_body)
-  static constexpr size_t SCR = 3 * (size_t)R * 64;
-  template <typename real> static constexpr bool offload() {
-    return NW >= 3 && (R + 3) / 4 <= NW - 1 && (base_elems() + SCR) * sizeof(real) <= 160 * 1024;
-  }
-  template <typename real> static constexpr size_t lds_bytes() {
-    return (base_elems() + (offload<real>() ? SCR : 0)) * sizeof(real);
-  }
-  static constexpr size_t scratch_elems() {
-    return GF == 1 ? (size_t)FRONTG + 3 * (size_t)SZ + BACK : GF == 2 ? (size_t)FRONTG + SZ + BACK : 0;
-  }
+  static constexpr bcn_geom::Rows1 g{NX, NY, R, GF};
+  static_assert(g.shape_ok(), "one row per lane: ny <= 64 (lanes run along y), at most 16 waves, at least 3 columns each");
+  static constexpr int NW = g.nw();
+  static constexpr int RL = g.rl();
+  static constexpr int NT = g.threads();
+  static constexpr int SY = g.sy();
+  static constexpr int SX = g.sx();
+  static constexpr int DEADPAD = g.deadpad();
+  static constexpr int SZ = g.sz();
+  static constexpr int PD = g.pd();
+  static constexpr int XC = g.xc();
+  static constexpr int EXCH = g.exch();
+  static constexpr int SCHED_WORDS = g.sched_words();   // (no static __shared__ in front of the dynamic region)
+  static constexpr int MISC = g.misc();
+  static constexpr int FRONT = g.front();
+  static constexpr int BACK = g.back();
+  static constexpr int FRONTG = g.frontg();
+  static constexpr int MISCA = g.misca();
+  static constexpr size_t base_elems() { return g.base_elems(); }
+  static constexpr size_t SCR = g.scr();
+  template <typename real> static constexpr bool offload() { return g.offload(sizeof(real)); }
+  template <typename real> static constexpr size_t lds_bytes() { return g.lds_bytes(sizeof(real)); }
+  static constexpr size_t scratch_elems() { return g.scratch_elems(); }
 };
 
 // Ordered part of the transport step, run by ONE wave (kept out of line: its unrolled, software-pipelined loops would
@@ -1288,6 +1244,7 @@ constexpr SchedPolicy kFastPolicy = {"ns2d_fast_step", "ns2d_fast_sched", 10, tr
 template <typename real, int NX, int NY, int R, int KIND, bool EQ, int GF>
 int launch_fast_eq(const NS2DArgs<real>& a, int batch, hipStream_t s BCN_PRM_PARAM) {
   using G = FastGeom<NX, NY, R, GF>;
+  static_assert(G::g.admissible(sizeof(real)), "one row per lane: this mapping needs more LDS than a workgroup has (160 KB)");
   if (GF && (!a.fscr || a.fscr_stride < G::scratch_elems())) { bcn_set_error("fast path: field scratch missing"); return BCN_ERR_UNSUPPORTED; }
   return ns2d_sched_launch<ns2d_fast_step<real, NX, NY, R, KIND, EQ, GF>, ns2d_fast_sched<real, NX, NY, R, KIND, EQ, GF>>(
       kFastPolicy, a, batch, s, G::NT, G::template lds_bytes<real>() BCN_PRM_ARG);

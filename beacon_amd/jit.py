@@ -40,33 +40,58 @@ class JitWarning(UserWarning):
 
 JIT_DIR = os.path.join(_build.PKG, "_jit")
 JIT_SRC = os.path.join(_build.CSRC, "jit", "ns2d_jit.hip")
-LDS_BYTES = 160 * 1024
 _LOADED = {}
 
 
-def _up16(x):
-    return (x + 15) // 16 * 16
+def _library():
+    """libbeacon_hip.so with its two internal queries declared (csrc/ns2d_geom.h: no part of the ABI of include/beacon_hip.h)."""
+    from . import _lib
+    L = _lib.load()
+    if L.bcn_jit_geometry.argtypes is None:
+        L.bcn_jit_geometry.restype = C.c_int
+        L.bcn_jit_geometry.argtypes = [C.c_int] * 6 + [C.POINTER(C.c_longlong)]
+        L.bcn_jit_builtin.restype = C.c_int
+        L.bcn_jit_builtin.argtypes = [C.c_int, C.POINTER(C.c_int)]
+    return L
 
 
-def _lds_rows1(nx, ny, nw, esz, gf, r=0):
-    sy = ny + 2
-    rl = nx - (nw - 1) * r if r else 0
-    deadpad = (r - rl + 2) * sy if (gf == 2 and r and rl != r) else 0      # FastGeom::DEADPAD: the one-body form's dead columns
-    sz = ((nx + 2) * (ny + 2) + 16 + deadpad + 63) // 64 * 64
-    misc = 2 * nw * (2 if gf == 2 else 4) * 64 + 224 + 16
-    front = _up16(max(misc, 63 * sy + 1))
-    back = (ny + 3 * 8 + 2) * sy
-    if gf == 1:
-        return _up16(misc) * esz
-    if gf == 2:
-        return (_up16(misc) + 2 * sz) * esz
-    return (front + 3 * sz + back) * esz
+def geometry(rows, nx, ny, r, g, f64):
+    """What csrc/ns2d_geom.h says about strips of `r` columns of an nx x ny grid in kernel family `rows` (1, 2, 4; g: gf, or rpl for
+    the hybrid): None where the family cannot hold the mapping (its shape, or more LDS than a workgroup has), else dict(nw, rl,
+    threads, lds, scratch) -- waves, columns of the last one, threads, LDS bytes of a launch, elements of global field scratch.  The
+    library computes it, from the header its kernels are built from and with its compiled prefetch depths."""
+    out = (C.c_longlong * 5)()
+    if not _library().bcn_jit_geometry(rows, nx, ny, r, g, int(bool(f64)), out):
+        return None
+    return dict(zip(("nw", "rl", "threads", "lds", "scratch"), (int(v) for v in out)))
+
+
+def builtin_rows():
+    """The register-resident instantiations built into libbeacon_hip.so (csrc/ns2d_builtin.h), as the library enumerates them:
+    [dict(f64, nx, ny, kind, rows, R, gf)]."""
+    L, out, rows = _library(), (C.c_int * 7)(), []
+    while L.bcn_jit_builtin(len(rows), out):
+        rows.append(dict(zip(("f64", "nx", "ny", "kind", "rows", "R", "gf"), [bool(out[0])] + [int(v) for v in out[1:]])))
+    return rows
+
+
+def builtin_grids():
+    """jit.BUILTIN_GRIDS: the grids of libbeacon_hip.so's own register-resident kernels as {(nx, ny, f64, kind)} -- no plugin is built
+    for them.  Derived from builtin_rows() at its first use (importing this module loads no library)."""
+    if "BUILTIN_GRIDS" not in globals():
+        globals()["BUILTIN_GRIDS"] = frozenset((b["nx"], b["ny"], b["f64"], b["kind"]) for b in builtin_rows())
+    return globals()["BUILTIN_GRIDS"]
+
+
+def __getattr__(name):
+    if name == "BUILTIN_GRIDS":
+        return builtin_grids()
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
 def _choose4(nx, ny, f64):
     """ns2d_fast4_impl.h: only the Poisson solve lives in registers (rpl = ceil(ny / 64) rows per lane, strips of r columns); 16
     waves of 128 VGPRs where phi and the rhs of a strip fit them, else 8 waves of 256; the fields stay in HBM/L2."""
-    esz = 8 if f64 else 4
     if ny > 256:
         return None
     rpl = -(-ny // 64)
@@ -74,17 +99,11 @@ def _choose4(nx, ny, f64):
         if f64 and nwmax > 8:
             continue
         r = -(-nx // nwmax)
-        nw = -(-nx // r)
-        if nw < 2 or r * rpl * (2 if f64 else 1) > words:
+        if r * rpl * (2 if f64 else 1) > words:
             continue
-        pitch = (nx + 2) | 1
-        cap = (LDS_BYTES // esz - 146) // (3 * pitch)
-        if cap < 1:
-            continue
-        nblk = -(-ny // cap)
-        lds = (144 + max(2 * nw * 2 * 64 * rpl + pitch * (ny + 2), 3 * pitch * -(-ny // nblk) + 2)) * esz
-        if lds <= LDS_BYTES:
-            return {"rows": 4, "R": r, "gf": 0, "nw": nw, "rpl": rpl}
+        g = geometry(4, nx, ny, r, rpl, f64)
+        if g is not None:
+            return {"rows": 4, "R": r, "gf": 0, "nw": g["nw"], "rpl": rpl}
     return None
 
 
@@ -92,8 +111,9 @@ def choose(nx, ny, f64, kind):
     """Mapping of an nx x ny grid onto one workgroup: dict(rows, R, gf) or None.  Waves: 8 (two per SIMD, 256 VGPRs
     each) where the strips fit the register file, else 12 or 16; the last wave may take fewer columns (>= 3).
     Everything in registers / LDS where that fits (rows 1: ny <= 64, rayleigh; rows 2: ny <= 128), else the hybrid of
-    ns2d_fast4_impl.h (rows 4: tall grids, wide grids, mixing below ny = 64)."""
-    esz = 8 if f64 else 4
+    ns2d_fast4_impl.h (rows 4: tall grids, wide grids, mixing below ny = 64).
+    This is the policy -- which wave counts to try, in which order, up to which strip width, and what float64 is refused; whether
+    a family can hold a candidate (strips, LDS) is geometry()'s answer: csrc/ns2d_geom.h, not restated here."""
     if nx < 6 or ny < 4:
         return None
     if ny <= 64 and kind == 0:      # ns2d_fast_impl.h (one row per lane) implements the rayleigh boundary conditions only
@@ -101,8 +121,7 @@ def choose(nx, ny, f64, kind):
             if f64 and nw > 8:
                 continue
             r = -(-nx // nw)
-            rl = nx - (nw - 1) * r
-            if r > rmax or rl < 3 or rl > r or (nw - 1) * r >= nx:
+            if r > rmax:
                 continue
             # float64: at most 16 columns per lane.  Strips of unequal width: round 4's two-body float64 kernel of 110x64 (strips of
             # 14 and 12 columns, two instantiations of the body in one kernel) computed ONE wrong word per timestep under a neutral
@@ -118,19 +137,20 @@ def choose(nx, ny, f64, kind):
             # found, so these grids take the hybrid (rows 4) instead.  6-wave strips of 10 and 11 columns measured exact.
             if f64 and nw != 8:
                 continue
-            for gf in ((0,) if not f64 else ((2, 1) if rl == r else (2,))):
-                if _lds_rows1(nx, ny, nw, esz, gf, r) <= LDS_BYTES:
-                    return {"rows": 1, "R": r, "gf": gf, "nw": nw}
+            for gf in ((2, 1) if f64 else (0,)):
+                g = geometry(1, nx, ny, r, gf, f64)
+                # (strips of r columns that make fewer waves than the candidate: another candidate's mapping)
+                if g is None or g["nw"] != nw or (gf == 1 and g["rl"] != r):
+                    continue
+                return {"rows": 1, "R": r, "gf": gf, "nw": nw}
     elif 64 < ny <= 128:
         # float64: the fields live in a global scratch, the Poisson rhs in LDS (gf = 1); rayleigh and mixing alike
         for nw, rmax in (((8, 13), (7, 13), (6, 13), (5, 13), (4, 13)) if f64 else ((8, 16), (12, 10), (16, 7), (7, 16), (6, 20), (5, 24), (4, 26))):
             r = -(-nx // nw)
-            rl = nx - (nw - 1) * r
-            if r > rmax or rl < 3 or rl > r or (nw - 1) * r >= nx:
+            if r > rmax:
                 continue
-            exch = 2 * nw * 4 * 64 + 160
-            lds = (exch + 2 * r * nw * 64) * esz if f64 else (exch + 3 * (nx + 2) * (ny + 2)) * esz
-            if lds <= LDS_BYTES:
+            g = geometry(2, nx, ny, r, 1 if f64 else 0, f64)
+            if g is not None and g["nw"] == nw:
                 return {"rows": 2, "R": r, "gf": 1 if f64 else 0, "nw": nw}
     return _choose4(nx, ny, f64)
 
@@ -306,22 +326,24 @@ def selftest(device="cuda:0", verbose=False):
     What to run after rebuilding the library with another ROCm / hipcc: these kernels sit at the register limit of the target
     and their code generation is the compiler's.  Returns {name: (ok, report)}."""
     from . import vec as V
-    cases = [("rayleigh 128x64", 0, dict(L=2.56, H=1.28), ("f32", "f64")), ("rayleigh 50x50", 0, dict(), ("f32", "f64")),
-             ("rayleigh 100x50", 0, dict(L=2.0), ("f32",)), ("rayleigh 150x50", 0, dict(L=3.0), ("f32",)),
-             ("rayleigh 200x50", 0, dict(L=4.0), ("f32",)), ("rayleigh 100x100", 0, dict(L=2.0, H=2.0), ("f32",)),   # (float64: the generic kernel, DESIGN.md 7)
-             ("mixing 100x100", 1, dict(), ("f32", "f64"))]
     out = {}
-    for name, kind, kw, dts in cases:
-        for dt in dts:
-            if kind == 0:
-                mk = lambda B, dt=dt, kw=kw: V.VecRayleigh(B, device, dt, None, **kw)
-            else:
-                mk = lambda B, dt=dt, kw=kw: V.VecMixing(B, device, dt, **kw)
-            ok, rep = compare_with_generic(mk, kind, dt == "f64")
-            out["%s %s" % (name, dt)] = (ok, rep)
-            if verbose:
-                print("%-24s %s  %s" % (name + " " + dt, "ok " if ok else "BAD", rep), flush=True)
+    for name, kind, kw, dt in selftest_cases():
+        if kind == 0:
+            mk = lambda B, dt=dt, kw=kw: V.VecRayleigh(B, device, dt, None, **kw)
+        else:
+            mk = lambda B, dt=dt, kw=kw: V.VecMixing(B, device, dt, **kw)
+        ok, rep = compare_with_generic(mk, kind, dt == "f64")
+        out["%s %s" % (name, dt)] = (ok, rep)
+        if verbose:
+            print("%-24s %s  %s" % (name + " " + dt, "ok " if ok else "BAD", rep), flush=True)
     return out
+
+
+def selftest_cases():
+    """selftest()'s cases, one per row of builtin_rows(): (name, kind, domain lengths of the env's constructor, "f32" | "f64")."""
+    return [("%s %dx%d" % (("rayleigh", "mixing")[b["kind"]], b["nx"], b["ny"]), b["kind"],
+             dict(L=_extent(b["nx"], (50.0, 100.0)[b["kind"]]), H=_extent(b["ny"], (50.0, 100.0)[b["kind"]])), "f64" if b["f64"] else "f32")
+            for b in builtin_rows()]
 
 
 def _signature(defs):
@@ -409,8 +431,14 @@ def plugin_for(nx, ny, f64, kind, extra_defs=None):
         except (OSError, AttributeError) as e:        # a truncated or foreign shared object in the cache
             warnings.warn("beacon_amd.jit: cannot load %s (%s); the generic kernel stays selected" % (path, e), JitWarning)
             p = None
-        if p is not None and p.lds > LDS_BYTES:
-            p = None
+        if p is not None and not os.environ.get("BEACON_JIT_DEFS"):     # (experiments may change the depth: the plugin's own figures rule)
+            m = choose(nx, ny, f64, kind)
+            g = geometry(m["rows"], nx, ny, m["R"], m["rpl"] if m["rows"] == 4 else m["gf"], f64)
+            if g is None or (p.lds, p.scratch) != (g["lds"], g["scratch"]):
+                warnings.warn("beacon_amd.jit: %s reports %d bytes of LDS and %d elements of field scratch, the library's geometry of its "
+                              "mapping says %s; the generic kernel stays selected"
+                              % (os.path.basename(p.path), p.lds, p.scratch, g and "%d and %d" % (g["lds"], g["scratch"])), JitWarning)
+                p = None
         _LOADED[key] = p
     return _LOADED[key]
 
@@ -492,9 +520,6 @@ def fuzz_cases(seed=6):
     return out
 
 
-# grids of libbeacon_hip.so's own register-resident kernels (nx, ny, kind): no plugin is built for them
-BUILTIN_GRIDS = {(128, 64, 0), (50, 50, 0), (100, 50, 0), (150, 50, 0), (200, 50, 0), (100, 100, 1)}
-
 # the grids where choose() switches family, and the narrowest last strips, as (nx, ny, f64, kind, with other constructor
 # arguments).  The family a grid maps to is in the comment (rows per lane: 1 / 2 / 4 = hybrid; "3 live": last strip of 3 columns)
 BOUNDARY_GRIDS = [
@@ -538,7 +563,7 @@ def oracle_cases(seed=7):
     rng = np.random.default_rng(seed)
     out = list(fuzz_cases())
     for nx, ny, f64, kind, args in BOUNDARY_GRIDS:
-        if (nx, ny, kind) in BUILTIN_GRIDS:
+        if (nx, ny, f64, kind) in builtin_grids():
             continue
         n = 50.0 if kind == 0 else 100.0
         kw = {}

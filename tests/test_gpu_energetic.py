@@ -45,7 +45,7 @@ def test_kernels_vs_oracle_from_energetic_flow(idx):
         try:
             nx, ny = env.nx, env.ny
             assert (nx, ny) == (c["nx"], c["ny"])
-            assert ((nx, ny, kind) in jit.BUILTIN_GRIDS) == c["builtin"]
+            assert ((nx, ny, f64, kind) in jit.BUILTIN_GRIDS) == c["builtin"]
             if variant and not c["builtin"]:
                 p = getattr(env, "_plugin", None)
                 assert p is not None and p.verified is True, "no verified plugin for %dx%d %s" % (nx, ny, dt)

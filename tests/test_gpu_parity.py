@@ -2864,7 +2864,7 @@ def test_jit_kernels_vs_oracle(idx):
         try:
             nx, ny = env.nx, env.ny
             m = jit.choose(nx, ny, f64, kind)
-            assert m is not None and (nx, ny, kind) not in jit.BUILTIN_GRIDS
+            assert m is not None and (nx, ny, f64, kind) not in jit.BUILTIN_GRIDS
             if variant:
                 p = getattr(env, "_plugin", None)
                 assert p is not None and p.verified is True, "no verified plugin for %dx%d %s" % (nx, ny, dt)

@@ -624,7 +624,7 @@ def test_jit_oracle_cases_cover_every_kernel_class_and_family_switch():
     assert len(keys) == len(set(keys)) and len(keys) == len(jit.oracle_cases())
     have = {}
     for nx, ny, f64, kind in keys:
-        assert (nx, ny, kind) not in jit.BUILTIN_GRIDS
+        assert (nx, ny, kind) not in {(g[0], g[1], g[3]) for g in jit.BUILTIN_GRIDS}      # (in neither precision)
         m = jit.choose(nx, ny, f64, kind)
         assert m is not None, (nx, ny, f64, kind)
         have.setdefault((m["rows"], f64, kind, ny % 2), []).append((nx, ny))
@@ -648,9 +648,163 @@ def test_jit_oracle_cases_cover_every_kernel_class_and_family_switch():
     assert 0.4 <= n_args / len(jit.BOUNDARY_GRIDS) <= 0.6
 
 
+def test_jit_choose_is_pinned():
+    """jit.choose() over the domain of the test above -- kind outermost, then float32 / float64, then nx, then ny --, one row per
+    grid, as a digest.  choose() takes the strips, the LDS and the scratch of a candidate from the library (csrc/ns2d_geom.h) and
+    keeps the policy; the digest is that of the choose() that computed both in Python, so neither side can move unnoticed.  A
+    deliberate change of the policy or of an LDS map updates it in the same commit."""
+    import hashlib
+    from beacon_amd import jit
+    rows = []
+    for kind, nxs, nys in ((0, range(50, 321), range(50, 257)), (1, range(100, 221), range(100, 257))):
+        for f64 in (False, True):
+            for nx in nxs:
+                for ny in nys:
+                    m = jit.choose(nx, ny, f64, kind)
+                    rows.append((nx, ny, int(f64), kind, m["rows"], m["R"], m["gf"], m["nw"], m.get("rpl") or 0) if m else
+                                (nx, ny, int(f64), kind, 0, 0, 0, 0, 0))
+    assert len(rows) == 150188
+    assert hashlib.sha256(repr(rows).encode()).hexdigest() == "cced238bfac20e74c7f4ce9a4dc4110aa3e0312573c5c833cc05900c040a9f0b"
+
+
+# one mapping per kernel family and precision, as (rows, nx, ny, r, gf | rpl, f64), and two that no family holds (a last strip of 2
+# columns; three float32 fields of 300x64 in LDS)
+GEOM_MAPPINGS = [(1, 128, 64, 16, 0, 0), (1, 128, 64, 16, 2, 1), (1, 75, 50, 10, 1, 1), (1, 125, 55, 16, 2, 1), (2, 100, 100, 13, 0, 0),
+                 (2, 57, 107, 10, 1, 1), (4, 100, 200, 7, 4, 0), (4, 50, 149, 7, 3, 1), (1, 52, 50, 5, 0, 0), (1, 300, 64, 26, 0, 0)]
+
+_GEOM_MAIN = r"""
+#include "ns2d_geom.h"
+#include <stdio.h>
+template <class G> static void show(const G& g, size_t esz) {
+  if (!g.admissible(esz)) { printf("0\n"); return; }
+  printf("1 %d %d %d %zu %zu\n", g.nw(), g.rl(), g.threads(), g.lds_bytes(esz), g.scratch_elems());
+}
+int main() {
+  static_assert(bcn_geom::Rows1{128, 64, 16, 2}.admissible(8) && !bcn_geom::Rows1{128, 64, 16, 0}.admissible(8), "constexpr");
+@CALLS@
+  return 0;
+}
+"""
+
+
+def test_geometry_header_is_plain_cxx_and_the_library_query_agrees(tmp_path):
+    """csrc/ns2d_geom.h alone, in a g++ -std=c++17 program with its own main: no HIP, no other header of the project.  Its figures
+    for GEOM_MAPPINGS -- admissible, waves, last strip, threads, LDS bytes, scratch elements -- are jit.geometry()'s, which the
+    library computes from the same header."""
+    import shutil
+    from beacon_amd import build, jit
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if cxx is None:
+        pytest.skip("no C++ compiler")
+    calls = "\n".join("  show(bcn_geom::Rows%d{%d, %d, %d, %d}, %d);" % (rows, nx, ny, r, g, 8 if f64 else 4)
+                      for rows, nx, ny, r, g, f64 in GEOM_MAPPINGS)
+    src, exe = tmp_path / "geom.cpp", tmp_path / "geom"
+    src.write_text(_GEOM_MAIN.replace("@CALLS@", calls))
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + build.CSRC, str(src), "-o", str(exe)])
+    lines = [tuple(map(int, ln.split())) for ln in subprocess.check_output([str(exe)], text=True).splitlines()]
+    assert len(lines) == len(GEOM_MAPPINGS)
+    for mp, got in zip(GEOM_MAPPINGS, lines):
+        g = jit.geometry(*mp)
+        assert got == ((0,) if g is None else (1, g["nw"], g["rl"], g["threads"], g["lds"], g["scratch"])), (mp, got, g)
+    assert [ln[0] for ln in lines] == [1] * 8 + [0, 0]
+    assert lines[1] == (1, 8, 16, 512, 156544, 18740)        # float64 128x64 (GF = 2), worked by hand from the LDS map
+    assert jit.geometry(3, 100, 100, 13, 0, False) is None and jit.geometry(1, 100, 50, 0, 0, False) is None
+
+
+def _prebuilt_plugins():
+    from beacon_amd import jit
+    grids = jit.TEST_GRIDS + [k for k in jit.oracle_grid_keys() if k not in jit.TEST_GRIDS]
+    return [(g, None) for g in grids] + list(jit.EXTRA_BUILDS)
+
+
+def test_every_prebuilt_plugin_reports_the_geometry_the_library_computes(monkeypatch):
+    """Every plugin __graft_entry__.build() compiles (jit.TEST_GRIDS, oracle_grid_keys(), EXTRA_BUILDS): its own
+    bcn_jit_lds_bytes() and bcn_jit_scratch_elems() -- the kernel templates' constants -- are jit.geometry()'s figures for the
+    mapping choose() gave it.  (The shared objects load without a device.)"""
+    from beacon_amd import jit
+    monkeypatch.delenv("BEACON_JIT_DEFS", raising=False)
+    monkeypatch.setenv("BEACON_NO_BUILD", "1")               # prebuilt means prebuilt: a missing one is a failure, not a compile
+    todo = _prebuilt_plugins()
+    assert len(todo) >= 80
+    for (nx, ny, f64, kind), defs in todo:
+        path = jit.build_plugin(nx, ny, f64, kind, extra_defs=defs)
+        assert path is not None, (nx, ny, f64, kind, defs)
+        p, m = jit.Plugin(path), jit.choose(nx, ny, f64, kind)
+        g = jit.geometry(m["rows"], nx, ny, m["R"], m["rpl"] if m["rows"] == 4 else m["gf"], f64)
+        assert g is not None and (p.lds, p.scratch) == (g["lds"], g["scratch"]) and p.lds <= 160 * 1024, (path, p.lds, p.scratch, g)
+        assert g["nw"] == m["nw"]
+
+
+# the register-resident instantiations of the library, from ns2d_fast.hip and ns2d_fast2.hip as they were before
+# csrc/ns2d_builtin.h listed them: (f64, nx, ny, kind, rows per lane, R, GF)
+BUILTIN_ROWS = [(False, 128, 64, 0, 1, 16, 0), (False, 50, 50, 0, 1, 5, 0), (False, 100, 50, 0, 1, 10, 0), (False, 150, 50, 0, 1, 15, 0),
+                (False, 200, 50, 0, 1, 25, 0), (False, 100, 100, 0, 2, 13, 0), (False, 100, 100, 1, 2, 13, 0),
+                (True, 50, 50, 0, 1, 5, 0), (True, 128, 64, 0, 1, 16, 2), (True, 100, 100, 1, 2, 13, 1)]
+
+
+def test_builtin_rows_are_the_ten_and_every_list_follows_them():
+    """bcn_jit_builtin enumerates exactly BUILTIN_ROWS; every row is a mapping its family holds; jit.BUILTIN_GRIDS, the cases of
+    jit.selftest() and the built-in rows of flow_states.CASES (tests/test_gpu_energetic.py) are consistent with them, and no grid
+    the tests build a plugin for is among them."""
+    import flow_states as FS
+    from beacon_amd import jit
+    rows = jit.builtin_rows()
+    got = [(b["f64"], b["nx"], b["ny"], b["kind"], b["rows"], b["R"], b["gf"]) for b in rows]
+    assert len(got) == 10 and sorted(got) == sorted(BUILTIN_ROWS), got
+    for b in rows:
+        assert jit.geometry(b["rows"], b["nx"], b["ny"], b["R"], b["gf"], b["f64"]) is not None, b
+    assert jit.BUILTIN_GRIDS == {(nx, ny, f64, kind) for f64, nx, ny, kind, _, _, _ in BUILTIN_ROWS} and len(jit.BUILTIN_GRIDS) == 10
+    assert (150, 50, True, 0) not in jit.BUILTIN_GRIDS and (100, 100, False, 0) in jit.BUILTIN_GRIDS
+    cases = jit.selftest_cases()
+    assert sorted((dt == "f64", int(round(kw["L"] * (50, 100)[kind])), int(round(kw["H"] * (50, 100)[kind])), kind) for _, kind, kw, dt in cases) \
+        == sorted((f64, nx, ny, kind) for f64, nx, ny, kind, _, _, _ in BUILTIN_ROWS)
+    assert sorted(n + " " + dt for n, _, _, dt in cases) == sorted(
+        ["rayleigh 128x64 f32", "rayleigh 128x64 f64", "rayleigh 50x50 f32", "rayleigh 50x50 f64", "rayleigh 100x50 f32",
+         "rayleigh 150x50 f32", "rayleigh 200x50 f32", "rayleigh 100x100 f32", "mixing 100x100 f32", "mixing 100x100 f64"])
+    by_grid = {(b["nx"], b["ny"], b["f64"], b["kind"]): b["rows"] for b in rows}
+    for c in FS.CASES:
+        key = (c["nx"], c["ny"], c["dtype"] == "f64", c["kind"])
+        assert c["builtin"] == (key in by_grid) and c["rows"] == by_grid.get(key), c
+    assert sum(c["builtin"] for c in FS.CASES) == 6
+    for g, _ in _prebuilt_plugins():
+        assert g not in jit.BUILTIN_GRIDS, g
+
+
 class _FakePlugin(object):
     def __init__(self, path):
         self.path, self.verified, self.report = path, None, ""
+
+
+def test_a_plugin_that_disagrees_with_the_geometry_is_refused_loudly(tmp_path, monkeypatch):
+    """plugin_for(): a plugin whose bcn_jit_lds_bytes() is not what the library computes for its mapping (built from another LDS map,
+    or with another prefetch depth) warns with JitWarning and is not handed out -- the generic kernel stays selected.
+    With BEACON_JIT_DEFS set (experiments change the depth on purpose) the plugin's own figures rule.  (A fake plugin object.)"""
+    from beacon_amd import jit
+    nx, ny, f64, kind = 75, 50, False, 0
+    m = jit.choose(nx, ny, f64, kind)
+    g = jit.geometry(m["rows"], nx, ny, m["R"], m["gf"], f64)
+
+    def fake(lds, scratch):
+        def make(path):
+            p = _FakePlugin(path)
+            p.lds, p.scratch = lds, scratch
+            return p
+        return make
+    monkeypatch.delenv("BEACON_JIT_DEFS", raising=False)
+    monkeypatch.setattr(jit, "build_plugin", lambda *a, **k: str(tmp_path / "ns2d_75x50_f32_k0_r10_0123456789ab.so"))
+    monkeypatch.setattr(jit, "_LOADED", {})
+    monkeypatch.setattr(jit, "Plugin", fake(g["lds"], g["scratch"]))
+    assert jit.plugin_for(nx, ny, f64, kind) is not None                     # the library's figures: accepted
+    for lds, scratch in ((g["lds"] + 4 * 3 * 4 * (ny + 2), g["scratch"]), (g["lds"], g["scratch"] + 16), (161 * 1024, g["scratch"])):
+        monkeypatch.setattr(jit, "_LOADED", {})
+        monkeypatch.setattr(jit, "Plugin", fake(lds, scratch))
+        with pytest.warns(jit.JitWarning, match="the generic kernel stays selected"):
+            assert jit.plugin_for(nx, ny, f64, kind) is None
+        assert jit.plugin_for(nx, ny, f64, kind) is None                     # (remembered: no second warning, no plugin)
+    monkeypatch.setenv("BEACON_JIT_DEFS", "BCN_PDF=12")
+    monkeypatch.setattr(jit, "_LOADED", {})
+    p = jit.plugin_for(nx, ny, f64, kind)
+    assert p is not None and p.lds == 161 * 1024
 
 
 def test_jit_verdict_markers_carry_the_runtime_tag(tmp_path, monkeypatch):

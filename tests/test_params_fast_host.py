@@ -124,6 +124,6 @@ def test_prebuild_lists_the_parameter_plugins_of_the_gpu_tests():
     assert [g for g, d in extra if "BCN_JIT_BREAK" not in d] == jit.PRM_TEST_GRIDS
     assert [(g, d) for g, d in extra if "BCN_JIT_BREAK" in d] == [(jit.PRM_BREAK_GRID, {"BCN_JIT_PRM": 1, "BCN_JIT_BREAK": 1})]
     for g in jit.PRM_TEST_GRIDS + [jit.PRM_BREAK_GRID]:
-        assert g in jit.TEST_GRIDS and g[:2] + (g[3],) not in jit.BUILTIN_GRIDS
+        assert g in jit.TEST_GRIDS and g not in jit.BUILTIN_GRIDS
     fam = [jit.choose(*g)["rows"] for g in jit.PRM_TEST_GRIDS]
     assert fam == [1, 2, 2, 4] and jit.choose(50, 75, True, 0)["gf"] == 1          # global scratch
