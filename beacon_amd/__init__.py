@@ -8,10 +8,13 @@ Full on-device state of a batch:  VecEnv.snapshot() -> Snapshot, VecEnv.restore(
 Auto-reset and episode statistics on the device:  VecEnv.step_autoreset(a) -> (obs, rwd, done, trunc, EpisodeStats) -- the step, one
 bookkeeping launch (episode return / length, the terminal observation in final_obs) and the masked reset of finished replicas;
 VecEnv.track_episodes() for the bookkeeping alone, VecEnv.capture(..., autoreset=True) for graph rollouts across episode ends
+The actor of a rollout on the device:  Actor(env, hidden=(64, 64)) -- a policy MLP and a value MLP, the draw from the project's Philox
+stream, log-probability and value in ONE launch (actor.act() -> actions; libbeacon_actor.so, include/beacon_actor.h)
 
 Importing the package does not touch the GPU; constructing an env does, and raises if the HIP
 library or a ROCm device is missing (there is no CPU fallback for the solver path)."""
 from .vec import Box, Discrete, EpisodeStats, JetStats, Normalizer, Rollout, RolloutOverflow, Snapshot, VecBurgers, VecEnv, VecLorenz, VecMixing, VecRayleigh, VecShkadov, VecSloshing, VecVortex  # noqa: F401
+from .actor import Actor  # noqa: F401
 from .lorenz import lorenz  # noqa: F401
 from .vortex import vortex  # noqa: F401
 

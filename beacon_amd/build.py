@@ -75,8 +75,9 @@ def sources():
 
 
 def _deps():
+    # (include/beacon_actor.h belongs to libbeacon_actor.so, a unit of its own: beacon_amd/actor.py)
     return (sources() + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) +
-            glob.glob(os.path.join(INC, "*.h")))
+            [f for f in glob.glob(os.path.join(INC, "*.h")) if os.path.basename(f) != "beacon_actor.h"])
 
 
 def signature():
