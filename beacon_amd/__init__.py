@@ -10,11 +10,15 @@ bookkeeping launch (episode return / length, the terminal observation in final_o
 VecEnv.track_episodes() for the bookkeeping alone, VecEnv.capture(..., autoreset=True) for graph rollouts across episode ends
 The actor of a rollout on the device:  Actor(env, hidden=(64, 64)) -- a policy MLP and a value MLP, the draw from the project's Philox
 stream, log-probability and value in ONE launch (actor.act() -> actions; libbeacon_actor.so, include/beacon_actor.h)
+The PPO update of that actor on the device:  Learner(actor, lr=3e-4) -- the clipped-surrogate loss, its gradient with respect to every
+parameter and Adam on actor.params in place, five launches per minibatch (learner.update(ro, adv, ret); libbeacon_learner.so,
+include/beacon_learner.h)
 
 Importing the package does not touch the GPU; constructing an env does, and raises if the HIP
 library or a ROCm device is missing (there is no CPU fallback for the solver path)."""
 from .vec import Box, Discrete, EpisodeStats, JetStats, Normalizer, Rollout, RolloutOverflow, Snapshot, VecBurgers, VecEnv, VecLorenz, VecMixing, VecRayleigh, VecShkadov, VecSloshing, VecVortex  # noqa: F401
 from .actor import Actor  # noqa: F401
+from .learner import Learner  # noqa: F401
 from .lorenz import lorenz  # noqa: F401
 from .vortex import vortex  # noqa: F401
 

@@ -8,23 +8,16 @@ launches that a caller captures in one graph, and Rollout.compute_gae gets its v
 The library is a unit of its own, like the torch extension: its entry points take no env handle, only device pointers and
 sizes; they are bound here through ctypes in a table of their own (SIGNATURES below -- not _lib.SIGNATURES).  Built in-tree
 with the flags of the main library (build.FLAGS) on first use; the sidecar .sig holds a hash of its sources, the headers they
-include and the flags.  Importing this module touches neither a compiler nor the GPU."""
+include and the flags (_unit.py: the machinery, shared with the learner).  Importing this module touches neither a compiler nor the GPU."""
 import ctypes as C
-import fcntl
-import glob
-import hashlib
 import os
-import subprocess
 
 import numpy as np
 import torch
 
 from . import build as _build
+from ._unit import Unit as _Unit
 
-SRC_DIR = os.path.join(_build.CSRC, "actor")
-HEADER = os.path.join(_build.INC, "beacon_actor.h")
-LIB = os.path.join(_build.PKG, "libbeacon_actor.so")
-OBJ = os.path.join(_build.OBJ, "actor")
 API_VERSION = 1                           # include/beacon_actor.h: BCN_ACTOR_API_VERSION
 # per-file flags, as build.FILE_FLAGS.  The float64 unit: one rounding per written operation, for the same reason as rollout.hip
 # (its NumPy restatement is the same sequence); the float32 unit may contract (its sums are explicit fma chains either way).
@@ -63,98 +56,22 @@ SIGNATURES = {
     "bcn_actor_last_error": (C.c_char_p, []),
 }
 
-_LIB = None
-
 
 class BeaconActorError(RuntimeError):
     pass
 
 
 # ---- the library -------------------------------------------------------------------------
-def sources():
-    return sorted(glob.glob(os.path.join(SRC_DIR, "*.hip")))
-
-
-def _deps():
-    """what the units include: their own directory, the Philox definition (csrc/env1d.h -> bcn_common.h -> beacon_hip.h), the header"""
-    return (sources() + glob.glob(os.path.join(SRC_DIR, "*.h")) + [os.path.join(_build.CSRC, "env1d.h"), os.path.join(_build.CSRC, "bcn_common.h"),
-                                                                  os.path.join(_build.INC, "beacon_hip.h"), HEADER])
-
-
-def signature():
-    h = hashlib.sha256()
-    h.update(repr((_build.ARCH, _build.FLAGS, sorted(FILE_FLAGS.items()))).encode())
-    for f in sorted(_deps()):
-        h.update(os.path.basename(f).encode())
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-    return h.hexdigest()
-
-
-def stale():
-    if not os.path.exists(LIB) or not os.path.exists(LIB + ".sig"):
-        return True
-    with open(LIB + ".sig") as fh:
-        return fh.read().strip() != signature()
+# what the units include from outside their directory: the Philox definition (csrc/env1d.h -> bcn_common.h -> beacon_hip.h)
+_UNIT = _Unit("actor", FILE_FLAGS, SIGNATURES, [os.path.join(_build.CSRC, "env1d.h"), os.path.join(_build.CSRC, "bcn_common.h"),
+                                                os.path.join(_build.INC, "beacon_hip.h")])
+SRC_DIR, HEADER, LIB, OBJ = _UNIT.src_dir, _UNIT.header, _UNIT.lib, _UNIT.obj
+sources, signature, stale, load = _UNIT.sources, _UNIT.signature, _UNIT.stale, _UNIT.load
 
 
 def build_actor(force=False, verbose=False):
     """Compile csrc/actor/*.hip for gfx950 and link libbeacon_actor.so.  Returns its path."""
-    if not force and not stale():
-        return LIB
-    cc = _build.hipcc()
-    if cc is None:
-        raise RuntimeError("hipcc not found: cannot build libbeacon_actor.so")
-    with open(LIB + ".lock", "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)               # one builder at a time per checkout
-        try:
-            if not force and not stale():              # another process built it while we waited
-                return LIB
-            sig = signature()
-            objdir = os.path.join(OBJ, "p%d" % os.getpid())
-            os.makedirs(objdir, exist_ok=True)
-            objs = []
-            for src in sources():
-                obj = os.path.join(objdir, os.path.basename(src)[:-4] + ".o")
-                cmd = [cc] + _build.FLAGS + FILE_FLAGS.get(os.path.basename(src), []) + ["-I", _build.INC, "-c", src, "-o", obj]
-                if verbose:
-                    print(" ".join(cmd), flush=True)
-                subprocess.check_call(cmd)
-                objs.append(obj)
-            tmp = "%s.tmp%d" % (LIB, os.getpid())
-            cmd = [cc, "-shared", "-fPIC", "--offload-arch=" + _build.ARCH, "-o", tmp] + objs
-            if verbose:
-                print(" ".join(cmd), flush=True)
-            subprocess.check_call(cmd)
-            os.replace(tmp, LIB)
-            with open(LIB + ".sig.tmp", "w") as fh:
-                fh.write(sig + "\n")
-            os.replace(LIB + ".sig.tmp", LIB + ".sig")
-            import shutil
-            shutil.rmtree(objdir, ignore_errors=True)
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
-    return LIB
-
-
-def load():
-    """dlopen the in-tree library (building it first when stale and hipcc is present); a missing library is an error."""
-    global _LIB
-    if _LIB is not None:
-        return _LIB
-    path = LIB
-    if stale():
-        if os.environ.get("BEACON_NO_BUILD") == "1":
-            raise RuntimeError("libbeacon_actor.so is missing or stale and BEACON_NO_BUILD=1: run "
-                               "`python -c 'import __graft_entry__ as g; g.build()'` first")
-        path = build_actor()
-    L = C.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(L, name)                          # AttributeError if the library lacks a declared symbol
-        fn.restype = res
-        fn.argtypes = args
-    _LIB = L
-    return L
+    return _UNIT.build(force=force, verbose=verbose)
 
 
 def _check(rc):

@@ -75,9 +75,10 @@ def sources():
 
 
 def _deps():
-    # (include/beacon_actor.h belongs to libbeacon_actor.so, a unit of its own: beacon_amd/actor.py)
+    # (include/beacon_actor.h and beacon_learner.h belong to libbeacon_actor.so and libbeacon_learner.so, units of their own:
+    # beacon_amd/actor.py, beacon_amd/learner.py)
     return (sources() + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) +
-            [f for f in glob.glob(os.path.join(INC, "*.h")) if os.path.basename(f) != "beacon_actor.h"])
+            [f for f in glob.glob(os.path.join(INC, "*.h")) if os.path.basename(f) not in ("beacon_actor.h", "beacon_learner.h")])
 
 
 def signature():

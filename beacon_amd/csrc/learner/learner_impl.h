@@ -1,0 +1,614 @@
+// learner_impl.h -- the kernels of libbeacon_learner.so (include/beacon_learner.h: bcn_learner_grad, bcn_learner_step), templated on
+// the real type and instantiated by learner.hip (float32) and learner_f64.hip (float64).
+//
+// The backward launch keeps the actor's tile: 256 lanes own TB rows (64 in float32, 32 in float64), activations live in LDS k-major,
+// h[k][row] with TBP = TB + 4 columns, weights are staged per slab of KS reduction steps (actor_impl.h: ActorGeom, actor_stage and the
+// math wrappers are used unchanged).  What is new:
+//   learner_layer   actor_layer's register tiling with two more things: the first layer's rows are GATHERED (idx, zero rows for
+//                   weight 0) while staging, and a transposed form, out[k][r] = (sum_o W[o][k] D[o][r]) f'(out[k][r]) IN PLACE over
+//                   the activations -- the gradient at a layer's input: the same product with the weight rows copied straight
+//   learner_dw      dW[o][k] = sum_r D[o][r] X[k][r] over the tile's rows: each lane owns 4 x 4 entries, reads four 16-byte chunks of
+//                   each array per four rows (64 fma per 8 LDS reads) and adds its entries to the workgroup's slab in HBM
+// LDS: n_hidden activation buffers [hmax][TBP] (every layer's output is kept: the backward pass overwrites them with the gradients,
+// top down), xs [KS][TBP] (a slab of gathered observations; between layers: scratch for the sums over the tile's rows), ws
+// [KS][wcols], head [16][TBP], the rows' sources int32 [TB].  At the limits (3 x 128 wide): 160 256 bytes in float32, 158 336 in
+// float64, of 163 840.
+//
+// Plain fma for the same reasons as in the actor (actor_impl.h); no atomics, no inter-workgroup communication inside a launch.
+#pragma once
+#include "../actor/actor_impl.h"
+#include "../../../include/beacon_learner.h"
+
+#define LEARNER_NT ACTOR_NT
+#define LEARNER_MAX_PSEGS (4 * (BCN_ACTOR_MAX_LAYERS + 1) + 1)
+#define LEARNER_RED_PARAMS 64        // parameters per block of the reduce launch
+#define LEARNER_RED_SPLIT 4          // lanes per parameter: each adds a quarter of the slabs
+
+template <typename real>
+struct LearnerArgs {
+  const real* params;
+  const real* obs;                  // [n_rows][obs_dim]
+  const void* act;                  // real [n_rows][act_dim] or int32 [n_rows]
+  const real *logp_old, *adv, *ret;
+  const void* weight;
+  const int32_t* idx;
+  const int32_t* cursor;
+  long long n_rows, m, tiles;
+  int weight_kind, rows_per_step;
+  int obs_dim, n_hidden, hidden[BCN_ACTOR_MAX_LAYERS], activation, kind, act_dim;
+  int hmax_pad, wcols;
+  ActorNet pi, vf;
+  unsigned log_std;
+  real clip, vf_coef, ent_coef;
+  real* slabs;                      // [grid][slab_elems]
+  size_t slab_elems;
+  double* wg_stats;                 // [grid][8]
+};
+
+template <typename real>
+struct LearnerReduceArgs {
+  const real* slabs;
+  size_t slab_elems;
+  int used;                         // slabs written: the backward launch's workgroups
+  const double* wg_stats;
+  real* grad;
+  int n_elems;                      // elements of the gradient buffer, gaps between segments included
+  int n_segs;
+  int seg_begin[LEARNER_MAX_PSEGS], seg_end[LEARNER_MAX_PSEGS];
+  double* norm2;                    // [blocks]
+  double* stats;
+  double vf_coef, ent_coef;
+};
+
+template <typename real>
+struct LearnerAdamArgs {
+  real* params;
+  const real* grad;
+  real *m, *v;
+  const int32_t* step;
+  const double* stats;
+  int n_elems;
+  double lr, beta1, beta2, eps, max_grad_norm;
+};
+
+__device__ __forceinline__ float learner_sqrt(float x) { return sqrtf(x); }
+__device__ __forceinline__ double learner_sqrt(double x) { return sqrt(x); }
+__device__ __forceinline__ float learner_abs(float x) { return fabsf(x); }
+__device__ __forceinline__ double learner_abs(double x) { return fabs(x); }
+
+// ks columns (from k0 on) of the tile's GATHERED observation rows into LDS transposed, dst[k * TBP + r]: row r is row rowsrc[r] of obs,
+// or zeros for rowsrc[r] < 0 (behind m, weight 0).  The loads are issued before the first LDS store, as in actor_stage.
+template <typename real>
+__device__ __forceinline__ void learner_stage_obs(const real* __restrict__ obs, int K, int k0, int ks, const int* rowsrc, real* dst) {
+  constexpr int TB = ActorGeom<real>::TB, TBP = TB + 4;
+  const int total = TB * ks;
+  for (int e0 = threadIdx.x; e0 < total; e0 += LEARNER_NT * ACTOR_STAGE_U) {
+    real v[ACTOR_STAGE_U];
+    int at[ACTOR_STAGE_U];
+#pragma unroll
+    for (int u = 0; u < ACTOR_STAGE_U; u++) {
+      const int e = e0 + u * LEARNER_NT;
+      const int r = e / ks, k = e - r * ks;
+      const int s = e < total ? rowsrc[r] : -1;
+      at[u] = e < total ? k * TBP + r : -1;
+      v[u] = s >= 0 ? obs[(size_t)s * K + k0 + k] : real(0);
+    }
+#pragma unroll
+    for (int u = 0; u < ACTOR_STAGE_U; u++)
+      if (at[u] >= 0) dst[at[u]] = v[u];
+  }
+}
+
+// qs rows (from q0 on) of the row-major matrix W[.][N] into LDS as they are, dst[q * ld + n], n < n4 (zeros behind N)
+template <typename real>
+__device__ __forceinline__ void learner_stage_rows(const real* __restrict__ W, int N, int n4, int q0, int qs, real* dst, int ld) {
+  const int total = qs * n4;
+  for (int e = threadIdx.x; e < total; e += LEARNER_NT) {
+    const int q = e / n4, n = e - q * n4;
+    dst[q * ld + n] = n < N ? W[(size_t)(q0 + q) * N + n] : real(0);
+  }
+}
+
+// One layer on the workgroup's tile, out[n][r] for n < N, r < TB, a sum over R steps q in ascending order:
+//   tr = 0  out[n][r] = f(bias[n] + sum_q W[n][q] in[q][r]), W [N][R]: the forward pass (actor_layer)
+//   tr = 1  out[n][r] = (sum_q W[q][n] in[q][r]) f'(out[n][r]), W [R][N]: the gradient at the layer's input, in place over its output
+//   xin     the input in LDS (row stride TBP; must not alias out), or nullptr (tr = 0): the gathered rows of `obs`, staged per slab
+//   f       0 tanh, 1 relu, 2 identity; with tr = 1 the derivative of 0 / 1 from the layer's output: 1 - y^2, [y > 0]
+template <typename real>
+__device__ __forceinline__ void learner_layer(const real* __restrict__ W, const real* __restrict__ bias, int R, int N, int tr, int f,
+                                              const real* xin, const real* __restrict__ obs, const int* rowsrc, real* xs, real* ws, int wcols,
+                                              real* out) {
+  constexpr int TB = ActorGeom<real>::TB, KS = ActorGeom<real>::KS, TBP = TB + 4;
+  constexpr int NPASS = 2;
+  const int lane = threadIdx.x;
+  const int n4 = (N + 3) & ~3;
+  int nog = 1;
+  while (nog * 4 < n4) nog <<= 1;                   // <= 32: N <= 128
+  const int nrg = LEARNER_NT / nog;
+  const int og = lane / nrg, rg = lane - og * nrg;
+  const int o0 = og * 4;
+  const bool has_out = o0 < n4;
+
+  real acc[NPASS][4][4];                            // [pass][row][output]
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const real bj = (bias != nullptr && has_out && o0 + j < N) ? bias[o0 + j] : real(0);
+#pragma unroll
+    for (int p = 0; p < NPASS; p++)
+#pragma unroll
+      for (int i = 0; i < 4; i++) acc[p][i][j] = bj;
+  }
+  const int r_a = rg * 4, r_b = (nrg + rg) * 4;
+  const bool act_a = has_out && r_a < TB, act_b = has_out && r_b < TB;
+
+  for (int q0 = 0; q0 < R; q0 += KS) {
+    const int qs = min(KS, R - q0);
+    __syncthreads();                                // the previous slab's (or phase's) readers of ws / xs are done, its writers too
+    if (tr) learner_stage_rows<real>(W, N, n4, q0, qs, ws, wcols);
+    else actor_stage<real>(W, R, q0, qs, n4, N, ws, wcols);
+    if (xin == nullptr) learner_stage_obs<real>(obs, R, q0, qs, rowsrc, xs);
+    __syncthreads();
+    const real* x = xin ? xin + (size_t)q0 * TBP : xs;
+    if (act_a) {
+#pragma unroll 4
+      for (int q = 0; q < qs; q++) {
+        const ActorV4<real> wq = *reinterpret_cast<const ActorV4<real>*>(ws + q * wcols + o0);
+        const ActorV4<real> xq = *reinterpret_cast<const ActorV4<real>*>(x + q * TBP + r_a);
+        const real* wv = wq.v;
+        const real* xa = xq.v;
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+#pragma unroll
+          for (int j = 0; j < 4; j++) acc[0][i][j] = actor_fma(wv[j], xa[i], acc[0][i][j]);
+        if (act_b) {
+          const ActorV4<real> xr = *reinterpret_cast<const ActorV4<real>*>(x + q * TBP + r_b);
+          const real* xb = xr.v;
+#pragma unroll
+          for (int i = 0; i < 4; i++)
+#pragma unroll
+            for (int j = 0; j < 4; j++) acc[1][i][j] = actor_fma(wv[j], xb[i], acc[1][i][j]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < NPASS; p++) {
+    const int r0 = p ? r_b : r_a;
+    if (!(p ? act_b : act_a)) continue;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      if (o0 + j >= N) continue;
+      ActorV4<real>* at = reinterpret_cast<ActorV4<real>*>(out + (o0 + j) * TBP + r0);
+      ActorV4<real> q, y;
+      if (tr) y = *at;                              // this lane's own entries: nobody else reads or writes them in this phase
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        real v = acc[p][i][j];
+        if (tr) {
+          if (f == 0) v = v * (real(1) - y.v[i] * y.v[i]);
+          else if (f == 1) v = y.v[i] > real(0) ? v : real(0);
+        } else {
+          if (f == 0) v = actor_tanh(v);
+          else if (f == 1) v = v > real(0) ? v : real(0);
+        }
+        q.v[i] = v;
+      }
+      *at = q;
+    }
+  }
+}
+
+// dW[o][k0 + k] (+)= sum_r D[o][r] X[k][r] for o < OUT, k < ks, r ascending over the tile; with k0 = 0 also db[o] (+)= sum_r D[o][r].
+// D, X: LDS, row stride TBP, complete (the caller synchronised).  gW: the workgroup's slab at the matrix [OUT][K], gB at the bias.
+// `first`: the workgroup's first tile stores, the later ones add.  Lane = og * nkg + kg owns the outputs 4 og .. 4 og + 3 and, per
+// chunk of 4 nkg columns, the columns 4 kg .. 4 kg + 3: consecutive lanes touch consecutive addresses of a slab row.
+template <typename real>
+__device__ __forceinline__ void learner_dw(const real* D, int OUT, const real* X, int ks, real* __restrict__ gW, real* __restrict__ gB, int K,
+                                           int k0, bool first) {
+  constexpr int TB = ActorGeom<real>::TB, TBP = TB + 4;
+  const int lane = threadIdx.x;
+  const int out4 = (OUT + 3) & ~3;
+  int nog = 1;
+  while (nog * 4 < out4) nog <<= 1;
+  const int nkg = LEARNER_NT / nog;
+  const int og = lane / nkg, kg = lane - og * nkg;
+  const int o0 = og * 4;
+  if (o0 < OUT) {
+    for (int kb = kg * 4; kb < ks; kb += nkg * 4) {
+      real acc[4][4];                               // [output][column]
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+#pragma unroll
+        for (int i = 0; i < 4; i++) acc[j][i] = real(0);
+#pragma unroll 2
+      for (int r = 0; r < TB; r += 4) {
+        ActorV4<real> d[4], x[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          if (o0 + j < OUT) d[j] = *reinterpret_cast<const ActorV4<real>*>(D + (o0 + j) * TBP + r);
+          else d[j] = ActorV4<real>{{real(0), real(0), real(0), real(0)}};
+          if (kb + j < ks) x[j] = *reinterpret_cast<const ActorV4<real>*>(X + (kb + j) * TBP + r);
+          else x[j] = ActorV4<real>{{real(0), real(0), real(0), real(0)}};
+        }
+#pragma unroll
+        for (int c = 0; c < 4; c++)
+#pragma unroll
+          for (int j = 0; j < 4; j++)
+#pragma unroll
+            for (int i = 0; i < 4; i++) acc[j][i] = actor_fma(d[j].v[c], x[i].v[c], acc[j][i]);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+          if (o0 + j < OUT && kb + i < ks) {
+            real* at = gW + (size_t)(o0 + j) * K + k0 + kb + i;
+            *at = first ? acc[j][i] : *at + acc[j][i];
+          }
+    }
+  }
+  if (k0 == 0 && lane < OUT) {
+    real s = real(0);
+    for (int r = 0; r < TB; r++) s += D[lane * TBP + r];
+    gB[lane] = first ? s : gB[lane] + s;
+  }
+}
+
+// Forward pass of one MLP on the tile: layer l's output stays in hbuf + l * hstride, the head's in `head` ([n_head][TBP]).
+template <typename real>
+__device__ __forceinline__ void learner_forward(const LearnerArgs<real>& A, const ActorNet& net, int n_head, const int* rowsrc, real* hbuf,
+                                                size_t hstride, real* xs, real* ws, real* head) {
+  const real* in = nullptr;
+  int K = A.obs_dim;
+  for (int l = 0; l < A.n_hidden; l++) {
+    real* o = hbuf + l * hstride;
+    learner_layer<real>(A.params + net.w[l], A.params + net.b[l], K, A.hidden[l], 0, A.activation, in, A.obs, rowsrc, xs, ws, A.wcols, o);
+    in = o;
+    K = A.hidden[l];
+  }
+  learner_layer<real>(A.params + net.w[A.n_hidden], A.params + net.b[A.n_hidden], K, n_head, 0, 2, in, A.obs, rowsrc, xs, ws, A.wcols, head);
+}
+
+// Backward pass of one MLP: `head` holds the gradient at the head's outputs, the activation buffers the forward pass's outputs.
+template <typename real>
+__device__ __forceinline__ void learner_backward(const LearnerArgs<real>& A, const ActorNet& net, int n_head, const int* rowsrc, real* hbuf,
+                                                 size_t hstride, real* xs, real* ws, real* head, real* slab, bool first) {
+  constexpr int KS = ActorGeom<real>::KS;
+  for (int l = A.n_hidden; l >= 0; l--) {
+    const real* D = l == A.n_hidden ? head : hbuf + l * hstride;
+    const int OUT = l == A.n_hidden ? n_head : A.hidden[l];
+    __syncthreads();                                // D is complete
+    if (l > 0) {
+      const int K = A.hidden[l - 1];
+      real* X = hbuf + (l - 1) * hstride;
+      learner_dw<real>(D, OUT, X, K, slab + net.w[l], slab + net.b[l], K, 0, first);
+      // the gradient at this layer's input, in place over X (learner_layer synchronises before it writes anything)
+      learner_layer<real>(A.params + net.w[l], nullptr, OUT, K, 1, A.activation, D, A.obs, rowsrc, xs, ws, A.wcols, X);
+    } else {
+      const int K = A.obs_dim;
+      for (int k0 = 0; k0 < K; k0 += KS) {
+        const int ks = min(KS, K - k0);
+        if (k0) __syncthreads();                    // the previous slab's readers of xs are done
+        learner_stage_obs<real>(A.obs, K, k0, ks, rowsrc, xs);
+        __syncthreads();
+        learner_dw<real>(D, OUT, xs, ks, slab + net.w[0], slab + net.b[0], K, k0, first);
+      }
+    }
+  }
+}
+
+template <typename real>
+__global__ __launch_bounds__(LEARNER_NT) void learner_backward_kernel(const LearnerArgs<real> A) {
+  constexpr int TB = ActorGeom<real>::TB, KS = ActorGeom<real>::KS, TBP = TB + 4;
+  extern __shared__ __attribute__((aligned(16))) unsigned char learner_lds[];
+  real* hbuf = reinterpret_cast<real*>(learner_lds);
+  const size_t hstride = (size_t)A.hmax_pad * TBP;
+  real* xs = hbuf + (size_t)A.n_hidden * hstride;     // [KS][TBP]
+  real* ws = xs + (size_t)KS * TBP;                   // [KS][wcols]
+  real* head = ws + (size_t)KS * A.wcols;             // [BCN_ACTOR_MAX_ACT][TBP]
+  int* rowsrc = reinterpret_cast<int*>(head + (size_t)BCN_ACTOR_MAX_ACT * TBP);   // [TB]
+  real* slab = A.slabs + (size_t)blockIdx.x * A.slab_elems;
+  const int r = threadIdx.x;
+  const int n = A.act_dim;
+  const real* log_std = A.params + A.log_std;
+  double st = 0.0;                                    // lane s < 6: the workgroup's sum of statistic s
+  bool first = true;
+
+  for (long long tile = blockIdx.x; tile < A.tiles; tile += gridDim.x, first = false) {
+    const long long row0 = tile * TB;
+    __syncthreads();                                  // the previous tile's readers of xs and rowsrc are done
+    // ---- the rows' sources and weights: one lane per row -------------------------------------------------------------------
+    real w = real(0);
+    int src = -1, cls = 0;
+    if (r < TB && row0 + r < A.m) {
+      const long long s = A.idx ? (long long)A.idx[row0 + r] : row0 + r;
+      long long lim = A.n_rows;
+      if (A.cursor) {
+        const long long c = A.cursor[0] > 0 ? A.cursor[0] : 0;
+        lim = min(lim, c * (long long)A.rows_per_step);
+      }
+      if (s >= 0 && s < lim) {
+        real wv = real(1);
+        if (A.weight_kind == BCN_LEARNER_W_U8) wv = (real) static_cast<const uint8_t*>(A.weight)[s];
+        else if (A.weight_kind == BCN_LEARNER_W_REAL) wv = static_cast<const real*>(A.weight)[s];
+        bool ok = wv > real(0);
+        if (ok && A.kind == BCN_ACTOR_CATEGORICAL) {
+          cls = static_cast<const int32_t*>(A.act)[s];
+          ok = cls >= 0 && cls < n;
+        }
+        if (ok) { w = wv; src = (int)s; }
+      }
+    }
+    if (r < TB) rowsrc[r] = src;
+
+    // ---- the policy network ----------------------------------------------------------------------------------------------
+    learner_forward<real>(A, A.pi, n, rowsrc, hbuf, hstride, xs, ws, head);
+    __syncthreads();
+    real t_pg = real(0), t_h = real(0), t_kl = real(0), t_cf = real(0), t_v = real(0);
+    if (r < TB) {
+      real hd[BCN_ACTOR_MAX_ACT], dl[BCN_ACTOR_MAX_ACT], gl[BCN_ACTOR_MAX_ACT];
+#pragma unroll
+      for (int i = 0; i < BCN_ACTOR_MAX_ACT; i++) {
+        hd[i] = i < n ? head[i * TBP + r] : real(0);
+        dl[i] = real(0);
+        gl[i] = real(0);
+      }
+      if (src >= 0) {
+        real logp = real(0), H = real(0);
+        real z[BCN_ACTOR_MAX_ACT], e[BCN_ACTOR_MAX_ACT];      // Gaussian: z, exp(-log_std); categorical: d, p
+        if (A.kind == BCN_ACTOR_GAUSSIAN) {
+          const real* a = static_cast<const real*>(A.act) + (size_t)src * n;
+#pragma unroll
+          for (int i = 0; i < BCN_ACTOR_MAX_ACT; i++) {
+            z[i] = e[i] = real(0);
+            if (i < n) {
+              const real ls = log_std[i];
+              e[i] = actor_exp(-ls);
+              z[i] = (a[i] - hd[i]) * e[i];
+              logp += (real(-0.5) * z[i] * z[i] - ls) - real(0.91893853320467274178);
+              H += ls + real(1.41893853320467274178);
+            }
+          }
+        } else {
+          real mx = hd[0];
+#pragma unroll
+          for (int i = 1; i < BCN_ACTOR_MAX_ACT; i++)
+            if (i < n && hd[i] > mx) mx = hd[i];
+          real se = real(0);
+#pragma unroll
+          for (int i = 0; i < BCN_ACTOR_MAX_ACT; i++)
+            if (i < n) se += actor_exp(hd[i] - mx);
+          const real lse = actor_log(se);
+#pragma unroll
+          for (int i = 0; i < BCN_ACTOR_MAX_ACT; i++) {
+            z[i] = e[i] = real(0);
+            if (i < n) {
+              z[i] = (hd[i] - mx) - lse;
+              e[i] = actor_exp(z[i]);
+              H -= e[i] * z[i];
+              if (i == cls) logp = z[i];
+            }
+          }
+        }
+        const real dlp = logp - A.logp_old[src];
+        const real ratio = actor_exp(dlp), adv = A.adv[src];
+        const real lo = real(1) - A.clip, hi = real(1) + A.clip;
+        const real s1 = ratio * adv, s2 = (ratio < lo ? lo : (ratio > hi ? hi : ratio)) * adv;
+        const bool unclipped = s1 <= s2;
+        const real g = unclipped ? -s1 : real(0);              // d pg / d logp
+        t_pg = w * -(unclipped ? s1 : s2);
+        t_h = w * H;
+        t_kl = w * ((ratio - real(1)) - dlp);
+        t_cf = learner_abs(ratio - real(1)) > A.clip ? w : real(0);
+        if (A.kind == BCN_ACTOR_GAUSSIAN) {
+#pragma unroll
+          for (int i = 0; i < BCN_ACTOR_MAX_ACT; i++)
+            if (i < n) {
+              dl[i] = w * (g * z[i] * e[i]);
+              gl[i] = w * (g * (z[i] * z[i] - real(1)) - A.ent_coef);
+            }
+        } else {
+#pragma unroll
+          for (int i = 0; i < BCN_ACTOR_MAX_ACT; i++)
+            if (i < n) dl[i] = w * (g * ((i == cls ? real(1) : real(0)) - e[i]) + A.ent_coef * (e[i] * (z[i] + H)));
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < BCN_ACTOR_MAX_ACT; i++)
+        if (i < n) {
+          head[i * TBP + r] = dl[i];
+          xs[i * TBP + r] = gl[i];
+        }
+    }
+    __syncthreads();
+    if (A.kind == BCN_ACTOR_GAUSSIAN && r < n) {               // d L / d log_std: the sum over the tile's rows
+      real s = real(0);
+      for (int q = 0; q < TB; q++) s += xs[r * TBP + q];
+      real* at = slab + A.log_std + r;
+      *at = first ? s : *at + s;
+    }
+    learner_backward<real>(A, A.pi, n, rowsrc, hbuf, hstride, xs, ws, head, slab, first);
+
+    // ---- the value network -----------------------------------------------------------------------------------------------
+    learner_forward<real>(A, A.vf, 1, rowsrc, hbuf, hstride, xs, ws, head);
+    __syncthreads();
+    if (r < TB) {
+      real d = real(0);
+      if (src >= 0) {
+        const real err = head[r] - A.ret[src];
+        t_v = w * (err * err);
+        d = w * (A.vf_coef * (real(2) * err));
+      }
+      head[r] = d;
+    }
+    learner_backward<real>(A, A.vf, 1, rowsrc, hbuf, hstride, xs, ws, head, slab, first);
+
+    // ---- the statistics: per-row terms through xs, summed in float64 for r ascending -----------------------------------------
+    __syncthreads();
+    if (r < TB) {
+      xs[0 * TBP + r] = t_pg; xs[1 * TBP + r] = t_v; xs[2 * TBP + r] = t_h;
+      xs[3 * TBP + r] = t_kl; xs[4 * TBP + r] = t_cf; xs[5 * TBP + r] = w;
+    }
+    __syncthreads();
+    if (r < 6)
+      for (int q = 0; q < TB; q++) st += (double)xs[r * TBP + q];
+  }
+  if (r < BCN_LEARNER_N_STATS) A.wg_stats[(size_t)blockIdx.x * BCN_LEARNER_N_STATS + r] = r < 6 ? st : 0.0;
+}
+
+// grad[p] = (sum_g slab_g[p]) / W for g ascending; the block's part of the squared norm; block 0: stats[0 .. 6].
+// Lane = part * 64 + j: parameter blockIdx * 64 + j, the slabs part * ceil(used / 4) ... of it.
+template <typename real>
+__global__ __launch_bounds__(LEARNER_NT) void learner_reduce_kernel(const LearnerReduceArgs<real> A) {
+  __shared__ double tot[BCN_LEARNER_N_STATS];
+  __shared__ double wg[BCN_LEARNER_N_STATS][BCN_LEARNER_MAX_GRID + 1];
+  __shared__ double part[LEARNER_RED_SPLIT][LEARNER_RED_PARAMS];
+  const int t = threadIdx.x;
+  // the workgroups' partial statistics: one row per lane, every load in flight at once; then statistic s is summed by lane s for g ascending
+  for (int g = t; g < A.used; g += LEARNER_NT) {
+    double v[BCN_LEARNER_N_STATS];
+#pragma unroll
+    for (int k = 0; k < BCN_LEARNER_N_STATS; k++) v[k] = A.wg_stats[(size_t)g * BCN_LEARNER_N_STATS + k];
+#pragma unroll
+    for (int k = 0; k < BCN_LEARNER_N_STATS; k++) wg[k][g] = v[k];
+  }
+  __syncthreads();
+  if (t < BCN_LEARNER_N_STATS) {
+    double s = 0.0;
+    for (int g = 0; g < A.used; g++) s += wg[t][g];
+    tot[t] = s;
+  }
+  const int j = t % LEARNER_RED_PARAMS, sp = t / LEARNER_RED_PARAMS;
+  const int p = blockIdx.x * LEARNER_RED_PARAMS + j;
+  bool in_seg = false;
+  if (p < A.n_elems)
+    for (int s = 0; s < A.n_segs; s++) in_seg = in_seg || (p >= A.seg_begin[s] && p < A.seg_end[s]);
+  const int per = (A.used + LEARNER_RED_SPLIT - 1) / LEARNER_RED_SPLIT;
+  const int g0 = sp * per, g1 = min(A.used, g0 + per);
+  double s = 0.0;
+  if (in_seg) {
+    for (int g = g0; g < g1; g += 8) {              // eight loads in flight, added in the order g ascending
+      real v[8];
+#pragma unroll
+      for (int u = 0; u < 8; u++) v[u] = g + u < g1 ? A.slabs[(size_t)(g + u) * A.slab_elems + p] : real(0);
+#pragma unroll
+      for (int u = 0; u < 8; u++)
+        if (g + u < g1) s += (double)v[u];
+    }
+  }
+  part[sp][j] = s;
+  __syncthreads();
+  const double W = tot[5] > 1.0 ? tot[5] : 1.0;
+  if (sp == 0) {
+    double sum = part[0][j];
+#pragma unroll
+    for (int q = 1; q < LEARNER_RED_SPLIT; q++) sum += part[q][j];
+    const real g = (real)(sum / W);
+    if (p < A.n_elems) A.grad[p] = in_seg ? g : real(0);
+    part[0][j] = in_seg ? (double)g * (double)g : 0.0;
+  }
+  __syncthreads();
+  if (t == 0) {
+    double q = 0.0;
+    for (int i = 0; i < LEARNER_RED_PARAMS; i++) q += part[0][i];
+    A.norm2[blockIdx.x] = q;
+    if (blockIdx.x == 0) {
+      const double pg = tot[0] / W, vf = tot[1] / W, ent = tot[2] / W;
+      A.stats[BCN_LEARNER_STAT_LOSS] = pg + A.vf_coef * vf - A.ent_coef * ent;
+      A.stats[BCN_LEARNER_STAT_PG] = pg;
+      A.stats[BCN_LEARNER_STAT_VF] = vf;
+      A.stats[BCN_LEARNER_STAT_ENTROPY] = ent;
+      A.stats[BCN_LEARNER_STAT_KL] = tot[3] / W;
+      A.stats[BCN_LEARNER_STAT_CLIP_FRAC] = tot[4] / W;
+      A.stats[BCN_LEARNER_STAT_W] = W;
+    }
+  }
+}
+
+// stats[7] = sqrt(sum of the reduce launch's partials): lane t adds the partials t, t + 256, ... ascending, then a fixed tree
+template <typename real>      // (a template only so that each unit instantiates its own)
+__global__ __launch_bounds__(LEARNER_NT) void learner_finish_kernel(const double* norm2, int n_blocks, double* stats) {
+  __shared__ double sh[LEARNER_NT];
+  const int t = threadIdx.x;
+  double s = 0.0;
+  for (int i = t; i < n_blocks; i += LEARNER_NT) s += norm2[i];
+  sh[t] = s;
+  __syncthreads();
+  for (int d = LEARNER_NT / 2; d > 0; d >>= 1) {
+    if (t < d) sh[t] += sh[t + d];
+    __syncthreads();
+  }
+  if (t == 0) stats[BCN_LEARNER_STAT_GRAD_NORM] = sqrt(sh[0]);
+}
+
+template <typename real>
+__global__ __launch_bounds__(LEARNER_NT) void learner_adam_kernel(const LearnerAdamArgs<real> A) {
+  const int p = blockIdx.x * LEARNER_NT + threadIdx.x;
+  if (p >= A.n_elems) return;
+  const double norm = A.stats[BCN_LEARNER_STAT_GRAD_NORM];
+  double scale = 1.0;
+  if (A.max_grad_norm > 0.0) {
+    scale = A.max_grad_norm / (norm + 1e-6);
+    scale = scale < 1.0 ? scale : 1.0;
+  }
+  const double t = (double)(A.step[0] + 1);
+  const real step_size = (real)(A.lr / (1.0 - pow(A.beta1, t)));
+  const real bc2_sqrt = (real)sqrt(1.0 - pow(A.beta2, t));
+  const real g = A.grad[p] * (real)scale;
+  real m = A.m[p], v = A.v[p];
+  m = m + (real)(1.0 - A.beta1) * (g - m);
+  v = (real)A.beta2 * v + (real)(1.0 - A.beta2) * (g * g);
+  A.m[p] = m;
+  A.v[p] = v;
+  const real denom = learner_sqrt(v) / bc2_sqrt + (real)A.eps;
+  A.params[p] = A.params[p] - step_size * (m / denom);
+}
+
+template <typename real>
+__global__ void learner_tick_kernel(int32_t* step) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) step[0] = step[0] + 1;
+}
+
+// bytes of dynamic LDS of one workgroup of the backward launch
+template <typename real>
+inline size_t learner_lds_bytes(int n_hidden, int hmax_pad, int wcols) {
+  constexpr int TB = ActorGeom<real>::TB, KS = ActorGeom<real>::KS, TBP = TB + 4;
+  return sizeof(real) * ((size_t)n_hidden * hmax_pad * TBP + (size_t)KS * TBP + (size_t)KS * wcols + (size_t)BCN_ACTOR_MAX_ACT * TBP) + sizeof(int) * TB;
+}
+
+// defined by learner.hip (float) and learner_f64.hip (double): the launches, hipError_t as int
+template <typename real> int learner_launch_grad(const LearnerArgs<real>& a, const LearnerReduceArgs<real>& r, int grid, int red_blocks, void* stream);
+template <typename real> int learner_launch_step(const LearnerAdamArgs<real>& a, int32_t* step, void* stream);
+
+#define LEARNER_DEFINE_LAUNCH(real)                                                                                     \
+  template <> int learner_launch_grad<real>(const LearnerArgs<real>& a, const LearnerReduceArgs<real>& r, int grid,    \
+                                            int red_blocks, void* stream) {                                            \
+    const size_t lds = learner_lds_bytes<real>(a.n_hidden, a.hmax_pad, a.wcols);                                        \
+    static size_t lds_allowed[64] = {0};                                                                               \
+    int dev = 0;                                                                                                       \
+    hipError_t e = hipGetDevice(&dev);                                                                                 \
+    if (e != hipSuccess) return (int)e;                                                                                \
+    if (lds > 48 * 1024 && (dev < 0 || dev >= 64 || lds_allowed[dev] < lds)) {                                         \
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&learner_backward_kernel<real>),                           \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                                 \
+      if (e != hipSuccess) return (int)e;                                                                              \
+      if (dev >= 0 && dev < 64) lds_allowed[dev] = 160 * 1024;                                                         \
+    }                                                                                                                  \
+    hipStream_t s = static_cast<hipStream_t>(stream);                                                                  \
+    hipLaunchKernelGGL(learner_backward_kernel<real>, dim3(grid), dim3(LEARNER_NT), lds, s, a);                        \
+    e = hipGetLastError();                                                                                             \
+    if (e != hipSuccess) return (int)e;                                                                                \
+    hipLaunchKernelGGL(learner_reduce_kernel<real>, dim3(red_blocks), dim3(LEARNER_NT), 0, s, r);                      \
+    e = hipGetLastError();                                                                                             \
+    if (e != hipSuccess) return (int)e;                                                                                \
+    hipLaunchKernelGGL(learner_finish_kernel<real>, dim3(1), dim3(LEARNER_NT), 0, s, (const double*)r.norm2, red_blocks, r.stats); \
+    return (int)hipGetLastError();                                                                                     \
+  }                                                                                                                    \
+  template <> int learner_launch_step<real>(const LearnerAdamArgs<real>& a, int32_t* step, void* stream) {             \
+    hipStream_t s = static_cast<hipStream_t>(stream);                                                                  \
+    hipLaunchKernelGGL(learner_adam_kernel<real>, dim3((a.n_elems + LEARNER_NT - 1) / LEARNER_NT), dim3(LEARNER_NT), 0, s, a); \
+    const hipError_t e = hipGetLastError();                                                                            \
+    if (e != hipSuccess) return (int)e;                                                                                \
+    hipLaunchKernelGGL(learner_tick_kernel<real>, dim3(1), dim3(64), 0, s, step);                                      \
+    return (int)hipGetLastError();                                                                                     \
+  }
