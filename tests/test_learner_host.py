@@ -271,6 +271,64 @@ def test_reference_gradient_equals_a_central_finite_difference():
     assert ref.moments(opt)[2] == 1
 
 
+def test_float32_reference_agrees_with_the_float64_one():
+    """Ref(dtype=torch.float32) on two cases of tests/test_gpu_learner.py, on the float32 data of the case: per segment, its error
+    against the float64 reference is below 1e-5 of the segment's max |ref| (measured: at most 1.4e-6) -- and it is not the float64
+    answer under another name, which would leave it without the float32 roundoff that the GPU test measures the device against."""
+    import test_gpu_learner as G
+    for i in (1, 8):                                  # 65 x 33 (17, 128, 3) relu Gaussian; 2305 x 6 (64, 64) tanh, categorical 16
+        case, cid = G.CASES[i], G.IDS[i]
+        d = G.case_data(case, torch.float32, G.SEEDS[cid])
+        assert set(d["grads32"]) == set(d["grads"])
+        rels = {}
+        for k, g in d["grads"].items():
+            assert d["grads32"][k].dtype == torch.float32 and g.dtype == torch.float64 and float(g.abs().max()) > 0.0, k
+            rels[k] = G.rel(d["grads32"][k], g)
+        print("float32 reference %s: rel %.3e .. %.3e" % (cid, min(rels.values()), max(rels.values())))
+        assert max(rels.values()) < 1e-5, rels
+        assert min(rels.values()) > 2.0 ** -30, rels  # float32 roundoff is there in every segment
+    # the same loss in the same precision: the statistics agree to float32 roundoff too
+    r32 = R.Ref(d["w"], case[2], case[3], 1, dtype=torch.float32)
+    _, s32, t32 = r32.grad(d["obs"], d["act"], d["logp_old"], d["adv"], d["ret"], None, G.CLIP, G.VF_COEF, G.ENT_COEF)
+    assert t32["loss"].dtype == torch.float32 and all(p.dtype == torch.float32 for p in r32.parameters())
+    for k, v in d["stats"].items():
+        assert abs(s32[k] - v) <= 1e-5 * max(1.0, abs(v)), (k, s32[k], v)
+
+
+def test_every_gpu_case_has_data_that_exercises_it():
+    """check_reference of tests/test_gpu_learner.py on every case, in both dtypes: a seed that leaves a ratio on a clip boundary, a relu
+    pre-activation at 0, clip_frac outside [0.2, 0.8] or a row term outside f64_tol's bound is found here, without a GPU; and the
+    late-Adam test's three reference steps keep their margins."""
+    import test_gpu_learner as G
+    assert len(G.CASES) == len(G.IDS) == len(set(G.IDS)) == len(G.SEEDS) == 11
+    for case, cid in zip(G.CASES, G.IDS):
+        for dtype in (torch.float64, torch.float32):
+            d = G.case_data(case, dtype, G.SEEDS[cid])
+            G.check_reference(case, d)
+            assert (d["grads32"] is None) == (dtype == torch.float64)
+    # the selections: the first idx case is 130 rows of 257, the second names every row and 100 of them twice
+    d = G.case_data(G.CASES[4], torch.float32, G.SEEDS[G.IDS[4]])
+    assert d["m"] == 130 and len(set(d["idx"].tolist())) == 130
+    d = G.case_data(G.CASES[7], torch.float32, G.SEEDS[G.IDS[7]])
+    assert d["m"] == 16485 > d["obs"].shape[0] and set(d["idx"].tolist()) == set(range(16385))
+    assert 0.25 < float((d["weight"] == 0).double().mean()) < 0.42
+    # the regimes the cases are named for, from the library's own grid
+    from beacon_amd import actor, learner
+    L = _lib()
+    for i, cid in enumerate(G.IDS):
+        if cid not in G.REGIME:
+            continue
+        m, obs_dim, hidden, activation, kind, n, _ = G.CASES[i]
+        rows = G.case_data(G.CASES[i], torch.float32, G.SEEDS[cid])["m"]
+        for f64 in (False, True):
+            cfg = _cfg(dtype=int(f64), hidden=hidden, obs_dim=obs_dim, act_dim=n, kind=int(kind == "categorical"))
+            grid = L.bcn_learner_grid(C.byref(cfg))
+            assert G.REGIME[cid](grid, G.n_tiles(rows, torch.float64 if f64 else torch.float32), f64), (cid, f64, grid)
+    for dtype in (torch.float64, torch.float32):
+        _, _, _, norms, margins = G.late_reference(dtype, 0.0)
+        assert min(r for r, _ in margins) > 1e-4 and min(p for _, p in margins) > 1e-5 and min(norms) > 1.2 * 0.5, (margins, norms)
+
+
 def test_learner_units_compile_for_gfx950_without_dpp_hazards():
     from beacon_amd import build, learner
     tool = H.objdump()
