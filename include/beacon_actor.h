@@ -90,7 +90,8 @@ BCN_ACTOR_API size_t bcn_actor_seq_bytes(const bcn_actor_cfg* cfg, int T);
  * by the usual summation-order bound only.)
  *
  * The stream.  key = (low, high 32-bit word of `seed`); (w0, w1, w2, w3) = Philox4x32-10(counter = (replica_offset + b, the
- * replica's draw counter, j, 2), key).  Word 3 of the counter is 0 for the inlet noise of bcn_set_noise and 1 for the warm-up count
+ * replica's draw counter, j, 2), key).  Word 0 of the counter is (replica_offset + b) mod 2^32: the global index wraps, as the
+ * 32-bit draw counter does.  Word 3 of the counter is 0 for the inlet noise of bcn_set_noise and 1 for the warm-up count
  * of bcn_shkadov_reset_random, so an actor may share its env's seed.
  *
  * Gaussian, deterministic = 0.  mean = the policy head.  For the pair j = 0, 1, ... of components (2j, 2j + 1):
