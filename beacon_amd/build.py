@@ -36,6 +36,8 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-fvisibility=h
 # box (round 6): the headline kernel 781 -> 772 cycles per sweep, 18.37 -> 18.18 ms over kstat's 8 steps; the float64 kernel loses
 # 0.7 % with it and keeps -O3 (profiles/r06_sched_flags_ab.log)
 FILE_FLAGS = {"ns2d_fast.hip": ["-fno-slp-vectorize", "-ffp-contract=on", "-O2"],
+              # the float32 one-row built-ins with their Jacobi cells in runs: the flags of ns2d_fast.hip
+              "ns2d_fast_runs.hip": ["-fno-slp-vectorize", "-ffp-contract=on", "-O2"],
               "ns2d_fast_f64.hip": ["-fno-slp-vectorize", "-ffp-contract=on"],
               "ns2d_fast2.hip": ["-fno-slp-vectorize", "-ffp-contract=on", "-mllvm", "-amdgpu-disable-unclustered-high-rp-reschedule",
                                  "-mllvm", "-amdgpu-sdwa-peephole=0"],

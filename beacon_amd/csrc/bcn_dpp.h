@@ -118,3 +118,5 @@ __device__ __forceinline__ double read_lane(double v, int l) {
 }
 
 }  // namespace bcn_dpp
+
+#include "bcn_jacobi_cells.h"   // runs of jacobi_cell_eq cells as one statement

@@ -306,6 +306,9 @@ struct NS2DEnv : bcn_env_s {
       if (rc != BCN_ERR_UNSUPPORTED) return rc;
       return ns2d_launch_generic<real>(a, batch, s);
     }
+    if constexpr (std::is_same<real, float>::value) {
+      if (variant == 1 && ns2d_fast_runs_supported(a)) return ns2d_launch_fast_runs(a, batch, s);
+    }
     if (variant == 1) return ns2d_launch_fast<real>(a, batch, s);
     return ns2d_launch_generic<real>(a, batch, s);
   }

@@ -16,6 +16,7 @@
 #error "ns2d_fast_impl.h (one row per lane, ny <= 64) implements the rayleigh boundary conditions only: mixing needs BCN_JIT_ROWS=2"
 #endif
 #if BCN_JIT_ROWS == 1
+#define BCN_JACOBI_RUNS 1   // float32, dx == dy: the Jacobi cells in runs where the strip width takes them (../bcn_jacobi_cells.h)
 #include "../ns2d_fast_impl.h"
 #elif BCN_JIT_ROWS == 2
 #include "../ns2d_fast2_impl.h"
@@ -87,6 +88,15 @@ __attribute__((visibility("default"))) size_t bcn_jit_lds_bytes(void) {
   return Fast2Geom<BCN_JIT_NX, BCN_JIT_NY, BCN_JIT_R, BCN_JIT_GF>::lds_elems() * sizeof(BCN_JIT_REAL);
 #else
   return (size_t)Fast4Geom<BCN_JIT_NX, BCN_JIT_NY, BCN_JIT_R, BCN_JIT_RPL>::lds_elems(sizeof(BCN_JIT_REAL)) * sizeof(BCN_JIT_REAL);
+#endif
+}
+
+// 1 where this plugin's float32 kernels state their Jacobi cells in runs (dx == dy launches)
+__attribute__((visibility("default"))) int bcn_jit_cell_runs(void) {
+#if BCN_JIT_ROWS == 1
+  return std::is_same<BCN_JIT_REAL, float>::value && bcn_dpp::jacobi_runs_fit(BCN_JIT_R) ? 1 : 0;
+#else
+  return 0;
 #endif
 }
 

@@ -87,6 +87,9 @@ size_t ns2d_generic_lds_bytes(int ncell, size_t esz);
 // register-resident CDNA4 path (ns2d_fast.hip); returns BCN_ERR_UNSUPPORTED when the grid has none
 template <typename real> bool ns2d_fast_supported(const NS2DArgs<real>& a);
 template <typename real> int ns2d_launch_fast(const NS2DArgs<real>& a, int batch, hipStream_t s);
+// the float32 one-row built-ins with their Jacobi cells in runs (ns2d_fast_runs.hip): what a float32 handle runs where this unit has its grid
+bool ns2d_fast_runs_supported(const NS2DArgs<float>& a);
+int ns2d_launch_fast_runs(const NS2DArgs<float>& a, int batch, hipStream_t s);
 // two-rows-per-lane variant for 64 < ny <= 128 (ns2d_fast2.hip), reached through ns2d_launch_fast
 // elements of field scratch one workgroup of the fast path needs for this configuration (0: fields live in LDS)
 template <typename real> size_t ns2d_fast_scratch_elems(const NS2DArgs<real>& a);

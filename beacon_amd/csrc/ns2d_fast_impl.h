@@ -36,6 +36,10 @@
 
 
 
+#ifndef BCN_JACOBI_RUNS
+#define BCN_JACOBI_RUNS 0
+#endif
+
 namespace {
 
 using namespace bcn_dpp;
@@ -687,6 +691,46 @@ __device__ __forceinline__ void fast_body(const NS2DArgs<real>& A, const int w, 
       if (NY < 64) ph *= actf;                            // lanes past the top row stay 0
       return ph;
     };
+    // The float32 dx == dy kernels state their cells in RUNS: several cells per asm statement (bcn_jacobi_cells.h), each cell the
+    // six instructions of jacobi_cell_eq, so that hipcc has no place between them to pad; every other kernel goes cell by cell.
+    // (BCN_JACOBI_RUNS: set by every unit but ns2d_fast.hip, whose kernels are pinned -- ns2d_fast_runs.hip has the float32 built-ins
+    // in its place.  Without it this header generates what it did before the runs existed.  R0, the mapping's strip width, decides
+    // for both bodies of a kernel: jacobi_runs_fit, bcn_jacobi_cells.h)
+    constexpr bool RUNS = BCN_JACOBI_RUNS && EQ && std::is_same<real, float>::value && jacobi_runs_fit(R0);
+    // DST[k] = cell(SRC[k], SRC[k + 1], SRC[k - 1], nb[k]) for K0 <= k < K1
+#define BCN_RANGE(DST, SRC, K0, K1)                                                          \
+      if constexpr (RUNS) {                                                                  \
+        jacobi_range_eq<K0, K1>(DST, SRC, nb, cx, cBy);                                      \
+        if (NY < 64) { _Pragma("unroll") for (int k = K0; k < K1; k++) DST[k] *= actf; }     \
+      } else {                                                                               \
+        _Pragma("unroll") for (int k = K0; k < K1; k++) DST[k] = cell(SRC[k], SRC[k + 1], SRC[k - 1], nb[k]); \
+      }
+    // the halo-dependent cells of a double sweep's first half: the strip's own edge columns and the neighbours' (yw, ye)
+#define BCN_EDGE4(X, Y)                                                                      \
+      real yw, ye;                                                                           \
+      if constexpr (RUNS) {                                                                  \
+        jacobi_cells_eq(Y[0], Y[R - 1], yw, ye, X[0], X[1], xw1, nb[0], X[R - 1], xe1, X[R - 2], nb[R - 1], \
+                        hW1r, X[0], hW2r, nbW, hE1r, hE2r, X[R - 1], nbE, cx, cBy);          \
+        if (NY < 64) { Y[0] *= actf; Y[R - 1] *= actf; yw *= actf; ye *= actf; }             \
+      } else {                                                                               \
+        Y[0] = cell(X[0], X[1], xw1, nb[0]);                                                 \
+        Y[R - 1] = cell(X[R - 1], xe1, X[R - 2], nb[R - 1]);                                 \
+        yw = cell(hW1r, X[0], hW2r, nbW); ye = cell(hE1r, hE2r, X[R - 1], nbE);              \
+      }                                                                                      \
+      yw = (w > 0) ? yw : Y[0];                                                              \
+      ye = (w < NW - 1) ? ye : Y[R - 1];
+    // the four exchanged cells of its second half (R == 3: columns 1 and R - 2 are one variable, which one statement cannot write twice)
+#define BCN_XCHG4(X, Y)                                                                      \
+      if constexpr (RUNS && R >= 4) {                                                        \
+        jacobi_cells_eq(X[0], X[1], X[R - 2], X[R - 1], Y[0], Y[1], yw, nb[0], Y[1], Y[2], Y[0], nb[1], \
+                        Y[R - 2], Y[R - 1], Y[R - 3], nb[R - 2], Y[R - 1], ye, Y[R - 2], nb[R - 1], cx, cBy); \
+        if (NY < 64) { X[0] *= actf; X[1] *= actf; X[R - 2] *= actf; X[R - 1] *= actf; }     \
+      } else {                                                                               \
+        X[0] = cell(Y[0], Y[1], yw, nb[0]);                                                  \
+        X[1] = cell(Y[1], Y[2], Y[0], nb[1]);                                                \
+        X[R - 2] = cell(Y[R - 2], Y[R - 1], Y[R - 3], nb[R - 2]);                            \
+        X[R - 1] = cell(Y[R - 1], ye, Y[R - 2], nb[R - 1]);                                  \
+      }
     real hW = 0, hE = 0;            // halos of the array the last sweep read
     // columns -1, -2 / R, R+1 of the array the last sweep wrote (LDS reads issued behind its barrier)
     real hW1r, hW2r, hE1r, hE2r;
@@ -732,14 +776,20 @@ __device__ __forceinline__ void fast_body(const NS2DArgs<real>& A, const int w, 
     // all cells of one sweep; the two strip-edge cells come last (their halos were requested behind the previous
     // barrier) and go to the exchange buffer at once, in front of whatever else the sweep still has to do
 #define BCN_CELLS(SRC, DST)                                                                  \
-      _Pragma("unroll") for (int k = 1; k < R - 1; k++) DST[k] = cell(SRC[k], SRC[k + 1], SRC[k - 1], nb[k]); \
+      BCN_RANGE(DST, SRC, 1, R - 1)                                                          \
       /* keep the halo-dependent part behind the interior cells: hipcc otherwise sometimes hoists the edge cells \
          (and their s_waitcnt on the LDS reads) in front of them: +170 cycles per sweep */   \
       __builtin_amdgcn_sched_barrier(0);                                                     \
       hW = (w > 0) ? hW1r : SRC[0];                                                          \
       hE = (w < NW - 1) ? hE1r : SRC[R - 1];                                                 \
-      const real p0 = cell(SRC[0], SRC[1], hW, nb[0]);                                       \
-      const real pl = cell(SRC[R - 1], hE, SRC[R - 2], nb[R - 1]);                           \
+      real p0, pl;                                                                           \
+      if constexpr (RUNS) {                                                                  \
+        jacobi_cells_eq(p0, pl, SRC[0], SRC[1], hW, nb[0], SRC[R - 1], hE, SRC[R - 2], nb[R - 1], cx, cBy); \
+        if (NY < 64) { p0 *= actf; pl *= actf; }                                             \
+      } else {                                                                               \
+        p0 = cell(SRC[0], SRC[1], hW, nb[0]);                                                \
+        pl = cell(SRC[R - 1], hE, SRC[R - 2], nb[R - 1]);                                    \
+      }                                                                                      \
       DST[0] = p0;                                                                           \
       DST[R - 1] = pl;                                                                       \
       /* one body, last strip: the Neumann ghost east of the live edge, as a cell of the register row */ \
@@ -764,28 +814,38 @@ __device__ __forceinline__ void fast_body(const NS2DArgs<real>& A, const int w, 
     // the depth-2 halos (a wall's ghost column mirrors the strip's own new edge), the second then needs nothing from other
     // waves.  Two redundant cells per 2 R, half the barriers and exchanges; every value is computed exactly as in two
     // single sweeps.
+    // The inner columns of the second sweep and the barrier.  With single-cell statements hipcc moved the barrier up between the
+    // cells (behind the third of the 12 at R = 16); a run is one statement, and with two runs of 6 it left the barrier at the end:
+    // 801 cycles per sweep against 785.  Where these columns take two runs or more the barrier stands behind their first half, and
+    // the second half runs while the slower waves arrive -- measured at R = 16 with the barrier behind 0 / 3 / 4 / 5 / 6 / 7 / 8 /
+    // 10 / 12 of the 12 cells: 825 / 800 / 775 / 794 / 769 / 767 / 770 / 777 / 801 (profiles/jacobi_runs_ab.log).  Nothing between
+    // the barrier and the halo reads behind those cells touches LDS.
+#define BCN_TAIL2(X, Y)                                                                      \
+      if constexpr (RUNS && R - 4 >= 8) {                                                    \
+        constexpr int KB = 2 + (R - 4) / 2;                                                  \
+        BCN_RANGE(X, Y, 2, KB)                                                               \
+        __builtin_amdgcn_sched_barrier(0);                                                   \
+        __syncthreads();                                                                     \
+        __builtin_amdgcn_sched_barrier(0);                                                   \
+        BCN_RANGE(X, Y, KB, R - 2)                                                           \
+      } else {                                                                               \
+        BCN_RANGE(X, Y, 2, R - 2)                                                            \
+        __syncthreads();                                                                     \
+      }
 #define BCN_FAST2X(X, Y)                                                                     \
     {                                                                                        \
-      _Pragma("unroll") for (int k = 1; k < R - 1; k++) Y[k] = cell(X[k], X[k + 1], X[k - 1], nb[k]); \
+      BCN_RANGE(Y, X, 1, R - 1)                                                              \
       __builtin_amdgcn_sched_barrier(0);                                                     \
       const real xw1 = (w > 0) ? hW1r : X[0], xe1 = (w < NW - 1) ? hE1r : X[R - 1];          \
-      Y[0] = cell(X[0], X[1], xw1, nb[0]);                                                   \
-      Y[R - 1] = cell(X[R - 1], xe1, X[R - 2], nb[R - 1]);                                   \
-      real yw = cell(hW1r, X[0], hW2r, nbW), ye = cell(hE1r, hE2r, X[R - 1], nbE);           \
-      yw = (w > 0) ? yw : Y[0];                                                              \
-      ye = (w < NW - 1) ? ye : Y[R - 1];                                                     \
+      BCN_EDGE4(X, Y)                                                                        \
       __builtin_amdgcn_sched_barrier(0);                                                     \
       /* the second sweep needs no halo: its four exchanged columns go FIRST, so that their LDS stores complete behind \
          the interior cells instead of in front of the barrier */                             \
-      X[0] = cell(Y[0], Y[1], yw, nb[0]);                                                    \
-      X[1] = cell(Y[1], Y[2], Y[0], nb[1]);                                                  \
-      X[R - 2] = cell(Y[R - 2], Y[R - 1], Y[R - 3], nb[R - 2]);                              \
-      X[R - 1] = cell(Y[R - 1], ye, Y[R - 2], nb[R - 1]);                                    \
+      BCN_XCHG4(X, Y)                                                                        \
       hW = yw; hE = ye;                                                                      \
       BCN_PUBLISH(X)                                                                         \
       __builtin_amdgcn_sched_barrier(0);                                                     \
-      _Pragma("unroll") for (int k = 2; k < R - 2; k++) X[k] = cell(Y[k], Y[k + 1], Y[k - 1], nb[k]); \
-      __syncthreads();                                                                       \
+      BCN_TAIL2(X, Y)                                                                        \
       itp += 2;                                                                              \
       BCN_HALO_READS                                                                         \
     }
@@ -871,14 +931,10 @@ __device__ __forceinline__ void fast_body(const NS2DArgs<real>& A, const int w, 
 #define BCN_CHECK2X(X, Y)                                                                    \
     {                                                                                        \
       const int itp0 = itp;                                                                  \
-      _Pragma("unroll") for (int k = 1; k < R - 1; k++) Y[k] = cell(X[k], X[k + 1], X[k - 1], nb[k]); \
+      BCN_RANGE(Y, X, 1, R - 1)                                                              \
       __builtin_amdgcn_sched_barrier(0);                                                     \
       const real xw1 = (w > 0) ? hW1r : X[0], xe1 = (w < NW - 1) ? hE1r : X[R - 1];          \
-      Y[0] = cell(X[0], X[1], xw1, nb[0]);                                                   \
-      Y[R - 1] = cell(X[R - 1], xe1, X[R - 2], nb[R - 1]);                                   \
-      real yw = cell(hW1r, X[0], hW2r, nbW), ye = cell(hE1r, hE2r, X[R - 1], nbE);           \
-      yw = (w > 0) ? yw : Y[0];                                                              \
-      ye = (w < NW - 1) ? ye : Y[R - 1];                                                     \
+      BCN_EDGE4(X, Y)                                                                        \
       BCN_NCHK_INC BCN_NCHK_INC                                                              \
       real acc1 = 0;                                                                         \
       _Pragma("unroll") for (int k = 1; k < R - 1; k++) { const real d = Y[k] - X[k]; acc1 += d * d; } \
@@ -886,14 +942,11 @@ __device__ __forceinline__ void fast_body(const NS2DArgs<real>& A, const int w, 
       const real part1 = wl * acc1 + cW * (d10 * d10) + cE * (d1l * d1l);                    \
       const real upart1 = acc1 + d10 * d10 + d1l * d1l;                                      \
       __builtin_amdgcn_sched_barrier(0);                                                     \
-      X[0] = cell(Y[0], Y[1], yw, nb[0]);                                                    \
-      X[1] = cell(Y[1], Y[2], Y[0], nb[1]);                                                  \
-      X[R - 2] = cell(Y[R - 2], Y[R - 1], Y[R - 3], nb[R - 2]);                              \
-      X[R - 1] = cell(Y[R - 1], ye, Y[R - 2], nb[R - 1]);                                    \
+      BCN_XCHG4(X, Y)                                                                        \
       hW = yw; hE = ye;                                                                      \
       BCN_PUBLISH(X)                                                                         \
       __builtin_amdgcn_sched_barrier(0);                                                     \
-      _Pragma("unroll") for (int k = 2; k < R - 2; k++) X[k] = cell(Y[k], Y[k + 1], Y[k - 1], nb[k]); \
+      BCN_RANGE(X, Y, 2, R - 2)                                                              \
       real acc2 = 0;                                                                         \
       _Pragma("unroll") for (int k = 1; k < R - 1; k++) { const real d = X[k] - Y[k]; acc2 += d * d; } \
       const real d20 = X[0] - Y[0], d2l = X[R - 1] - Y[R - 1];                               \
@@ -1031,11 +1084,15 @@ __device__ __forceinline__ void fast_body(const NS2DArgs<real>& A, const int w, 
 #undef BCN_CHECK2X
 #undef BCN_CHECK
 #undef BCN_FAST2X
+#undef BCN_TAIL2
 #undef BCN_HALO_READS
 #undef BCN_PUBLISH
 #undef BCN_FAST
 #undef BCN_SWEEP_END
 #undef BCN_CELLS
+#undef BCN_XCHG4
+#undef BCN_EDGE4
+#undef BCN_RANGE
     {
       // Guard of the extrapolating plan (conv_plan 2, 3).  A stop at sweep s is the reference's stop sweep when sweep s - 1
       // was evaluated (and failed); when the passing evaluation directly follows SKIPPED sweeps the plan's own estimate was

@@ -1,6 +1,6 @@
 """Static VALU count of the headline kernel's plain double sweep, from the compiler's own assembly (no GPU needed):
     python scripts/valu_model.py [out.json]
-compiles csrc/ns2d_fast.hip for gfx950 with the library's flags (-S, device only), finds ns2d_fast_sched<float,128,64,16,0,true,0>,
+compiles csrc/ns2d_fast_runs.hip for gfx950 with the library's flags (-S, device only), finds ns2d_fast_sched<float,128,64,16,0,true,0>,
 takes its innermost loops that contain exactly the double sweep's 2 x (R + 1) cells -- 68 DPP adds, no LDS reduction -- and counts
 their vector instructions (everything SQ_INSTS_VALU counts: v_* including DPP, v_mov, v_readlane).  bench.py multiplies the count
 by the run's sweeps to cross-check the instruction figure it rescales from the committed PMC profile."""
@@ -14,8 +14,8 @@ KERNEL = "ns2d_fast_schedIfLi128ELi64ELi16ELi0ELb1ELi0EE"
 def main():
     out = sys.argv[1] if len(sys.argv) > 1 else None
     asm = "/tmp/valu_model_ns2d_fast.s"
-    subprocess.check_call([B.hipcc()] + B.FLAGS + B.FILE_FLAGS.get("ns2d_fast.hip", []) +
-                          ["-I", B.INC, "--cuda-device-only", "-S", os.path.join(B.CSRC, "ns2d_fast.hip"), "-o", asm])
+    subprocess.check_call([B.hipcc()] + B.FLAGS + B.FILE_FLAGS.get("ns2d_fast_runs.hip", []) +
+                          ["-I", B.INC, "--cuda-device-only", "-S", os.path.join(B.CSRC, "ns2d_fast_runs.hip"), "-o", asm])
     s = open(asm).read()
     m = re.search(r'^(_Z\w*%s\w*):[^\n]*\n(.*?)\n\.Lfunc_end' % KERNEL, s, re.S | re.M)
     lines = [l.strip() for l in m.group(2).split("\n")]
