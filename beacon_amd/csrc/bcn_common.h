@@ -82,6 +82,7 @@ struct bcn_env_s {
   virtual int get_counters(uint64_t* host, hipStream_t) { memset(host, 0, (size_t)batch * 4 * sizeof(uint64_t)); return BCN_OK; }   // only the 2D register-resident kernels schedule
   virtual const char* kernel_name() const = 0;
   virtual void kernel_shape(int* k, int* nt) const { *k = 0; *nt = 0; }   // (0, 0): the env has no such notion
+  virtual int cell_runs_active() const { return 0; }   // 2D envs: the next variant-1 step runs the kernels with Jacobi cell runs
   // per-replica physical parameters (bcn_set_params; params.h)
   virtual void use_params(const void* table) = 0;   // the kernels read `table` from the next launch on (nullptr: the argument block's values)
   void* prm_dev = nullptr;      // [n_derived][B] in the handle's dtype: allocated by the first bcn_set_params, never moved (freed by bcn_destroy)

@@ -242,6 +242,7 @@ struct NS2DEnv : bcn_env_s {
     if (!strcmp(name, "sched_tail") && value >= 0 && value <= 1024) { host.sched_tail = value; return BCN_OK; }
     if (!strcmp(name, "generic_threads") && (value == 0 || value == 256 || value == 1024)) { host.generic_nt = value; return BCN_OK; }
     if (!strcmp(name, "params_kernel") && (value == 0 || value == 1)) { params_kernel = value; host.launched = nullptr; return BCN_OK; }
+    if (!strcmp(name, "cell_runs") && (value == 0 || value == 1)) { cell_runs = value; host.launched = nullptr; return BCN_OK; }
     return bcn_env_s::set_option(name, value);
   }
   int get_counters(uint64_t* host, hipStream_t s) override {
@@ -307,11 +308,21 @@ struct NS2DEnv : bcn_env_s {
       return ns2d_launch_generic<real>(a, batch, s);
     }
     if constexpr (std::is_same<real, float>::value) {
-      if (variant == 1 && ns2d_fast_runs_supported(a)) return ns2d_launch_fast_runs(a, batch, s);
+      if (runs_unit()) return ns2d_launch_fast_runs(a, batch, s);
     }
     if (variant == 1) return ns2d_launch_fast<real>(a, batch, s);
     return ns2d_launch_generic<real>(a, batch, s);
   }
+  // option "cell_runs" (default 1): 0 keeps a float32 handle on a built-in grid off ns2d_fast_runs.hip, so that its variant-1 steps go
+  // to the cell-by-cell kernels of ns2d_fast.hip (the same bits: tests/test_gpu_jacobi_cells.py)
+  int cell_runs = 1;
+  // whether a variant-1 step of this handle without a parameter table goes through the kernels with cell runs: what launch() asks,
+  // and what bcn_cell_runs_active answers
+  bool runs_unit() const {
+    if constexpr (std::is_same<real, float>::value) return variant == 1 && !plugin && cell_runs == 1 && ns2d_fast_runs_supported(a);
+    return false;
+  }
+  int cell_runs_active() const override { return !prm && runs_unit() ? 1 : 0; }
 };
 
 template <typename real>
@@ -1549,6 +1560,9 @@ int bcn_render(bcn_env_t h, const bcn_render_cfg* cfg, const uint8_t* lut_dev, c
   return render_launch(a, static_cast<hipStream_t>(stream));
 }
 const char* bcn_kernel_name(bcn_env_t h) { return h ? h->kernel_name() : ""; }
+// 1 where the next variant-1 step of a 2D handle goes through the kernels of ns2d_fast_runs.hip (option "cell_runs"; for the tests: both
+// units' kernels carry the same names).  Default visibility like bcn_jit_builtin: no part of the ABI of include/beacon_hip.h.
+extern "C" __attribute__((visibility("default"))) int bcn_cell_runs_active(bcn_env_t h) { return h ? h->cell_runs_active() : 0; }
 int bcn_kernel_shape(bcn_env_t h, int* cells_per_thread, int* threads) {
   if (!h || !cells_per_thread || !threads) { bcn_set_error("bcn_kernel_shape: null argument"); return BCN_ERR_ARG; }
   h->kernel_shape(cells_per_thread, threads);

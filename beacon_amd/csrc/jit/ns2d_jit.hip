@@ -16,7 +16,9 @@
 #error "ns2d_fast_impl.h (one row per lane, ny <= 64) implements the rayleigh boundary conditions only: mixing needs BCN_JIT_ROWS=2"
 #endif
 #if BCN_JIT_ROWS == 1
+#ifndef BCN_JACOBI_RUNS     // -DBCN_JACOBI_RUNS=0: the cell-by-cell twin of this grid's kernels (tests/test_gpu_jacobi_cells.py: the same bits)
 #define BCN_JACOBI_RUNS 1   // float32, dx == dy: the Jacobi cells in runs where the strip width takes them (../bcn_jacobi_cells.h)
+#endif
 #include "../ns2d_fast_impl.h"
 #elif BCN_JIT_ROWS == 2
 #include "../ns2d_fast2_impl.h"
@@ -94,7 +96,7 @@ __attribute__((visibility("default"))) size_t bcn_jit_lds_bytes(void) {
 // 1 where this plugin's float32 kernels state their Jacobi cells in runs (dx == dy launches)
 __attribute__((visibility("default"))) int bcn_jit_cell_runs(void) {
 #if BCN_JIT_ROWS == 1
-  return std::is_same<BCN_JIT_REAL, float>::value && bcn_dpp::jacobi_runs_fit(BCN_JIT_R) ? 1 : 0;
+  return BCN_JACOBI_RUNS && std::is_same<BCN_JIT_REAL, float>::value && bcn_dpp::jacobi_runs_fit(BCN_JIT_R) ? 1 : 0;
 #else
   return 0;
 #endif

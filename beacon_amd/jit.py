@@ -592,8 +592,39 @@ BREAK2_DEFS = {"BCN_JIT_BREAK": 2, "BCN_JIT_BREAK_EPS": "3e-4"}
 # (global scratch); rows 2 mixing; rows 4 -- and the deliberately wrong one of the self-check's test
 PRM_TEST_GRIDS = [(75, 50, False, 0), (50, 75, True, 0), (100, 110, False, 1), (50, 150, False, 0)]
 PRM_BREAK_GRID = (75, 50, True, 0)
+# The float32 one-row-per-lane strip widths whose Jacobi cells are stated in runs (csrc/bcn_jacobi_cells.h: jacobi_runs_fit), one
+# on-demand rayleigh grid per width R and, among them, every last-strip width 8..11 -- a second body that takes the runs because R
+# does -- and the 3-column last strip.  Each is built twice: the default plugin and its cell-by-cell twin (RUNS_TWIN_DEFS), which
+# tests/test_gpu_jacobi_cells.py holds to each other bit for bit.  (nx, ny, f64, kind); R / last strip in the comments.  Kept out of
+# TEST_GRIDS: the test_jit_grids_* tests need not run them.
+RUNS_GRIDS = [(52, 50, False, 0),       # 7 / 3
+              (56, 64, False, 0),       # 7 / 7, ny = 64
+              (90, 50, False, 0),       # 12 / 6
+              (104, 64, False, 0),      # 13 / 13, ny = 64
+              (105, 50, False, 0),      # 14 / 7
+              (113, 50, False, 0),      # 15 / 8
+              (121, 50, False, 0),      # 16 / 9
+              (129, 64, False, 0),      # 17 / 10, ny = 64
+              (137, 50, False, 0),      # 18 / 11
+              (152, 50, False, 0),      # 19 / 19
+              (153, 50, False, 0),      # 20 / 13
+              (168, 50, False, 0),      # 21 / 21
+              (169, 50, False, 0),      # 22 / 15
+              (184, 50, False, 0),      # 23 / 23
+              (185, 50, False, 0),      # 24 / 17
+              (195, 50, False, 0),      # 25 / 20
+              (201, 50, False, 0)]      # 26 / 19
+RUNS_TWIN_DEFS = {"BCN_JACOBI_RUNS": 0}
+# the two ends of the band of widths that stay cell by cell (R - 4 in 4..7): R = 8 and R = 11, default plugins only
+RUNS_EXCLUDED_GRIDS = [(60, 53, False, 0), (88, 50, False, 0)]
 EXTRA_BUILDS = ([((75, 50, True, 0), {"BCN_JIT_BREAK": 1}), (BREAK2_GRID, BREAK2_DEFS)] + [(g, dict(PRM_DEFS)) for g in PRM_TEST_GRIDS] +
-                [(PRM_BREAK_GRID, dict(PRM_DEFS, BCN_JIT_BREAK=1))])
+                [(PRM_BREAK_GRID, dict(PRM_DEFS, BCN_JIT_BREAK=1))] + [(g, dict(RUNS_TWIN_DEFS)) for g in RUNS_GRIDS])
+
+
+def runs_default_grids():
+    """RUNS_GRIDS and RUNS_EXCLUDED_GRIDS without those whose default plugin another list builds already."""
+    other = set(TEST_GRIDS) | set(oracle_grid_keys())
+    return [g for g in RUNS_GRIDS + RUNS_EXCLUDED_GRIDS if g not in other]
 
 
 def _bounds_job(cell):
@@ -612,7 +643,7 @@ def prebuild(grids=None, verbose=False):
     from concurrent.futures import ThreadPoolExecutor
     todo = [(g, None) for g in (grids or (TEST_GRIDS + [k for k in oracle_grid_keys() if k not in TEST_GRIDS]))]
     if grids is None:
-        todo += EXTRA_BUILDS
+        todo += [(g, None) for g in runs_default_grids()] + EXTRA_BUILDS
     with ThreadPoolExecutor(max_workers=int(os.environ.get("BEACON_JIT_JOBS", "4"))) as ex:
         paths = list(ex.map(lambda t: build_plugin(t[0][0], t[0][1], t[0][2], t[0][3], verbose, t[1]), todo))
     # the slow-mode constants of the same grids (beacon_amd/stoprule.py; only the one-row-per-lane rayleigh kernels use them),

@@ -1386,6 +1386,17 @@ class _VecNS2D(VecEnv):
         self._apply_params_kernel()
         return self
 
+    @property
+    def cell_runs_active(self):
+        """Whether the next step under variant 1 goes through the library's float32 kernels with the Jacobi cells in runs
+        (csrc/ns2d_fast_runs.hip): False for float64, for an env on a kernel plugin (the plugin says it of itself:
+        bcn_jit_cell_runs), for a grid that unit does not have, and after set_option("cell_runs", 0), which sends the env to the
+        cell-by-cell kernels of the same grid (include/beacon_hip.h: option "cell_runs").  The library answers from the predicate
+        its dispatch uses.  Like every option, "cell_runs" is lost when set_ndt_act builds the handle anew."""
+        fn = self.lib.bcn_cell_runs_active          # an internal query of the library, like bcn_jit_builtin: not in _lib.SIGNATURES
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p]
+        return bool(fn(self.h))
+
     def _apply_params_kernel(self):
         fast = self._params_kernel == "fast"
         _lib.check(self.lib.bcn_set_option(self.h, b"params_kernel", 1 if fast else 0))

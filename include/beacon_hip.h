@@ -355,6 +355,14 @@ BCN_API int bcn_set_noise(bcn_env_t h, double sigma, uint64_t seed, int64_t repl
  *                 bit for bit, what a handle created with its parameters computes on the plain register-resident kernel.  Where
  *                 there is no such kernel (a plugin without the second launcher, a batch beyond the hybrid's 32-bit addressing) and
  *                 with variant 0 the generic kernel takes the step; bcn_kernel_name says which one did.  Without a table: no effect
+ *   "cell_runs"   0 / 1 (2D envs), TEST HOOK: which unit's one-row-per-lane kernels step a BCN_F32 rayleigh handle on a built-in grid
+ *                 under variant 1.  1 (default): the kernels whose Jacobi cells are stated in runs (csrc/ns2d_fast_runs.hip), where
+ *                 that unit has the grid; 0: the cell-by-cell kernels of csrc/ns2d_fast.hip, which compute the same bits
+ *                 (tests/test_gpu_jacobi_cells.py holds the two to each other).  No effect on BCN_F64 handles, on handles with a kernel
+ *                 plugin, on grids the runs unit does not have (100x50) and on steps with a parameter table.  Both units' kernels carry
+ *                 the same names, so bcn_kernel_name cannot tell them apart; the library's internal query
+ *                 int bcn_cell_runs_active(bcn_env_t) -- exported like bcn_jit_builtin, no part of this ABI -- answers 1 where the
+ *                 next variant-1 step of the handle goes through the runs unit, from the predicate the dispatch itself uses
  *   "cells_per_thread" (1D envs) 1, 2, 4, 8 cells per thread (0 = chosen from grid and batch); "one_wave" (1D envs) 0 / 1:
  *                 grids up to 512 cells as one wave per replica with DPP halos (default 1)
  *   "obs_stage"   (lorenz, vortex) 1 = the observation rows [B][n_obs] go through LDS so that every store of a workgroup writes

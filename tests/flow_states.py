@@ -108,6 +108,17 @@ CASES = [
 ]
 
 
+# The float32 one-row-per-lane strip widths that state their Jacobi cells in runs (csrc/bcn_jacobi_cells.h), one on-demand rayleigh
+# grid per width: (nx, ny, strip width R, columns of the last strip RL).  R: every width in 7..26 with R - 4 <= 3 or R - 4 >= 8 (on
+# eight waves nx >= 50 gives R >= 7).  RL: 3 (the four exchanged cells stay cell by cell), and 8..11 -- bodies of widths that no R
+# takes the runs at, but a last strip does, because the kernel's R does.  ny = 64: no product with the activity mask of the lanes.
+# beacon_amd/jit.py builds each twice (RUNS_GRIDS: with runs and cell by cell); tests/test_jacobi_runs_host.py checks the mappings,
+# tests/test_gpu_jacobi_twins.py holds the two builds to each other bit for bit and both to the float64 oracle.
+RUNS_TABLE = [(52, 50, 7, 3), (56, 64, 7, 7), (90, 50, 12, 6), (104, 64, 13, 13), (105, 50, 14, 7), (113, 50, 15, 8), (121, 50, 16, 9),
+              (129, 64, 17, 10), (137, 50, 18, 11), (152, 50, 19, 19), (153, 50, 20, 13), (168, 50, 21, 21), (169, 50, 22, 15),
+              (184, 50, 23, 23), (185, 50, 24, 17), (195, 50, 25, 20), (201, 50, 26, 19)]
+
+
 def case_id(c):
     return "%s-%dx%d-%s" % (("rayleigh", "mixing")[c["kind"]], c["nx"], c["ny"], c["dtype"])
 
@@ -173,3 +184,16 @@ F32_ENERGETIC = {
     # mixing, the hybrid: 100x130
     (4, 1): f32tol(1.1e-6, 1.1e-6, 1.1e-5, 2.3e-6, 1.4e-6, 5.9e-7),     # m: 1.1e-07 1.1e-07 1.1e-06 2.3e-07 1.4e-07 5.9e-08
 }
+# tests/test_gpu_jacobi_twins.py: rayleigh, one row per lane, the 17 on-demand grids of RUNS_TABLE (52x50 .. 201x50), 3 replicas, against
+# the float64 oracle.  None of them exceeds the family's entry, so it stands.  Worst over the 17 grids, MEASURED on the MI355X:
+#   register-resident (plain and ticketed, both plans)   m: 5.1e-08 4.2e-08 4.1e-06 2.4e-07 1.9e-07 4.8e-06
+#   generic kernel, same inputs                           m: 5.1e-08 4.1e-08 4.3e-06 3.0e-07 1.5e-07 4.1e-06
+# (p, T/C, obs and rwd lie above the three grids' figures beside (1, 0), within its tenfold margin.  Per grid and field the
+# register-resident error is 0.08 .. 3.2 x the generic kernel's -- 153x50 p 1.7e-6 against 5.5e-7, 201x50 rwd 4.8e-6 against 1.5e-6 at
+# the top, 185x50 p 3.1e-7 against 3.7e-6 at the bottom.  p follows the stop sweep, which float32 rounding moves by one in solves of
+# 10^4 sweeps, in either kernel: on the 8 grids where all 12 sweep counts of the register-resident run are the oracle's its p error
+# is 9.8e-8 .. 6.5e-7, on the 9 where one to six differ, 153x50 among them, 9.0e-7 .. 4.1e-6.  rwd: the register-resident kernel is
+# below the generic one on 14 of the 17 grids, both between 1.3e-6 and 4.8e-6 -- taken to be the rounding of two float32 reductions
+# in different orders; T, which rwd is computed from, agrees on 201x50 (2.3e-7, 2.4e-7).  The cell-by-cell twins give the same bits,
+# so none of it is the runs'.)
+F32_RUNS_GRIDS = F32_ENERGETIC[(1, 0)]

@@ -714,11 +714,12 @@ def test_geometry_header_is_plain_cxx_and_the_library_query_agrees(tmp_path):
 def _prebuilt_plugins():
     from beacon_amd import jit
     grids = jit.TEST_GRIDS + [k for k in jit.oracle_grid_keys() if k not in jit.TEST_GRIDS]
-    return [(g, None) for g in grids] + list(jit.EXTRA_BUILDS)
+    return [(g, None) for g in grids + jit.runs_default_grids()] + list(jit.EXTRA_BUILDS)
 
 
 def test_every_prebuilt_plugin_reports_the_geometry_the_library_computes(monkeypatch):
-    """Every plugin __graft_entry__.build() compiles (jit.TEST_GRIDS, oracle_grid_keys(), EXTRA_BUILDS): its own
+    """Every plugin __graft_entry__.build() compiles (jit.TEST_GRIDS, oracle_grid_keys(), the default plugins of RUNS_GRIDS and
+    RUNS_EXCLUDED_GRIDS, EXTRA_BUILDS -- the cell-by-cell twins of RUNS_GRIDS among them): its own
     bcn_jit_lds_bytes() and bcn_jit_scratch_elems() -- the kernel templates' constants -- are jit.geometry()'s figures for the
     mapping choose() gave it.  (The shared objects load without a device.)"""
     from beacon_amd import jit
@@ -726,6 +727,9 @@ def test_every_prebuilt_plugin_reports_the_geometry_the_library_computes(monkeyp
     monkeypatch.setenv("BEACON_NO_BUILD", "1")               # prebuilt means prebuilt: a missing one is a failure, not a compile
     todo = _prebuilt_plugins()
     assert len(todo) >= 80
+    for g in jit.RUNS_GRIDS:      # both builds of every grid of tests/test_gpu_jacobi_twins.py
+        assert (g, None) in todo and (g, dict(jit.RUNS_TWIN_DEFS)) in todo, g
+    assert all((g, None) in todo for g in jit.RUNS_EXCLUDED_GRIDS)
     for (nx, ny, f64, kind), defs in todo:
         path = jit.build_plugin(nx, ny, f64, kind, extra_defs=defs)
         assert path is not None, (nx, ny, f64, kind, defs)
