@@ -1,12 +1,9 @@
 // learner_impl.h -- the kernels of libbeacon_learner.so (include/beacon_learner.h: bcn_learner_grad, bcn_learner_step), templated on
 // the real type and instantiated by learner.hip (float32) and learner_f64.hip (float64).
 //
-// The backward launch keeps the actor's tile: 256 lanes own TB rows (64 in float32, 32 in float64), activations live in LDS k-major,
-// h[k][row] with TBP = TB + 4 columns, weights are staged per slab of KS reduction steps (actor_impl.h: ActorGeom, actor_stage and the
-// math wrappers are used unchanged).  What is new:
-//   learner_layer   actor_layer's register tiling with two more things: the first layer's rows are GATHERED (idx, zero rows for
-//                   weight 0) while staging, and a transposed form, out[k][r] = (sum_o W[o][k] D[o][r]) f'(out[k][r]) IN PLACE over
-//                   the activations -- the gradient at a layer's input: the same product with the weight rows copied straight
+// The backward launch runs the actor's networks on the actor's tile: the geometry, the staging (with the learner's GATHERED rows: idx,
+// zero rows for weight 0), the layer in its forward and its transposed form, the walk over an MLP and the head's log-density terms are
+// ../actor/policy_net.h, compiled into both libraries.  What is the learner's own:
 //   learner_dw      dW[o][k] = sum_r D[o][r] X[k][r] over the tile's rows: each lane owns 4 x 4 entries, reads four 16-byte chunks of
 //                   each array per four rows (64 fma per 8 LDS reads) and adds its entries to the workgroup's slab in HBM
 // LDS: n_hidden activation buffers [hmax][TBP] (every layer's output is kept: the backward pass overwrites them with the gradients,
@@ -14,9 +11,9 @@
 // [KS][wcols], head [16][TBP], the rows' sources int32 [TB].  At the limits (3 x 128 wide): 160 256 bytes in float32, 158 336 in
 // float64, of 163 840.
 //
-// Plain fma for the same reasons as in the actor (actor_impl.h); no atomics, no inter-workgroup communication inside a launch.
+// Plain fma for the same reasons as in the actor (policy_net.h); no atomics, no inter-workgroup communication inside a launch.
 #pragma once
-#include "../actor/actor_impl.h"
+#include "../actor/actor_impl.h"          // policy_net.h comes with it
 #include "../../../include/beacon_learner.h"
 
 #define LEARNER_NT ACTOR_NT
@@ -70,133 +67,6 @@ struct LearnerAdamArgs {
   int n_elems;
   double lr, beta1, beta2, eps, max_grad_norm;
 };
-
-__device__ __forceinline__ float learner_sqrt(float x) { return sqrtf(x); }
-__device__ __forceinline__ double learner_sqrt(double x) { return sqrt(x); }
-__device__ __forceinline__ float learner_abs(float x) { return fabsf(x); }
-__device__ __forceinline__ double learner_abs(double x) { return fabs(x); }
-
-// ks columns (from k0 on) of the tile's GATHERED observation rows into LDS transposed, dst[k * TBP + r]: row r is row rowsrc[r] of obs,
-// or zeros for rowsrc[r] < 0 (behind m, weight 0).  The loads are issued before the first LDS store, as in actor_stage.
-template <typename real>
-__device__ __forceinline__ void learner_stage_obs(const real* __restrict__ obs, int K, int k0, int ks, const int* rowsrc, real* dst) {
-  constexpr int TB = ActorGeom<real>::TB, TBP = TB + 4;
-  const int total = TB * ks;
-  for (int e0 = threadIdx.x; e0 < total; e0 += LEARNER_NT * ACTOR_STAGE_U) {
-    real v[ACTOR_STAGE_U];
-    int at[ACTOR_STAGE_U];
-#pragma unroll
-    for (int u = 0; u < ACTOR_STAGE_U; u++) {
-      const int e = e0 + u * LEARNER_NT;
-      const int r = e / ks, k = e - r * ks;
-      const int s = e < total ? rowsrc[r] : -1;
-      at[u] = e < total ? k * TBP + r : -1;
-      v[u] = s >= 0 ? obs[(size_t)s * K + k0 + k] : real(0);
-    }
-#pragma unroll
-    for (int u = 0; u < ACTOR_STAGE_U; u++)
-      if (at[u] >= 0) dst[at[u]] = v[u];
-  }
-}
-
-// qs rows (from q0 on) of the row-major matrix W[.][N] into LDS as they are, dst[q * ld + n], n < n4 (zeros behind N)
-template <typename real>
-__device__ __forceinline__ void learner_stage_rows(const real* __restrict__ W, int N, int n4, int q0, int qs, real* dst, int ld) {
-  const int total = qs * n4;
-  for (int e = threadIdx.x; e < total; e += LEARNER_NT) {
-    const int q = e / n4, n = e - q * n4;
-    dst[q * ld + n] = n < N ? W[(size_t)(q0 + q) * N + n] : real(0);
-  }
-}
-
-// One layer on the workgroup's tile, out[n][r] for n < N, r < TB, a sum over R steps q in ascending order:
-//   tr = 0  out[n][r] = f(bias[n] + sum_q W[n][q] in[q][r]), W [N][R]: the forward pass (actor_layer)
-//   tr = 1  out[n][r] = (sum_q W[q][n] in[q][r]) f'(out[n][r]), W [R][N]: the gradient at the layer's input, in place over its output
-//   xin     the input in LDS (row stride TBP; must not alias out), or nullptr (tr = 0): the gathered rows of `obs`, staged per slab
-//   f       0 tanh, 1 relu, 2 identity; with tr = 1 the derivative of 0 / 1 from the layer's output: 1 - y^2, [y > 0]
-template <typename real>
-__device__ __forceinline__ void learner_layer(const real* __restrict__ W, const real* __restrict__ bias, int R, int N, int tr, int f,
-                                              const real* xin, const real* __restrict__ obs, const int* rowsrc, real* xs, real* ws, int wcols,
-                                              real* out) {
-  constexpr int TB = ActorGeom<real>::TB, KS = ActorGeom<real>::KS, TBP = TB + 4;
-  constexpr int NPASS = 2;
-  const int lane = threadIdx.x;
-  const int n4 = (N + 3) & ~3;
-  int nog = 1;
-  while (nog * 4 < n4) nog <<= 1;                   // <= 32: N <= 128
-  const int nrg = LEARNER_NT / nog;
-  const int og = lane / nrg, rg = lane - og * nrg;
-  const int o0 = og * 4;
-  const bool has_out = o0 < n4;
-
-  real acc[NPASS][4][4];                            // [pass][row][output]
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    const real bj = (bias != nullptr && has_out && o0 + j < N) ? bias[o0 + j] : real(0);
-#pragma unroll
-    for (int p = 0; p < NPASS; p++)
-#pragma unroll
-      for (int i = 0; i < 4; i++) acc[p][i][j] = bj;
-  }
-  const int r_a = rg * 4, r_b = (nrg + rg) * 4;
-  const bool act_a = has_out && r_a < TB, act_b = has_out && r_b < TB;
-
-  for (int q0 = 0; q0 < R; q0 += KS) {
-    const int qs = min(KS, R - q0);
-    __syncthreads();                                // the previous slab's (or phase's) readers of ws / xs are done, its writers too
-    if (tr) learner_stage_rows<real>(W, N, n4, q0, qs, ws, wcols);
-    else actor_stage<real>(W, R, q0, qs, n4, N, ws, wcols);
-    if (xin == nullptr) learner_stage_obs<real>(obs, R, q0, qs, rowsrc, xs);
-    __syncthreads();
-    const real* x = xin ? xin + (size_t)q0 * TBP : xs;
-    if (act_a) {
-#pragma unroll 4
-      for (int q = 0; q < qs; q++) {
-        const ActorV4<real> wq = *reinterpret_cast<const ActorV4<real>*>(ws + q * wcols + o0);
-        const ActorV4<real> xq = *reinterpret_cast<const ActorV4<real>*>(x + q * TBP + r_a);
-        const real* wv = wq.v;
-        const real* xa = xq.v;
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-          for (int j = 0; j < 4; j++) acc[0][i][j] = actor_fma(wv[j], xa[i], acc[0][i][j]);
-        if (act_b) {
-          const ActorV4<real> xr = *reinterpret_cast<const ActorV4<real>*>(x + q * TBP + r_b);
-          const real* xb = xr.v;
-#pragma unroll
-          for (int i = 0; i < 4; i++)
-#pragma unroll
-            for (int j = 0; j < 4; j++) acc[1][i][j] = actor_fma(wv[j], xb[i], acc[1][i][j]);
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int p = 0; p < NPASS; p++) {
-    const int r0 = p ? r_b : r_a;
-    if (!(p ? act_b : act_a)) continue;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      if (o0 + j >= N) continue;
-      ActorV4<real>* at = reinterpret_cast<ActorV4<real>*>(out + (o0 + j) * TBP + r0);
-      ActorV4<real> q, y;
-      if (tr) y = *at;                              // this lane's own entries: nobody else reads or writes them in this phase
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        real v = acc[p][i][j];
-        if (tr) {
-          if (f == 0) v = v * (real(1) - y.v[i] * y.v[i]);
-          else if (f == 1) v = y.v[i] > real(0) ? v : real(0);
-        } else {
-          if (f == 0) v = actor_tanh(v);
-          else if (f == 1) v = v > real(0) ? v : real(0);
-        }
-        q.v[i] = v;
-      }
-      *at = q;
-    }
-  }
-}
 
 // dW[o][k0 + k] (+)= sum_r D[o][r] X[k][r] for o < OUT, k < ks, r ascending over the tile; with k0 = 0 also db[o] (+)= sum_r D[o][r].
 // D, X: LDS, row stride TBP, complete (the caller synchronised).  gW: the workgroup's slab at the matrix [OUT][K], gB at the bias.
@@ -254,26 +124,11 @@ __device__ __forceinline__ void learner_dw(const real* D, int OUT, const real* X
   }
 }
 
-// Forward pass of one MLP on the tile: layer l's output stays in hbuf + l * hstride, the head's in `head` ([n_head][TBP]).
-template <typename real>
-__device__ __forceinline__ void learner_forward(const LearnerArgs<real>& A, const ActorNet& net, int n_head, const int* rowsrc, real* hbuf,
-                                                size_t hstride, real* xs, real* ws, real* head) {
-  const real* in = nullptr;
-  int K = A.obs_dim;
-  for (int l = 0; l < A.n_hidden; l++) {
-    real* o = hbuf + l * hstride;
-    learner_layer<real>(A.params + net.w[l], A.params + net.b[l], K, A.hidden[l], 0, A.activation, in, A.obs, rowsrc, xs, ws, A.wcols, o);
-    in = o;
-    K = A.hidden[l];
-  }
-  learner_layer<real>(A.params + net.w[A.n_hidden], A.params + net.b[A.n_hidden], K, n_head, 0, 2, in, A.obs, rowsrc, xs, ws, A.wcols, head);
-}
-
 // Backward pass of one MLP: `head` holds the gradient at the head's outputs, the activation buffers the forward pass's outputs.
 template <typename real>
 __device__ __forceinline__ void learner_backward(const LearnerArgs<real>& A, const ActorNet& net, int n_head, const int* rowsrc, real* hbuf,
                                                  size_t hstride, real* xs, real* ws, real* head, real* slab, bool first) {
-  constexpr int KS = ActorGeom<real>::KS;
+  constexpr int TB = ActorGeom<real>::TB, KS = ActorGeom<real>::KS, TBP = TB + 4;
   for (int l = A.n_hidden; l >= 0; l--) {
     const real* D = l == A.n_hidden ? head : hbuf + l * hstride;
     const int OUT = l == A.n_hidden ? n_head : A.hidden[l];
@@ -282,14 +137,14 @@ __device__ __forceinline__ void learner_backward(const LearnerArgs<real>& A, con
       const int K = A.hidden[l - 1];
       real* X = hbuf + (l - 1) * hstride;
       learner_dw<real>(D, OUT, X, K, slab + net.w[l], slab + net.b[l], K, 0, first);
-      // the gradient at this layer's input, in place over X (learner_layer synchronises before it writes anything)
-      learner_layer<real>(A.params + net.w[l], nullptr, OUT, K, 1, A.activation, D, A.obs, rowsrc, xs, ws, A.wcols, X);
+      // the gradient at this layer's input, in place over X (policy_layer synchronises before it writes anything)
+      policy_layer<real, true, true>(A.params + net.w[l], nullptr, OUT, K, A.activation, D, A.obs, 0, 0, rowsrc, xs, ws, A.wcols, X);
     } else {
       const int K = A.obs_dim;
       for (int k0 = 0; k0 < K; k0 += KS) {
         const int ks = min(KS, K - k0);
         if (k0) __syncthreads();                    // the previous slab's readers of xs are done
-        learner_stage_obs<real>(A.obs, K, k0, ks, rowsrc, xs);
+        actor_stage<real, true>(A.obs, K, k0, ks, TB, 0, rowsrc, xs, TBP);
         __syncthreads();
         learner_dw<real>(D, OUT, xs, ks, slab + net.w[0], slab + net.b[0], K, k0, first);
       }
@@ -303,6 +158,7 @@ __global__ __launch_bounds__(LEARNER_NT) void learner_backward_kernel(const Lear
   extern __shared__ __attribute__((aligned(16))) unsigned char learner_lds[];
   real* hbuf = reinterpret_cast<real*>(learner_lds);
   const size_t hstride = (size_t)A.hmax_pad * TBP;
+  const auto out_of = [=](int l) { return hbuf + l * hstride; };      // every layer's output is kept for the backward pass
   real* xs = hbuf + (size_t)A.n_hidden * hstride;     // [KS][TBP]
   real* ws = xs + (size_t)KS * TBP;                   // [KS][wcols]
   real* head = ws + (size_t)KS * A.wcols;             // [BCN_ACTOR_MAX_ACT][TBP]
@@ -342,7 +198,7 @@ __global__ __launch_bounds__(LEARNER_NT) void learner_backward_kernel(const Lear
     if (r < TB) rowsrc[r] = src;
 
     // ---- the policy network ----------------------------------------------------------------------------------------------
-    learner_forward<real>(A, A.pi, n, rowsrc, hbuf, hstride, xs, ws, head);
+    policy_mlp<real, true>(A, A.pi, n, 0, rowsrc, out_of, xs, ws, head);
     __syncthreads();
     real t_pg = real(0), t_h = real(0), t_kl = real(0), t_cf = real(0), t_v = real(0);
     if (r < TB) {
@@ -365,20 +221,12 @@ __global__ __launch_bounds__(LEARNER_NT) void learner_backward_kernel(const Lear
               const real ls = log_std[i];
               e[i] = actor_exp(-ls);
               z[i] = (a[i] - hd[i]) * e[i];
-              logp += (real(-0.5) * z[i] * z[i] - ls) - real(0.91893853320467274178);
+              logp += policy_gauss_logp<real>(z[i], ls);
               H += ls + real(1.41893853320467274178);
             }
           }
         } else {
-          real mx = hd[0];
-#pragma unroll
-          for (int i = 1; i < BCN_ACTOR_MAX_ACT; i++)
-            if (i < n && hd[i] > mx) mx = hd[i];
-          real se = real(0);
-#pragma unroll
-          for (int i = 0; i < BCN_ACTOR_MAX_ACT; i++)
-            if (i < n) se += actor_exp(hd[i] - mx);
-          const real lse = actor_log(se);
+          POLICY_LOG_SUM_EXP(hd, n)
 #pragma unroll
           for (int i = 0; i < BCN_ACTOR_MAX_ACT; i++) {
             z[i] = e[i] = real(0);
@@ -399,7 +247,7 @@ __global__ __launch_bounds__(LEARNER_NT) void learner_backward_kernel(const Lear
         t_pg = w * -(unclipped ? s1 : s2);
         t_h = w * H;
         t_kl = w * ((ratio - real(1)) - dlp);
-        t_cf = learner_abs(ratio - real(1)) > A.clip ? w : real(0);
+        t_cf = actor_abs(ratio - real(1)) > A.clip ? w : real(0);
         if (A.kind == BCN_ACTOR_GAUSSIAN) {
 #pragma unroll
           for (int i = 0; i < BCN_ACTOR_MAX_ACT; i++)
@@ -430,7 +278,7 @@ __global__ __launch_bounds__(LEARNER_NT) void learner_backward_kernel(const Lear
     learner_backward<real>(A, A.pi, n, rowsrc, hbuf, hstride, xs, ws, head, slab, first);
 
     // ---- the value network -----------------------------------------------------------------------------------------------
-    learner_forward<real>(A, A.vf, 1, rowsrc, hbuf, hstride, xs, ws, head);
+    policy_mlp<real, true>(A, A.vf, 1, 0, rowsrc, out_of, xs, ws, head);
     __syncthreads();
     if (r < TB) {
       real d = real(0);
@@ -560,7 +408,7 @@ __global__ __launch_bounds__(LEARNER_NT) void learner_adam_kernel(const LearnerA
   v = (real)A.beta2 * v + (real)(1.0 - A.beta2) * (g * g);
   A.m[p] = m;
   A.v[p] = v;
-  const real denom = learner_sqrt(v) / bc2_sqrt + (real)A.eps;
+  const real denom = actor_sqrt(v) / bc2_sqrt + (real)A.eps;
   A.params[p] = A.params[p] - step_size * (m / denom);
 }
 
@@ -585,15 +433,8 @@ template <typename real> int learner_launch_step(const LearnerAdamArgs<real>& a,
                                             int red_blocks, void* stream) {                                            \
     const size_t lds = learner_lds_bytes<real>(a.n_hidden, a.hmax_pad, a.wcols);                                        \
     static size_t lds_allowed[64] = {0};                                                                               \
-    int dev = 0;                                                                                                       \
-    hipError_t e = hipGetDevice(&dev);                                                                                 \
+    hipError_t e = policy_allow_lds(reinterpret_cast<const void*>(&learner_backward_kernel<real>), lds, lds_allowed);  \
     if (e != hipSuccess) return (int)e;                                                                                \
-    if (lds > 48 * 1024 && (dev < 0 || dev >= 64 || lds_allowed[dev] < lds)) {                                         \
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&learner_backward_kernel<real>),                           \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                                 \
-      if (e != hipSuccess) return (int)e;                                                                              \
-      if (dev >= 0 && dev < 64) lds_allowed[dev] = 160 * 1024;                                                         \
-    }                                                                                                                  \
     hipStream_t s = static_cast<hipStream_t>(stream);                                                                  \
     hipLaunchKernelGGL(learner_backward_kernel<real>, dim3(grid), dim3(LEARNER_NT), lds, s, a);                        \
     e = hipGetLastError();                                                                                             \

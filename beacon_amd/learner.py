@@ -66,9 +66,11 @@ class BeaconLearnerError(RuntimeError):
 
 
 # ---- the library -------------------------------------------------------------------------
-# what the units include from outside their directory: the actor's kernel header and what that includes
-_UNIT = _Unit("learner", FILE_FLAGS, SIGNATURES, [os.path.join(_actor.SRC_DIR, "actor_impl.h"), _actor.HEADER, os.path.join(_build.CSRC, "env1d.h"),
-                                                  os.path.join(_build.CSRC, "bcn_common.h"), os.path.join(_build.INC, "beacon_hip.h")])
+# what the units include from outside their directory: the network both libraries run (csrc/actor/policy_net.h), the actor's kernel
+# header that brings it, and what that includes
+_UNIT = _Unit("learner", FILE_FLAGS, SIGNATURES, [os.path.join(_actor.SRC_DIR, "policy_net.h"), os.path.join(_actor.SRC_DIR, "actor_impl.h"),
+                                                  _actor.HEADER, os.path.join(_build.CSRC, "env1d.h"), os.path.join(_build.CSRC, "bcn_common.h"),
+                                                  os.path.join(_build.INC, "beacon_hip.h")])
 SRC_DIR, HEADER, LIB, OBJ = _UNIT.src_dir, _UNIT.header, _UNIT.lib, _UNIT.obj
 sources, signature, stale, load = _UNIT.sources, _UNIT.signature, _UNIT.stale, _UNIT.load
 

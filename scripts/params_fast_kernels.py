@@ -21,12 +21,14 @@ number of instruction lines, and the scalar loads of the unit (s_load_*: the tab
     python scripts/params_fast_kernels.py --compare PARENT_ROOT [--jobs N] [--only TEXT] [--asm-dir DIR] [--out FILE.md]
 
 compiles every object of compare_objects() -- the generic unit, the register-resident units and their parameter twins, the plugin
-grids of COMPARE_GRIDS and the parameter plugins of jit.PRM_TEST_GRIDS -- for this tree (--root) and for the checkout at
+grids of COMPARE_GRIDS, the parameter plugins of jit.PRM_TEST_GRIDS and the four units of the actor and the learner (POLICY_UNITS;
+--only actor/, --only learner/) -- for this tree (--root) and for the checkout at
 PARENT_ROOT (a `git worktree` of the parent commit) and reports, per object and per kernel symbol, `identical` or the resource
 rows that differ: whole-file identity first, else per-function bodies with their local labels renumbered.  What a refactoring of
 the kernel sources that must not change the code is checked with.  --only: the objects whose name contains TEXT; with --asm-dir
 the parent's files already there (DIR/parent) are reused.  Exit status 1 unless every kernel is identical."""
 import argparse
+import importlib.machinery
 import importlib.util
 import json
 import os
@@ -34,6 +36,7 @@ import re
 import subprocess
 import sys
 import tempfile
+import zlib
 
 UNITS = ("ns2d_fast.hip", "ns2d_fast_f64.hip", "ns2d_fast2.hip")
 # one plugin grid per family (beacon_amd/jit.py: TEST_GRIDS): rows 1, rows 2, rows 4
@@ -43,13 +46,19 @@ PLUGIN_GRIDS = ((75, 50, False, 0), (100, 110, False, 1), (50, 150, False, 0))
 COMPARE_UNITS = ("ns2d_generic.hip",) + UNITS + ("ns2d_fast_prm.hip", "ns2d_fast_prm_f64.hip", "ns2d_fast2_prm.hip")
 COMPARE_GRIDS = ((75, 50, False, 0), (75, 50, True, 0), (52, 50, True, 0), (100, 110, False, 1), (50, 75, True, 0),
                  (100, 105, True, 1), (50, 150, False, 0), (50, 150, True, 0), (100, 200, False, 1))
+# --compare: the units that include the policy network (csrc/actor/policy_net.h)
+POLICY_UNITS = ("actor/actor.hip", "actor/actor_f64.hip", "learner/learner.hip", "learner/learner_f64.hip")
 
 
 def _load(root, name):
-    spec = importlib.util.spec_from_file_location("_pfk_" + name, os.path.join(root, "beacon_amd", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+    """beacon_amd/<name>.py of the checkout at `root`, inside a stand-in package per checkout: a module's `from . import build` is
+    that checkout's build.py, and the checkout's __init__.py does not run."""
+    pkg = "_pfk_%08x" % zlib.crc32(os.path.abspath(root).encode())
+    if pkg not in sys.modules:
+        spec = importlib.machinery.ModuleSpec(pkg, None, is_package=True)
+        spec.submodule_search_locations = [os.path.join(root, "beacon_amd")]
+        sys.modules[pkg] = importlib.util.module_from_spec(spec)
+    return importlib.import_module(pkg + "." + name)
 
 
 def normalise(text):
@@ -123,9 +132,10 @@ def resources(root, asm_dir):
     return head + "\n".join(rows) + "\n"
 
 
-def unit_asm(build, unit, out_path):
+def unit_asm(build, unit, out_path, file_flags=None):
+    """`file_flags`: the table of per-file flags when it is not build.FILE_FLAGS (the actor's, the learner's)"""
     src = os.path.join(build.CSRC, unit)
-    subprocess.check_call([build.hipcc()] + build.FLAGS + build.FILE_FLAGS.get(unit, []) +
+    subprocess.check_call([build.hipcc()] + build.FLAGS + (build.FILE_FLAGS if file_flags is None else file_flags).get(os.path.basename(unit), []) +
                           ["-I", build.INC, "--cuda-device-only", "-S", src, "-o", out_path])
     return normalise(open(out_path).read())
 
@@ -172,6 +182,8 @@ def compare_objects(jit):
     for grids, extra, tail in ((COMPARE_GRIDS, None, ""), (jit.PRM_TEST_GRIDS, {"BCN_JIT_PRM": 1}, " prm")):
         for g in grids:
             objs.append((plugin_key(g) + tail, lambda b, o, g=g, extra=extra: plugin_asm(b, plugin_defs(jit.choose, *g, extra=extra), o)))
+    for u in POLICY_UNITS:                              # their flags: FILE_FLAGS of actor.py / learner.py of the checkout `b` is of
+        objs.append((u, lambda b, o, u=u: unit_asm(b, u, o, _load(os.path.dirname(b.PKG), u.split("/")[0]).FILE_FLAGS)))
     return objs
 
 
@@ -199,7 +211,7 @@ def compare(root, parent, asm_dir, jobs, only):
 
     def one(job):
         side, (name, fn) = job
-        path = os.path.join(asm_dir, side, name.replace(" ", "_") + ".s")
+        path = os.path.join(asm_dir, side, name.replace(" ", "_").replace("/", "_") + ".s")
         if side == "parent" and os.path.exists(path):
             return normalise(open(path).read())
         return fn(sides[side], path)

@@ -65,12 +65,36 @@ def test_main_and_actor_abi_are_untouched():
     deps = {os.path.basename(f) for f in build._deps()}
     assert "beacon_learner.h" not in deps and "beacon_actor.h" not in deps and "beacon_hip.h" in deps
     assert not any("learner" in d for d in deps)
-    # the learner's units include the actor's kernel header: it is among what the .sig hashes
+    # the learner's units include the actor's kernel header and the network's (policy_net.h): both are among what the .sig hashes
     ldeps = {os.path.basename(f) for f in learner._UNIT.deps()}
-    assert {"learner.hip", "learner_f64.hip", "learner_impl.h", "actor_impl.h", "beacon_actor.h", "beacon_learner.h", "env1d.h"} <= ldeps
+    assert {"learner.hip", "learner_f64.hip", "learner_impl.h", "actor_impl.h", "policy_net.h", "beacon_actor.h", "beacon_learner.h", "env1d.h"} <= ldeps
     assert actor._UNIT.__class__ is learner._UNIT.__class__                       # one build machinery
     import beacon_amd
     assert beacon_amd.Learner is learner.Learner and "Learner" in beacon_amd.__doc__
+
+
+def test_the_shared_network_header_moves_both_signatures(monkeypatch):
+    """csrc/actor/policy_net.h is compiled into both libraries: a change of its content makes both stale.  Nothing on disk is touched:
+    the bytes the signature reads for that one file are changed."""
+    import builtins
+    import io
+    from beacon_amd import actor, learner
+    hdr = os.path.join(actor.SRC_DIR, "policy_net.h")
+    assert hdr in actor._UNIT.deps() and hdr in learner._UNIT.deps()
+    before = actor.signature(), learner.signature()
+    real_open = builtins.open
+
+    def edited(f, mode="r", *a, **kw):
+        if mode == "rb" and os.path.abspath(f) == hdr:
+            with real_open(f, "rb") as fh:
+                return io.BytesIO(fh.read() + b"\n// edited\n")
+        return real_open(f, mode, *a, **kw)
+    monkeypatch.setattr(builtins, "open", edited)
+    after = actor.signature(), learner.signature()
+    assert after[0] != before[0] and after[1] != before[1]
+    assert actor._UNIT.stale() and learner._UNIT.stale()          # whatever .sig is on disk holds another hash, or there is none
+    monkeypatch.undo()
+    assert (actor.signature(), learner.signature()) == before
 
 
 CFGS = [dict(), dict(dtype=1), dict(dtype=0, hidden=(17, 128, 3), act_dim=5, obs_dim=33), dict(dtype=1, hidden=(17, 128, 3), act_dim=5, obs_dim=33),
