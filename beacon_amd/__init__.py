@@ -13,6 +13,7 @@ stream, log-probability and value in ONE launch (actor.act() -> actions; libbeac
 The PPO update of that actor on the device:  Learner(actor, lr=3e-4) -- the clipped-surrogate loss, its gradient with respect to every
 parameter and Adam on actor.params in place, five launches per minibatch (learner.update(ro, adv, ret); libbeacon_learner.so,
 include/beacon_learner.h)
+Multi-agent shkadov under one shared policy:  Actor(env, per_jet=True) -- every (replica, jet) a row of that actor and that update
 
 Importing the package does not touch the GPU; constructing an env does, and raises if the HIP
 library or a ROCm device is missing (there is no CPU fallback for the solver path)."""

@@ -34,7 +34,8 @@ _vp = C.c_void_p
 class ActorCfg(C.Structure):
     """bcn_actor_cfg"""
     _fields_ = [("batch", C.c_int32), ("obs_dim", C.c_int32), ("dtype", C.c_int32), ("n_hidden", C.c_int32), ("hidden", C.c_int32 * 3),
-                ("activation", C.c_int32), ("kind", C.c_int32), ("act_dim", C.c_int32), ("low", C.c_double), ("high", C.c_double)]
+                ("activation", C.c_int32), ("kind", C.c_int32), ("act_dim", C.c_int32), ("low", C.c_double), ("high", C.c_double),
+                ("agents", C.c_int32)]          # appended: rows per replica, 0 means 1
 
 
 class ActorSeg(C.Structure):
@@ -79,11 +80,13 @@ def _check(rc):
         raise BeaconActorError("libbeacon_actor: error %d: %s" % (rc, load().bcn_actor_last_error().decode()))
 
 
-def make_cfg(batch, obs_dim, dtype, hidden, activation, kind, act_dim, low=-1.0, high=1.0):
-    """bcn_actor_cfg from plain values (dtype: 0 / 1; activation: "tanh" / "relu" or 0 / 1).  No range check: the library's."""
+def make_cfg(batch, obs_dim, dtype, hidden, activation, kind, act_dim, low=-1.0, high=1.0, agents=1):
+    """bcn_actor_cfg from plain values (dtype: 0 / 1; activation: "tanh" / "relu" or 0 / 1; agents: rows per replica, with
+    `batch` the number of rows).  No range check: the library's."""
     hid = [int(h) for h in hidden]
     return ActorCfg(batch=int(batch), obs_dim=int(obs_dim), dtype=int(dtype), n_hidden=len(hid), hidden=(C.c_int32 * 3)(*(hid + [0] * 3)[:3]),
-                    activation=_ACTIVATIONS.get(activation, activation), kind=int(kind), act_dim=int(act_dim), low=float(low), high=float(high))
+                    activation=_ACTIVATIONS.get(activation, activation), kind=int(kind), act_dim=int(act_dim), low=float(low), high=float(high),
+                    agents=int(agents))
 
 
 def layout(which, cfg, T=None):
@@ -138,9 +141,25 @@ class Actor(object):
       counters int32 [B] (the uint32 draw counters' bits), actions [B, act_dim] (or int32 [B]), raw [B, act_dim], logp [B],
       value [B], dist [B, act_dim]
     and, once attach()ed to a Rollout of T steps, `seq` with logp_seq [T, B], value_seq [T, B], raw_seq [T, B, act_dim].
-    Fresh parameters are zero (log_std too): load() / load_modules() / load_state_dict() fill them."""
+    Fresh parameters are zero (log_std too): load() / load_modules() / load_state_dict() fill them.
 
-    def __init__(self, env, hidden=(64, 64), activation="tanh", seed=None, replica_offset=0):
+    per_jet=True (a VecShkadov: n_jets, n_obs, a Box of n_jets components): every jet is an agent of the ONE policy, the mode of the
+    reference's shkadov_separable.  A = n_jets, obs_dim = n_obs, act_dim = 1, a row per (replica, jet): row b A + j is jet j of
+    replica b, with its own draw, log-probability, value and counter -- bit for bit what a plain actor computes for a batch of
+    B A rows [B A, n_obs] with replica_offset A in place of replica_offset.  A is not limited by the 16 action components.
+
+        env = VecShkadov(B, n_jets=5); env.set_jet_rewards()
+        actor = Actor(env, hidden=(64, 64), per_jet=True); ro = env.rollout(T); actor.attach(ro); env.reset(); ro.begin()
+        for _ in range(T):
+            env.step_autoreset(actor.act())
+        adv, ret = ro.compute_gae(actor.value_seq, actor.values(env.obs.view(-1, env.n_obs)),
+                                  actor.values(ro.final_obs.view(-1, env.n_obs)), per_jet=True)
+
+    Then counters, actions, raw, logp, value and dist are all [B, A], logp_seq and value_seq [T, B A] (what compute_gae(per_jet=True)
+    takes), raw_seq [T, B A, 1]; the mask of act() and the rollout's `valid` stay per replica, and the kernels index them by
+    row / A.  Observation normalisation keeps its per-column statistics; rwd_jets stays raw."""
+
+    def __init__(self, env, hidden=(64, 64), activation="tanh", seed=None, replica_offset=0, per_jet=False):
         try:
             hid = [int(h) for h in hidden]
             ok = all(int(h) == h and not isinstance(h, bool) for h in hidden)
@@ -153,7 +172,19 @@ class Actor(object):
         space = getattr(env, "action_space", None)
         if space is None:
             raise ValueError("Actor: env has no action_space")
-        if getattr(env, "action_is_int", False):
+        agents, obs_dim = 1, int(env.obs_dim)
+        if per_jet:
+            # every jet is an agent of the one policy: a row per (replica, jet), n_obs observations in, one action component out
+            lo = hi = None
+            if not getattr(env, "action_is_int", False) and hasattr(space, "low") and hasattr(space, "high"):
+                lo, hi = np.asarray(space.low, dtype=np.float64).reshape(-1), np.asarray(space.high, dtype=np.float64).reshape(-1)
+            nj, no = getattr(env, "n_jets", None), getattr(env, "n_obs", None)
+            if (lo is None or not all(isinstance(x, (int, np.integer)) and not isinstance(x, bool) and x >= 1 for x in (nj, no))
+                    or lo.size != nj or hi.size != nj or np.any(lo != lo[0]) or np.any(hi != hi[0]) or int(env.obs_dim) != nj * no):
+                raise ValueError("Actor: per_jet=True needs an env with n_jets, n_obs (obs_dim = n_jets n_obs) and a Box action space of "
+                                 "n_jets components with one bound pair -- a VecShkadov")
+            kind, act_dim, low, high, agents, obs_dim = GAUSSIAN, 1, float(lo[0]), float(hi[0]), int(nj), int(no)
+        elif getattr(env, "action_is_int", False):
             kind, act_dim, low, high = CATEGORICAL, int(space.n), 0.0, 0.0
             if not 2 <= act_dim <= MAX_ACT:
                 raise ValueError("Actor: env.action_space has %d classes; a categorical actor takes 2 .. %d" % (act_dim, MAX_ACT))
@@ -165,12 +196,16 @@ class Actor(object):
             if np.any(lo != lo[0]) or np.any(hi != hi[0]):
                 raise ValueError("Actor: env.action_space must be one scalar bound pair for all components")
             low, high = float(lo[0]), float(hi[0])
-        if not 1 <= int(env.obs_dim) <= MAX_OBS:
-            raise ValueError("Actor: env.obs_dim = %d; an actor reads 1 .. %d observations per replica" % (env.obs_dim, MAX_OBS))
+        if not 1 <= obs_dim <= MAX_OBS:
+            raise ValueError("Actor: %s = %d; an actor reads 1 .. %d observations per %s"
+                             % ("env.n_obs" if per_jet else "env.obs_dim", obs_dim, MAX_OBS, "jet" if per_jet else "replica"))
         self.env = env
-        self.batch, self.obs_dim, self.tdtype, self.device = int(env.batch), int(env.obs_dim), env.tdtype, torch.device(env.device)
+        self.batch, self.obs_dim, self.tdtype, self.device = int(env.batch), obs_dim, env.tdtype, torch.device(env.device)
+        self.per_jet, self.agents, self.rows = bool(per_jet), agents, int(env.batch) * agents      # rows: what the library calls batch
+        if per_jet and self.rows >= 1 << 31:
+            raise ValueError("Actor: %d replicas of %d jets are %d rows; one launch covers 2^31 - 1" % (self.batch, agents, self.rows))
         self.hidden, self.activation, self.kind, self.act_dim, self.low, self.high = tuple(hid), activation, kind, act_dim, low, high
-        self.cfg = make_cfg(self.batch, self.obs_dim, 1 if self.tdtype == torch.float64 else 0, hid, activation, kind, act_dim, low, high)
+        self.cfg = make_cfg(self.rows, self.obs_dim, 1 if self.tdtype == torch.float64 else 0, hid, activation, kind, act_dim, low, high, agents)
         self.lib = load()
         self.params_layout, nbytes = layout("params", self.cfg)
         self.params = torch.zeros((nbytes,), dtype=torch.uint8, device=self.device)
@@ -183,8 +218,11 @@ class Actor(object):
         self.state_layout, nbytes = layout("state", self.cfg)
         self.state = torch.zeros((nbytes,), dtype=torch.uint8, device=self.device)
         B, n = self.batch, act_dim
-        v = _views(self.state, self.state_layout, B, self.tdtype,
-                   {"raw": (B, n), "dist": (B, n), **({} if kind == CATEGORICAL else {"actions": (B, n)})})
+        if per_jet:                                  # a row per (replica, jet), one element each: every view is [B, n_jets]
+            shapes = {k: (B, agents) for k in ("counters", "actions", "raw", "logp", "value", "dist")}
+        else:
+            shapes = {"raw": (B, n), "dist": (B, n), **({} if kind == CATEGORICAL else {"actions": (B, n)})}
+        v = _views(self.state, self.state_layout, self.rows, self.tdtype, shapes)
         self.counters, self.actions, self.raw, self.logp, self.value, self.dist = (v[k] for k in ("counters", "actions", "raw", "logp", "value", "dist"))
         self.rollout, self.seq, self.T = None, None, 0
         self.logp_seq = self.value_seq = self.raw_seq = None
@@ -239,15 +277,17 @@ class Actor(object):
         return self.load(pairs("pi_module", pi_module), pairs("vf_module", vf_module), log_std)
 
     def state_dict(self):
-        """For checkpoints: both buffers on the CPU, what they were laid out for, seed and replica offset."""
+        """For checkpoints: both buffers on the CPU, what they were laid out for (`agents`: the rows per replica, 1 for a plain
+        actor), seed and replica offset."""
         return {"params": self.params.cpu(), "state": self.state.cpu(), "batch": self.batch, "obs_dim": self.obs_dim,
                 "dtype": "f64" if self.tdtype == torch.float64 else "f32", "hidden": self.hidden, "activation": self.activation,
-                "kind": self.kind, "act_dim": self.act_dim, "seed": self.seed, "replica_offset": self.replica_offset}
+                "kind": self.kind, "act_dim": self.act_dim, "seed": self.seed, "replica_offset": self.replica_offset, "agents": self.agents}
 
     def load_state_dict(self, d):
-        keys = ("batch", "obs_dim", "dtype", "activation", "kind", "act_dim")
+        keys = ("batch", "obs_dim", "dtype", "activation", "kind", "act_dim", "agents")
         cur = {"batch": self.batch, "obs_dim": self.obs_dim, "dtype": "f64" if self.tdtype == torch.float64 else "f32",
-               "activation": self.activation, "kind": self.kind, "act_dim": self.act_dim}
+               "activation": self.activation, "kind": self.kind, "act_dim": self.act_dim, "agents": self.agents}
+        d = dict(d, agents=d.get("agents", 1))       # a state written before there were agents is of a plain actor
         if (any(d[k] != cur[k] for k in keys) or tuple(d["hidden"]) != self.hidden or d["params"].numel() != self.params.numel()
                 or d["state"].numel() != self.state.numel()):
             raise ValueError("Actor.load_state_dict: the state is of another actor (%s, hidden %s); this one is %s, hidden %s"
@@ -286,11 +326,21 @@ class Actor(object):
         default: what the env's last reset() / step() returned -- env._norm.norm_obs while it normalises, else env.obs), the draw
         (deterministic=True: the mean / the first most probable class, no draw, no counter tick), the outputs into `state` and,
         with a rollout attached, into the slot its device cursor names.  `mask` ([B] bool / uint8): replicas with 0 keep their
-        output rows and counters.  Returns `actions`: what env.step() / step_autoreset() take."""
+        output rows and counters.  Returns `actions`: what env.step() / step_autoreset() take.
+        per_jet: `obs` is [B, n_jets n_obs] or [B n_jets, n_obs] (the same bytes); `mask` stays [B], and a replica with 0 keeps
+        all of its jets' rows and counters; `actions` is [B, n_jets]."""
         env = self.env
         if obs is None:
             obs = env._norm.norm_obs if getattr(env, "_norm_on", False) else env.obs
-        self._rows("obs", obs, self.batch)
+        if self.per_jet:
+            # the row is jet-major: [B, n_jets n_obs] IS [B n_jets, n_obs], the same bytes
+            if (not torch.is_tensor(obs) or obs.dtype != self.tdtype or obs.device != self.device or not obs.is_contiguous() or obs.dim() != 2
+                    or tuple(obs.shape) not in ((self.batch, self.agents * self.obs_dim), (self.rows, self.obs_dim))):
+                raise ValueError("Actor: obs must be a contiguous %s tensor [%d, %d] or [%d, %d] on %s"
+                                 % ("f64" if self.tdtype == torch.float64 else "f32", self.batch, self.agents * self.obs_dim, self.rows,
+                                    self.obs_dim, self.device))
+        else:
+            self._rows("obs", obs, self.batch)
         m = None
         if mask is not None:
             if not torch.is_tensor(mask):
@@ -330,7 +380,7 @@ class Actor(object):
         cfg_layout, nbytes = layout("seq", self.cfg, T)
         if self.seq is None or self.seq.numel() != nbytes:
             self.seq = torch.zeros((nbytes,), dtype=torch.uint8, device=self.device)
-        B, n = self.batch, self.act_dim
+        B, n = self.rows, self.act_dim               # per_jet: B n_jets columns, the shape Rollout.compute_gae(per_jet=True) takes
         v = _views(self.seq, cfg_layout, B, self.tdtype, {"logp_seq": (T, B), "value_seq": (T, B), "raw_seq": (T, B, n)})
         self.seq_layout, self.logp_seq, self.value_seq, self.raw_seq = cfg_layout, v["logp_seq"], v["value_seq"], v["raw_seq"]
         self.rollout, self.T = rollout, T

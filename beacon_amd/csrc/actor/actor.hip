@@ -101,8 +101,10 @@ static int actor_act_t(const bcn_actor_cfg* c, const void* params, const void* o
   a.value = reinterpret_cast<real*>(st + s[4].offset);
   a.dist = reinterpret_cast<real*>(st + s[5].offset);
   a.mask = mask;
+  a.agents = policy_agents(c);
   a.seed_lo = (uint32_t)(seed & 0xffffffffull); a.seed_hi = (uint32_t)(seed >> 32);
-  a.replica_offset = (long long)replica_offset;
+  // row 0's global index: the first replica's times the rows per replica, in 64 bits (the kernel adds b and keeps the low word)
+  a.replica_offset = (long long)((unsigned long long)replica_offset * (unsigned long long)a.agents);
   a.deterministic = deterministic != 0;
   if (cursor) {
     bcn_actor_seq_layout(c, T, s, BCN_ACTOR_MAX_SEGS);

@@ -1,6 +1,8 @@
 // actor_impl.h -- the actor kernel (include/beacon_actor.h: bcn_actor_act, bcn_actor_values), templated on the real type and
 // instantiated by actor.hip (float32, the hot path) and actor_f64.hip (float64).  The networks -- tile, staging, layers, the head's
 // log-density terms -- are policy_net.h; here: the two MLPs on the tile, then one lane per replica draws and writes.
+// With cfg.agents = A > 1 a "replica" below is a ROW, agent b % A of replica b / A: only the mask is indexed per replica (b / A),
+// and the host passes replica_offset A as the index of row 0.
 #pragma once
 #include "../env1d.h"                     // bcn_philox4x32: the project's one Philox definition
 #include "policy_net.h"
@@ -21,13 +23,14 @@ struct ActorArgs {
   uint32_t* counters;
   void* actions;                    // real [B][act_dim] or int32 [B]
   real *raw, *logp, *value, *dist;
-  const uint8_t* mask;
+  const uint8_t* mask;              // [n_rows / agents]: one byte per replica
   uint32_t seed_lo, seed_hi;
-  long long replica_offset;
+  long long replica_offset;         // the global index of row 0: the first replica's times agents
   int deterministic;
   const int32_t* cursor;
   int T;
   real *logp_seq, *value_seq, *raw_seq;
+  int agents;                       // rows per replica, >= 1 (last: the fields above keep their offsets)
 };
 
 // ln u1 and 2 u2 of the Box-Muller pair from the four Philox words (beacon_actor.h).
@@ -75,7 +78,8 @@ __global__ __launch_bounds__(ACTOR_NT) void actor_kernel(const ActorArgs<real> A
   if (r >= TB || b >= A.n_rows) return;
   const real value = vf[r];
   if (A.values_only) { A.value[b] = value; return; }
-  if (A.mask && A.mask[b] == 0) return;
+  // the mask is per replica: with agents the row's byte is b / agents (b < 2^31, cfg.batch is an int32: one 32-bit division per row)
+  if (A.mask && A.mask[A.agents > 1 ? (long long)((uint32_t)b / (uint32_t)A.agents) : b] == 0) return;
 
   const int n = A.act_dim;
   real head[BCN_ACTOR_MAX_ACT], rawv[BCN_ACTOR_MAX_ACT];

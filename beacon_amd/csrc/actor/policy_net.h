@@ -266,8 +266,16 @@ inline bool policy_cfg_ok(const bcn_actor_cfg* c, bool need_batch, PolicyErr* er
   const int lo = c->kind == BCN_ACTOR_GAUSSIAN ? 1 : 2;
   if (c->act_dim < lo || c->act_dim > BCN_ACTOR_MAX_ACT) { err->set("cfg.act_dim = %d: must lie in %d .. %d for this kind", c->act_dim, lo, BCN_ACTOR_MAX_ACT); return false; }
   if (c->kind == BCN_ACTOR_GAUSSIAN && !(c->low <= c->high)) { err->set("cfg.low = %g, cfg.high = %g: need low <= high", c->low, c->high); return false; }
+  if (c->agents < 0) { err->set("cfg.agents = %d: must be >= 0 (0 means 1)", c->agents); return false; }
+  if (need_batch && c->agents > 1 && c->batch % c->agents != 0) {
+    err->set("cfg.batch = %d is no multiple of cfg.agents = %d: batch counts rows, agents per replica", c->batch, c->agents);
+    return false;
+  }
   return true;
 }
+
+// rows per replica of a cfg: cfg.agents, 0 meaning 1
+inline int policy_agents(const bcn_actor_cfg* c) { return c->agents > 1 ? c->agents : 1; }
 
 inline size_t policy_esz(const bcn_actor_cfg* c) { return c->dtype ? 8 : 4; }
 

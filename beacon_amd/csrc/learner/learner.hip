@@ -111,6 +111,7 @@ static int learner_grad_t(const bcn_actor_cfg* c, const void* params, const bcn_
   a.ret = static_cast<const real*>(b->ret_dev);
   a.weight = b->weight_dev; a.weight_kind = b->weight_kind;
   a.idx = b->idx_dev; a.cursor = b->cursor_dev; a.rows_per_step = b->rows_per_step;
+  a.rows_per_weight = b->rows_per_weight > 1 ? b->rows_per_weight : 1;
   a.n_rows = (long long)b->n_rows; a.m = (long long)b->m;
   a.tiles = (a.m + TB - 1) / TB;
   bcn_actor_seg s[BCN_ACTOR_MAX_SEGS];
@@ -200,6 +201,11 @@ BCN_LEARNER_API int bcn_learner_grad(const bcn_actor_cfg* cfg, const void* param
     return BCN_LEARNER_ERR_ARG;
   }
   if (b->cursor_dev && b->rows_per_step < 1) { g_learner_err.set("bcn_learner_grad: batch.rows_per_step = %d: a cursor needs >= 1", b->rows_per_step); return BCN_LEARNER_ERR_ARG; }
+  if (b->rows_per_weight < 0) { g_learner_err.set("bcn_learner_grad: batch.rows_per_weight = %d: must be >= 0 (0 means 1)", b->rows_per_weight); return BCN_LEARNER_ERR_ARG; }
+  if (b->rows_per_weight > 1 && b->n_rows % b->rows_per_weight != 0) {
+    g_learner_err.set("bcn_learner_grad: batch.rows_per_weight = %d does not divide batch.n_rows = %lld", b->rows_per_weight, (long long)b->n_rows);
+    return BCN_LEARNER_ERR_ARG;
+  }
   if (!(loss->clip >= 0.0)) { g_learner_err.set("bcn_learner_grad: loss.clip = %g: must be >= 0", loss->clip); return BCN_LEARNER_ERR_ARG; }
   return cfg->dtype ? learner_grad_t<double>(cfg, params_dev, b, loss, grad_dev, work_dev, stream)
                     : learner_grad_t<float>(cfg, params_dev, b, loss, grad_dev, work_dev, stream);

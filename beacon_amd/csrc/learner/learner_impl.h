@@ -40,6 +40,7 @@ struct LearnerArgs {
   real* slabs;                      // [grid][slab_elems]
   size_t slab_elems;
   double* wg_stats;                 // [grid][8]
+  int rows_per_weight;              // consecutive rows that share one element of weight, >= 1 (last: the fields above keep their offsets)
 };
 
 template <typename real>
@@ -184,9 +185,11 @@ __global__ __launch_bounds__(LEARNER_NT) void learner_backward_kernel(const Lear
         lim = min(lim, c * (long long)A.rows_per_step);
       }
       if (s >= 0 && s < lim) {
+        // the row's weight element: s itself, or s / rows_per_weight (s < n_rows < 2^31: one 32-bit division per row per tile)
+        const long long ws = A.rows_per_weight > 1 ? (long long)((uint32_t)s / (uint32_t)A.rows_per_weight) : s;
         real wv = real(1);
-        if (A.weight_kind == BCN_LEARNER_W_U8) wv = (real) static_cast<const uint8_t*>(A.weight)[s];
-        else if (A.weight_kind == BCN_LEARNER_W_REAL) wv = static_cast<const real*>(A.weight)[s];
+        if (A.weight_kind == BCN_LEARNER_W_U8) wv = (real) static_cast<const uint8_t*>(A.weight)[ws];
+        else if (A.weight_kind == BCN_LEARNER_W_REAL) wv = static_cast<const real*>(A.weight)[ws];
         bool ok = wv > real(0);
         if (ok && A.kind == BCN_ACTOR_CATEGORICAL) {
           cls = static_cast<const int32_t*>(A.act)[s];

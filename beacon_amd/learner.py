@@ -32,7 +32,8 @@ _vp = C.c_void_p
 class LearnerBatch(C.Structure):
     """bcn_learner_batch"""
     _fields_ = [("obs", _vp), ("act", _vp), ("logp_old", _vp), ("adv", _vp), ("ret", _vp), ("weight", _vp), ("idx", _vp), ("cursor", _vp),
-                ("n_rows", C.c_int64), ("m", C.c_int64), ("weight_kind", C.c_int32), ("rows_per_step", C.c_int32)]
+                ("n_rows", C.c_int64), ("m", C.c_int64), ("weight_kind", C.c_int32), ("rows_per_step", C.c_int32),
+                ("rows_per_weight", C.c_int32)]     # appended: consecutive rows that share one weight, 0 means 1
 
 
 class LearnerLoss(C.Structure):
@@ -131,7 +132,10 @@ class Learner(object):
     value loss, entropy, approx_kl, clip_frac, W, the gradient norm before clipping -- read by stats_dict(), the only host read).
     The hyperparameters are plain attributes (lr, clip_range, vf_coef, ent_coef, max_grad_norm, betas, eps): they are ARGUMENTS of
     the launches, so a captured graph keeps what it was recorded with.  max_grad_norm <= 0 or None: no clipping.
-    Not covered: ShardedVecEnv (no gradient all-reduce), per-jet policies, learning-rate schedules, value clipping."""
+    A per-jet actor (Actor(env, per_jet=True)) is updated the same way: update() then takes adv / ret of
+    ro.compute_gae(..., per_jet=True), every (step, replica, jet) is a row and the rollout's per-replica `valid` bytes weigh all
+    jets of their replica (grad's rows_per_weight).
+    Not covered: ShardedVecEnv (no gradient all-reduce), learning-rate schedules, value clipping."""
 
     def __init__(self, actor, lr=3e-4, clip_range=0.2, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5, betas=(0.9, 0.999), eps=1e-8):
         if not isinstance(actor, _actor.Actor):
@@ -195,11 +199,12 @@ class Learner(object):
                              % (name, str(dtype).replace("torch.", ""), n, " x %d" % cols if cols else "", self.device))
         return t
 
-    def grad(self, obs_rows, actions, logp_old, adv, ret, weight=None, idx=None, _cursor=None, _rows_per_step=0):
+    def grad(self, obs_rows, actions, logp_old, adv, ret, weight=None, idx=None, _cursor=None, _rows_per_step=0, rows_per_weight=1):
         """Loss, statistics and gradient of one minibatch: THREE launches on the current stream, no host synchronisation, nothing
         allocated.  obs_rows [N, obs_dim]; actions [N, act_dim] (Gaussian: the unclipped samples, actor.raw_seq) or int32 [N]
         (categorical); logp_old, adv, ret [N] (any shape with N elements); weight: None (all 1), or uint8 / bool / the env dtype
-        [N], >= 0 (ro.valid is the intended one); idx: None -- the minibatch is all N rows -- or an int32 tensor of row numbers:
+        [N / rows_per_weight], >= 0 (ro.valid is the intended one; rows_per_weight: an integer >= 1 that divides N -- row s takes
+        weight[s // rows_per_weight], so the n_jets rows of a replica share its one `valid` byte); idx: None -- the minibatch is all N rows -- or an int32 tensor of row numbers:
         the minibatch is those rows, gathered on the device while staging.  Rows of weight 0 may hold anything, NaN included.
         Contiguous device tensors of the env dtype.  Returns (grads, stats): {segment name: view of the gradient buffer} and the
         float64 [8] statistics ON THE DEVICE (stats_dict() reads them).  ValueError for a wrong shape, dtype or device, before any
@@ -216,12 +221,16 @@ class Learner(object):
         self._vec("logp_old", logp_old, N)
         self._vec("adv", adv, N)
         self._vec("ret", ret, N)
+        if isinstance(rows_per_weight, bool) or not isinstance(rows_per_weight, (int, np.integer)) or rows_per_weight < 1 \
+                or N % int(rows_per_weight):
+            raise ValueError("Learner.grad: rows_per_weight must be an integer >= 1 that divides the %d rows, got %r" % (N, rows_per_weight))
+        rpw = int(rows_per_weight)
         wk = W_NONE
         if weight is not None:
             if torch.is_tensor(weight) and weight.dtype == torch.bool:
                 weight = weight.view(torch.uint8)
             wk = W_U8 if torch.is_tensor(weight) and weight.dtype == torch.uint8 else W_REAL
-            self._vec("weight", weight, N, dtype=torch.uint8 if wk == W_U8 else self.tdtype)
+            self._vec("weight", weight, N // rpw, dtype=torch.uint8 if wk == W_U8 else self.tdtype)
         m = N
         if idx is not None:
             if not torch.is_tensor(idx) or idx.dtype != torch.int32 or idx.device != self.device or not idx.is_contiguous() or idx.dim() != 1 \
@@ -232,7 +241,7 @@ class Learner(object):
         self._keep = (obs_rows, actions, logp_old, adv, ret, weight, idx, _cursor)      # alive behind the asynchronous launches
         p = _actor._ptr
         b = LearnerBatch(obs=p(obs_rows), act=p(actions), logp_old=p(logp_old), adv=p(adv), ret=p(ret), weight=p(weight), idx=p(idx),
-                         cursor=p(_cursor), n_rows=N, m=m, weight_kind=wk, rows_per_step=int(_rows_per_step))
+                         cursor=p(_cursor), n_rows=N, m=m, weight_kind=wk, rows_per_step=int(_rows_per_step), rows_per_weight=rpw)
         loss = LearnerLoss(clip=self.clip_range, vf_coef=self.vf_coef, ent_coef=self.ent_coef)
         _check(self.lib.bcn_learner_grad(C.byref(self.cfg), p(a.params), C.byref(b), C.byref(loss), p(self.grad_buf), p(self.work), stream))
         return self.grads, self.stats
@@ -257,28 +266,40 @@ class Learner(object):
         (torch ops on the device; mean and the unbiased standard deviation + 1e-8).  Per epoch one torch.randperm of the T B rows
         on the device (`generator`: a torch.Generator of that device, for reproducible minibatches) is cut into `minibatches`
         index ranges, and each gets grad() + step().  Rows of steps the rollout has not recorded get weight 0 ON THE DEVICE, from
-        its cursor: the host never reads it.  No host synchronisation.  Returns self."""
+        its cursor: the host never reads it.  No host synchronisation.  Returns self.
+        With a per-jet actor (A = n_jets) the rows are the T B A (step, replica, jet) triples: obs = ro.obs[:-1] read as
+        [T B A, n_obs], the actions actor.raw_seq, adv and ret [T, B A] from ro.compute_gae(..., per_jet=True); ro.valid is passed as
+        it is, T B bytes, each weighing the A rows of its replica on the device.  The standardisation pools all jets: a valid step
+        counts A times."""
         a = self.actor
         if a.rollout is not ro or ro is None:
             raise ValueError("Learner.update: ro must be the Rollout this learner's actor is attached to")
         for name, x in (("epochs", epochs), ("minibatches", minibatches)):
             if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < 1:
                 raise ValueError("Learner.update: %s must be an integer >= 1, got %r" % (name, x))
-        T, B = int(ro.T), a.batch
-        N = T * B
+        T, B, A = int(ro.T), a.batch, a.agents
+        N = T * B * A
         if minibatches > N:
             raise ValueError("Learner.update: %d minibatches of %d rows" % (minibatches, N))
+        if A > 1:
+            for name, x in (("adv", adv), ("ret", ret)):
+                if not torch.is_tensor(x) or x.numel() != N:
+                    raise ValueError("Learner.update: with a per-jet actor %s must hold %d x %d x %d elements: pass what "
+                                     "ro.compute_gae(..., per_jet=True) returns" % (name, T, B, A))
         self._vec("adv", adv, N)
         self._vec("ret", ret, N)
         self._stream()
         obs = ro.obs[:-1].reshape(N, a.obs_dim)
         actions = ro.act.reshape(N) if a.kind == _actor.CATEGORICAL else a.raw_seq.reshape(N, a.act_dim)
         logp_old = a.logp_seq.reshape(N)
-        valid = ro.valid.reshape(N)
+        valid = ro.valid.reshape(T * B)              # per replica: grad's rows_per_weight = A spreads a byte over its A rows
         adv, ret = adv.reshape(N), ret.reshape(N)
         if normalize_adv:
             t = torch.arange(T, device=self.device, dtype=torch.int32).view(T, 1)
-            w = (valid.view(T, B) * (t < ro.cursor[0])).reshape(N).to(self.tdtype)
+            w = valid.view(T, B) * (t < ro.cursor[0])
+            if A > 1:
+                w = w.view(T, B, 1).expand(T, B, A)
+            w = w.reshape(N).to(self.tdtype)
             cnt = w.sum().clamp_(min=1.0)
             mean = (torch.where(w > 0, adv, torch.zeros_like(adv))).sum() / cnt
             var = (torch.where(w > 0, adv - mean, torch.zeros_like(adv)) ** 2).sum() / (cnt - 1.0).clamp_(min=1.0)
@@ -287,7 +308,7 @@ class Learner(object):
             perm = torch.randperm(N, device=self.device, generator=generator).to(torch.int32)
             for k in range(int(minibatches)):
                 idx = perm[k * N // minibatches:(k + 1) * N // minibatches]
-                self.grad(obs, actions, logp_old, adv, ret, weight=valid, idx=idx, _cursor=ro.cursor, _rows_per_step=B)
+                self.grad(obs, actions, logp_old, adv, ret, weight=valid, idx=idx, _cursor=ro.cursor, _rows_per_step=B * A, rows_per_weight=A)
                 self.step()
         return self
 

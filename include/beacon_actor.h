@@ -45,6 +45,9 @@ typedef struct {
   int32_t kind;         /* BCN_ACTOR_GAUSSIAN / BCN_ACTOR_CATEGORICAL */
   int32_t act_dim;      /* Gaussian: 1 .. 16 components; categorical: 2 .. 16 classes */
   double low, high;     /* the Box bound of a Gaussian action, low <= high (ignored by the categorical kind) */
+  int32_t agents;       /* APPENDED (a cfg that ends at `high`, zero-filled behind it, means what it meant): rows per replica, >= 0;
+                         * 0 means 1.  With agents = A > 1 the rows are the agents of B / A replicas, row b = agent b % A of
+                         * replica b / A (shkadov's jets under one shared policy): `batch` stays the number of ROWS, a multiple of A */
 } bcn_actor_cfg;
 
 /* One named segment of a packed buffer: planes arrays of [rows][row_elems] elements of kind `elem` at `offset` bytes, one behind the
@@ -111,6 +114,13 @@ BCN_ACTOR_API size_t bcn_actor_seq_bytes(const bcn_actor_cfg* cfg, int T);
  *
  * The draw counter.  A stochastic launch advances the counter of every replica it writes by one.
  * mask_dev (uint8 [B], may be NULL): a replica whose byte is 0 keeps every output row and its counter.
+ * Agents.  With cfg.agents = A > 1 every per-row rule above holds with "row" for "replica" (B = cfg.batch rows, each with its own
+ *   draw, outputs and counter), except that
+ *     mask_dev is uint8 [B / A], one byte per REPLICA: row b reads mask_dev[b / A], so a masked replica keeps all A rows;
+ *     replica_offset stays the global index of the first REPLICA: word 0 of the counter is (replica_offset A + b) mod 2^32, the
+ *     product taken in 64 bits -- what a batch of B rows with replica_offset A in place of replica_offset draws, and what the
+ *     rows of this shard draw in the unsharded batch.
+ *   A = 0 or 1: nothing changes.
  * The rollout slot.  With cursor_dev != NULL (int32, the `cursor` segment of a rollout buffer) the launch reads t = cursor_dev[0] ON
  *   THE DEVICE; if 0 <= t < T it also writes logp, value and raw of the replicas it writes into row t of seq_dev
  *   (bcn_actor_seq_layout(cfg, T)); otherwise it writes no slot.  The cursor is never written.  cursor_dev = NULL: seq_dev and T are

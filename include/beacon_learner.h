@@ -51,6 +51,9 @@
  * device.  Of an inactive row only idx and the weight (and the class) are read; its observation, adv, ret and logp_old may hold
  * anything, NaN included: it is staged as zeros and adds +0 to every sum.  Rows behind m stage as zeros too.  Nothing is read
  * past a row or past an array.
+ * With rows_per_weight = R > 1 the weight of source row s is weight_dev[s / R] and weight_dev holds n_rows / R elements: the
+ * per-agent rows of an actor with cfg.agents = R under the per-replica `valid` bytes of a rollout.  Every other array, idx_dev,
+ * the cursor rule and rows_per_step count ROWS as before.  R = 0 or 1: nothing changes.
  *
  * ---- Launches -------------------------------------------------------------------------------------------------------------
  * bcn_learner_grad, three launches in stream order:
@@ -103,13 +106,15 @@ typedef struct {
   const void* logp_old_dev;  /* real [n_rows] */
   const void* adv_dev;       /* real [n_rows] */
   const void* ret_dev;       /* real [n_rows] */
-  const void* weight_dev;    /* uint8 or real [n_rows] by weight_kind; ignored (may be NULL) for BCN_LEARNER_W_NONE */
+  const void* weight_dev;    /* uint8 or real [n_rows / rows_per_weight] by weight_kind; ignored (may be NULL) for BCN_LEARNER_W_NONE */
   const int32_t* idx_dev;    /* int32 [m] row numbers, or NULL: rows 0 .. m - 1 (then m <= n_rows) */
   const int32_t* cursor_dev; /* int32, the `cursor` segment of a rollout buffer, or NULL */
   int64_t n_rows;            /* rows of every per-row array, >= 1 */
   int64_t m;                 /* rows of the minibatch, 1 .. 2^31 - 1 */
   int32_t weight_kind;       /* BCN_LEARNER_W_* */
-  int32_t rows_per_step;     /* with cursor_dev: rows per recorded step (the rollout's batch), >= 1 */
+  int32_t rows_per_step;     /* with cursor_dev: rows per recorded step (the rollout's batch; with agents: batch x agents), >= 1 */
+  int32_t rows_per_weight;   /* APPENDED (a batch that ends at rows_per_step, zero-filled behind it, means what it meant): consecutive
+                              * rows that share one weight, >= 0; 0 means 1.  It divides n_rows */
 } bcn_learner_batch;
 
 typedef struct {
