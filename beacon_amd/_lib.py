@@ -3,7 +3,6 @@
 The product path has NO CPU fallback: if the HIP library cannot be built/loaded, or no
 GPU is visible, every env constructor raises."""
 import ctypes as C
-import os
 
 from . import build as _build
 
@@ -180,29 +179,15 @@ def lib_path():
 def load():
     """dlopen the in-tree library (building it first when stale and hipcc is present)."""
     global _LIB
-    if _LIB is not None:
-        return _LIB
-    path = _build.LIB
-    if _build.stale():
-        # BEACON_NO_BUILD=1 (exported by the profiling scripts): never spawn a compiler from this process --
-        # under rocprofv3 the children would inherit the profiler's preload (scripts/prof_bench.sh).
-        # A stale binary is never dlopen'ed: its cfg structs / signatures may disagree with this source tree.
-        if os.environ.get("BEACON_NO_BUILD") == "1":
-            raise RuntimeError("libbeacon_hip.so is missing or stale and BEACON_NO_BUILD=1: run "
-                               "`python -c 'import __graft_entry__ as g; g.build()'` first")
-        if _build.hipcc() is None:
-            raise RuntimeError("libbeacon_hip.so is missing or older than its sources and hipcc is not "
-                               "available to build it; beacon_amd has no CPU fallback")
-        path = _build.build_lib()
-    L = C.CDLL(path, mode=C.RTLD_GLOBAL)   # the on-demand kernel plugins resolve bcn_set_error against it
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(L, name)  # AttributeError if the library lacks a declared symbol
-        fn.restype = res
-        fn.argtypes = args
-    if L.bcn_api_version() != API_VERSION:
-        raise RuntimeError("libbeacon_hip.so has API version %d, this binding expects %d" % (L.bcn_api_version(), API_VERSION))
-    _LIB = L
-    return L
+    if _LIB is None:
+        # RTLD_GLOBAL: the on-demand kernel plugins resolve bcn_set_error against it
+        L = _build.MAIN.load(SIGNATURES, mode=C.RTLD_GLOBAL,
+                             no_compiler="libbeacon_hip.so is missing or older than its sources and hipcc is not "
+                                         "available to build it; beacon_amd has no CPU fallback")
+        if L.bcn_api_version() != API_VERSION:
+            raise RuntimeError("libbeacon_hip.so has API version %d, this binding expects %d" % (L.bcn_api_version(), API_VERSION))
+        _LIB = L
+    return _LIB
 
 
 class BeaconHipError(RuntimeError):

@@ -8,7 +8,7 @@ launches that a caller captures in one graph, and Rollout.compute_gae gets its v
 The library is a unit of its own, like the torch extension: its entry points take no env handle, only device pointers and
 sizes; they are bound here through ctypes in a table of their own (SIGNATURES below -- not _lib.SIGNATURES).  Built in-tree
 with the flags of the main library (build.FLAGS) on first use; the sidecar .sig holds a hash of its sources, the headers they
-include and the flags (_unit.py: the machinery, shared with the learner).  Importing this module touches neither a compiler nor the GPU."""
+include and the flags (build.py: the machinery, shared with every library of the package).  Importing this module touches neither a compiler nor the GPU."""
 import ctypes as C
 import os
 
@@ -16,7 +16,6 @@ import numpy as np
 import torch
 
 from . import build as _build
-from ._unit import Unit as _Unit
 
 API_VERSION = 1                           # include/beacon_actor.h: BCN_ACTOR_API_VERSION
 # per-file flags, as build.FILE_FLAGS.  The float64 unit: one rounding per written operation, for the same reason as rollout.hip
@@ -63,10 +62,9 @@ class BeaconActorError(RuntimeError):
 
 
 # ---- the library -------------------------------------------------------------------------
-# what the units include from outside their directory: the Philox definition (csrc/env1d.h -> bcn_common.h -> beacon_hip.h)
-_UNIT = _Unit("actor", FILE_FLAGS, SIGNATURES, [os.path.join(_build.CSRC, "env1d.h"), os.path.join(_build.CSRC, "bcn_common.h"),
-                                                os.path.join(_build.INC, "beacon_hip.h")])
-SRC_DIR, HEADER, LIB, OBJ = _UNIT.src_dir, _UNIT.header, _UNIT.lib, _UNIT.obj
+SRC_DIR, HEADER = os.path.join(_build.CSRC, "actor"), os.path.join(_build.INC, "beacon_actor.h")
+LIB, OBJ = os.path.join(_build.PKG, "libbeacon_actor.so"), os.path.join(_build.OBJ, "actor")
+_UNIT = _build.hip_library(LIB, SRC_DIR, FILE_FLAGS, OBJ, SIGNATURES)
 sources, signature, stale, load = _UNIT.sources, _UNIT.signature, _UNIT.stale, _UNIT.load
 
 

@@ -1,16 +1,26 @@
-"""In-tree build of libbeacon_hip.so (hand-written HIP for gfx950) with hipcc.
+"""The in-tree build of every library this package ships, stated once: libbeacon_hip.so (hand-written HIP for gfx950, hipcc),
+libbeacon_actor.so and libbeacon_learner.so (actor.py, learner.py), libbeacon_torch.so (torch_ext.py, g++) and the per-grid kernel
+plugins (jit.py).  Each is a `Unit`: its sources, its flags, its commands.  The machinery is Unit's:
 
-The shared object is git-ignored but travels to the GPU box with the snapshot.  Staleness is decided by
-CONTENT, not by mtime (a snapshot or a fresh checkout may reset file times): the library carries a sidecar
-`libbeacon_hip.so.sig` with a hash of every source, header and flag it was built from.  Concurrent builds
-(N ranks of one node importing the package at once) are serialised by a file lock and build into a
-per-process object directory."""
+  what a library depends on   closure(): the quoted #include lines of its sources, followed transitively
+  whether it is current       CONTENT, not mtime (a snapshot or a fresh checkout may reset file times): the sidecar `<lib>.sig` holds
+                              a hash of every file of deps(), the flags and the architecture, taken BEFORE the compiler runs
+  how it is built             under the file lock `<lib>.lock` (N ranks of one node importing the package at once), objects in a
+                              per-process directory under csrc/_obj, four compiles at a time, linked to a temporary name and
+                              os.replace'd; the .sig written and renamed; nothing temporary left, on success or failure
+  the argv of one file        compile_cmd(): the build, the plugins, scripts and tests that look at a unit's assembly
+  BEACON_NO_BUILD=1           no_build()
+
+The shared objects are git-ignored but travel to the GPU box with the snapshot of the tree."""
+import ctypes as C
 import fcntl
 import glob
 import hashlib
 import os
+import re
 import shutil
 import subprocess
+import sys
 from concurrent.futures import ThreadPoolExecutor
 
 PKG = os.path.dirname(os.path.abspath(__file__))
@@ -72,42 +82,75 @@ def hipcc():
     return None
 
 
-def sources():
-    return sorted(glob.glob(os.path.join(CSRC, "*.hip")))
+def no_build():
+    """BEACON_NO_BUILD=1 (exported by the profiling scripts): never spawn a compiler from this process -- under rocprofv3 the
+    children would inherit the profiler's preload (scripts/prof_bench.sh).  Read here only.  What follows from it is the caller's:
+    Unit.load() raises (a stale binary is never dlopen'ed: its structs and signatures may disagree with this source tree),
+    torch_ext.build_ext() and jit.build_plugin() return None."""
+    return os.environ.get("BEACON_NO_BUILD") == "1"
 
 
-def _deps():
-    # (include/beacon_actor.h and beacon_learner.h belong to libbeacon_actor.so and libbeacon_learner.so, units of their own:
-    # beacon_amd/actor.py, beacon_amd/learner.py)
-    return (sources() + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) +
-            [f for f in glob.glob(os.path.join(INC, "*.h")) if os.path.basename(f) not in ("beacon_actor.h", "beacon_learner.h")])
+def compile_cmd(src, out, file_flags=None, defs=None, extra=(), mode=("-c",), cc=None, tables=None):
+    """The argv that compiles one file: FLAGS, the file's own flags, -D `defs`, `extra`, the include directory, `mode` ("-c" for the
+    build; ("--cuda-device-only", "-S") for a look at the assembly; ("-shared",) for a plugin).  `file_flags`: the table basename ->
+    flags the file is looked up in (default FILE_FLAGS), or the list itself.  `tables`: the build module of another checkout, whose
+    FLAGS, FILE_FLAGS, INC and hipcc() are meant (scripts/params_fast_kernels.py compiles two checkouts side by side)."""
+    b = tables or sys.modules[__name__]
+    ff = b.FILE_FLAGS if file_flags is None else file_flags
+    if isinstance(ff, dict):
+        ff = ff.get(os.path.basename(src), [])
+    return ([cc or b.hipcc()] + b.FLAGS + list(ff) + ["-D%s=%s" % kv for kv in sorted((defs or {}).items())] + list(extra) +
+            ["-I", b.INC] + list(mode) + [src, "-o", out])
 
 
-def signature():
-    """Hash of everything the library is built from: sources, headers, flags."""
-    h = hashlib.sha256()
-    h.update(repr((ARCH, FLAGS, sorted(FILE_FLAGS.items()))).encode())
-    for f in sorted(_deps()):
-        h.update(os.path.basename(f).encode())
+_INCLUDE = re.compile(rb"^[ \t]*#[ \t]*include\b[ \t]*(.*)$", re.M)
+
+
+def quoted_includes(path, text):
+    """The names of the `#include "..."` lines of `text`; `#include <...>` is the toolchain's and ignored; anything else after
+    #include (a macro) is an error: the dependency rule could not follow it."""
+    names = []
+    for rest in _INCLUDE.findall(text):
+        m = re.match(rb'"([^"]+)"|<[^>]+>', rest)
+        if m is None:
+            raise RuntimeError("%s: `#include %s` is neither \"...\" nor <...>: the build cannot tell what it depends on"
+                               % (path, rest.decode(errors="replace").strip()))
+        if m.group(1):
+            names.append(m.group(1).decode())
+    return names
+
+
+def closure(sources):
+    """{path: bytes} of `sources` and every file their quoted includes reach, each include looked for beside the includer, then in
+    csrc/, then in include/ (whether or not a preprocessor condition guards it: at least what the compiler reads).  One that
+    resolves nowhere is an error."""
+    seen, todo = {}, [os.path.abspath(s) for s in sources]
+    while todo:
+        f = todo.pop()
+        if f in seen:
+            continue
         with open(f, "rb") as fh:
-            h.update(fh.read())
-    return h.hexdigest()
+            seen[f] = fh.read()
+        for name in quoted_includes(f, seen[f]):
+            for d in (os.path.dirname(f), CSRC, INC):
+                if os.path.isfile(os.path.join(d, name)):
+                    todo.append(os.path.normpath(os.path.join(d, name)))
+                    break
+            else:
+                raise RuntimeError("%s includes \"%s\", which is neither beside it nor in %s nor in %s" % (f, name, CSRC, INC))
+    return seen
 
 
-def stale():
-    if not os.path.exists(LIB) or not os.path.exists(LIB + ".sig"):
-        return True
-    with open(LIB + ".sig") as fh:
-        return fh.read().strip() != signature()
-
-
-def sweep_objdirs():
-    """Remove the per-process object directories of builders that are gone (a build that was killed leaves its
-    csrc/_obj/p<pid> behind, and the directory ships with every snapshot of the tree)."""
-    if not os.path.isdir(OBJ):
+def sweep_objdirs(root=None):
+    """Remove the per-process object directories of builders that are gone (a build that was killed leaves its p<pid> behind,
+    and the directory ships with every snapshot of the tree): csrc/_obj/p<pid> and the units' csrc/_obj/<unit>/p<pid>."""
+    root = root or OBJ
+    if not os.path.isdir(root):
         return
-    for d in os.listdir(OBJ):
+    for d in os.listdir(root):
         if not (d.startswith("p") and d[1:].isdigit()):
+            if os.path.isdir(os.path.join(root, d)):
+                sweep_objdirs(os.path.join(root, d))
             continue
         pid = int(d[1:])
         if pid != os.getpid():
@@ -118,51 +161,134 @@ def sweep_objdirs():
                 pass
             except OSError:
                 continue
-        shutil.rmtree(os.path.join(OBJ, d), ignore_errors=True)
+        shutil.rmtree(os.path.join(root, d), ignore_errors=True)
+
+
+def _run(cmd, verbose):
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+
+
+class Unit(object):
+    """One in-tree library, described as data; deps(), signature(), stale(), build() and load() are stated here once.
+    `lib`: the output; `sources`: () -> its source files; `key`: () -> whatever besides file contents belongs in the hash (flags
+    without absolute paths, a version); `commands`: (cc, tmp, objdir) -> (compile argvs, run four at a time; the argv that
+    writes `tmp`) -- a single-command build has no compile argvs and no `obj`; `compiler`: () -> path or None; `obj`: where the
+    per-process object directory goes; `signatures`: symbol -> (restype, argtypes) for load(); `sig`: False for an output that
+    carries the hash in its name (a plugin) and has no sidecar."""
+
+    def __init__(self, lib, sources, key, commands, compiler=hipcc, obj=None, signatures=None, sig=True):
+        self.lib, self.sources, self.key, self.commands, self.compiler = lib, sources, key, commands, compiler
+        self.obj, self.signatures, self.sig, self._loaded = obj, signatures, sig, None
+
+    def deps(self):
+        return sorted(closure(self.sources()))
+
+    def signature(self):
+        """Hash of everything the library is built from: key(), and name and content of every file of deps().  Independent of
+        where the tree lies."""
+        h = hashlib.sha256()
+        h.update(repr(self.key()).encode())
+        for f, text in sorted(closure(self.sources()).items()):
+            h.update(os.path.basename(f).encode())
+            h.update(text)
+        return h.hexdigest()
+
+    def stale(self):
+        if not self.sig:
+            return not os.path.exists(self.lib)
+        if not os.path.exists(self.lib) or not os.path.exists(self.lib + ".sig"):
+            return True
+        with open(self.lib + ".sig") as fh:
+            return fh.read().strip() != self.signature()
+
+    def build(self, force=False, verbose=False):
+        """Build the library if it is stale (or `force`); returns its path.  The signature is taken before the compiler runs, so
+        a source edited during the build leaves the library stale.  Whatever happens, no temporary file and no object directory
+        stays behind, and the previous library and .sig stay whole until the new ones replace them."""
+        if not force and not self.stale():
+            sweep_objdirs()
+            return self.lib
+        cc = self.compiler()
+        if cc is None:
+            raise RuntimeError("no compiler found: cannot build %s" % os.path.basename(self.lib))
+        os.makedirs(os.path.dirname(self.lib), exist_ok=True)
+        tmp, sigtmp = "%s.tmp%d" % (self.lib, os.getpid()), "%s.sig.tmp%d" % (self.lib, os.getpid())
+        objdir = os.path.join(self.obj, "p%d" % os.getpid()) if self.obj else None
+        with open(self.lib + ".lock", "w") as lock:
+            fcntl.flock(lock, fcntl.LOCK_EX)           # one builder at a time per output (N ranks of one node ask at once)
+            try:
+                if not force and not self.stale():     # another process built it while we waited
+                    return self.lib
+                sig = self.signature()
+                if objdir:
+                    os.makedirs(objdir, exist_ok=True)
+                compiles, link = self.commands(cc, tmp, objdir)
+                with ThreadPoolExecutor(max_workers=4) as ex:       # (never sized by the CPU count: a GPU box lends 16 of many)
+                    list(ex.map(lambda cmd: _run(cmd, verbose), compiles))
+                _run(link, verbose)
+                os.replace(tmp, self.lib)
+                if self.sig:
+                    with open(sigtmp, "w") as fh:
+                        fh.write(sig + "\n")
+                    os.replace(sigtmp, self.lib + ".sig")
+            finally:
+                for f in (tmp, sigtmp):
+                    if os.path.exists(f):
+                        os.remove(f)
+                if objdir:
+                    shutil.rmtree(objdir, ignore_errors=True)
+                sweep_objdirs()
+                fcntl.flock(lock, fcntl.LOCK_UN)
+        return self.lib
+
+    def load(self, signatures=None, mode=C.DEFAULT_MODE, no_compiler=None):
+        """dlopen the library (building it first when stale) and declare every symbol of the table; a missing library or symbol is
+        an error.  `no_compiler`: the error text of a stale library that nothing here can build."""
+        if self._loaded is None:
+            if self.stale():
+                if no_build():
+                    raise RuntimeError("%s is missing or stale and BEACON_NO_BUILD=1: run "
+                                       "`python -c 'import __graft_entry__ as g; g.build()'` first" % os.path.basename(self.lib))
+                if no_compiler and self.compiler() is None:
+                    raise RuntimeError(no_compiler)
+                self.build()
+            L = C.CDLL(self.lib, mode=mode)
+            for name, (res, args) in (signatures or self.signatures).items():
+                fn = getattr(L, name)                  # AttributeError if the library lacks a declared symbol
+                fn.restype = res
+                fn.argtypes = args
+            self._loaded = L
+        return self._loaded
+
+
+def hip_library(lib, src_dir, file_flags, obj, signatures=None):
+    """The Unit of a library of src_dir/*.hip: every file with FLAGS and its entry of `file_flags` (a table, or () -> table),
+    linked by hipcc.  FLAGS and a callable's table are read when they are used, not here: scripts/kstat.py and its kin extend
+    FLAGS, or rebind FILE_FLAGS, and then build."""
+    table = file_flags if callable(file_flags) else (lambda: file_flags)
+
+    def sources():
+        return sorted(glob.glob(os.path.join(src_dir, "*.hip")))
+
+    def commands(cc, tmp, objdir):
+        objs = [os.path.join(objdir, os.path.basename(s)[:-4] + ".o") for s in sources()]
+        return ([compile_cmd(s, o, table(), cc=cc) for s, o in zip(sources(), objs)],
+                [cc, "-shared", "-fPIC", "--offload-arch=" + ARCH, "-o", tmp] + objs)
+
+    return Unit(lib, sources, lambda: (ARCH, FLAGS, sorted(table().items())), commands, obj=obj, signatures=signatures)
+
+
+# libbeacon_hip.so: every csrc/*.hip.  (include/beacon_actor.h and beacon_learner.h belong to libbeacon_actor.so and
+# libbeacon_learner.so, units of their own -- beacon_amd/actor.py, beacon_amd/learner.py; no source of this library includes them)
+MAIN = hip_library(LIB, CSRC, lambda: FILE_FLAGS, OBJ)
+sources, _deps, signature, stale = MAIN.sources, MAIN.deps, MAIN.signature, MAIN.stale
 
 
 def build_lib(force=False, verbose=False):
     """Compile every csrc/*.hip for gfx950 and link libbeacon_hip.so.  Returns its path."""
-    if not force and not stale():
-        sweep_objdirs()
-        return LIB
-    cc = hipcc()
-    if cc is None:
-        raise RuntimeError("hipcc not found: cannot build libbeacon_hip.so")
-    os.makedirs(OBJ, exist_ok=True)
-    with open(os.path.join(OBJ, ".lock"), "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)               # one builder at a time per checkout
-        try:
-            if not force and not stale():              # another process built it while we waited
-                return LIB
-            sig = signature()
-            objdir = os.path.join(OBJ, "p%d" % os.getpid())
-            os.makedirs(objdir, exist_ok=True)
-
-            def one(src):
-                obj = os.path.join(objdir, os.path.basename(src)[:-4] + ".o")
-                cmd = [cc] + FLAGS + FILE_FLAGS.get(os.path.basename(src), []) + ["-I", INC, "-c", src, "-o", obj]
-                if verbose:
-                    print(" ".join(cmd), flush=True)
-                subprocess.check_call(cmd)
-                return obj
-
-            with ThreadPoolExecutor(max_workers=4) as ex:
-                objs = list(ex.map(one, sources()))
-            tmp = "%s.tmp%d" % (LIB, os.getpid())
-            cmd = [cc, "-shared", "-fPIC", "--offload-arch=" + ARCH, "-o", tmp] + objs
-            if verbose:
-                print(" ".join(cmd), flush=True)
-            subprocess.check_call(cmd)
-            os.replace(tmp, LIB)
-            with open(LIB + ".sig.tmp", "w") as fh:
-                fh.write(sig + "\n")
-            os.replace(LIB + ".sig.tmp", LIB + ".sig")
-            shutil.rmtree(objdir, ignore_errors=True)
-            sweep_objdirs()
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
-    return LIB
+    return MAIN.build(force=force, verbose=verbose)
 
 
 if __name__ == "__main__":

@@ -26,7 +26,6 @@ with a table of three distinct parameter sets on both envs (SELF_CHECK_PARAMS), 
 does the plugin; its `.ok` / `.bad` markers are its own."""
 import ctypes as C
 import fcntl
-import hashlib
 import os
 import subprocess
 import warnings
@@ -346,15 +345,11 @@ def selftest_cases():
             for b in builtin_rows()]
 
 
-def _signature(defs):
-    h = hashlib.sha256()
-    h.update(repr((_build.ARCH, _build.FLAGS, _build.JIT_FLAGS, sorted(defs.items()))).encode())
-    for f in sorted([JIT_SRC] + [os.path.join(_build.CSRC, n) for n in os.listdir(_build.CSRC) if n.endswith(".h")] +
-                    [os.path.join(_build.INC, n) for n in os.listdir(_build.INC) if n.endswith(".h")]):
-        h.update(os.path.basename(f).encode())
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-    return h.hexdigest()[:12]
+def _unit(defs):
+    """The build.Unit of the plugin with these -D flags: one hipcc command, named by its hash instead of carrying a .sig."""
+    def commands(cc, tmp, objdir):
+        return [], _build.compile_cmd(JIT_SRC, tmp, _build.JIT_FLAGS, defs, mode=("-shared",), cc=cc)
+    return _build.Unit(None, lambda: [JIT_SRC], lambda: (_build.ARCH, _build.FLAGS, _build.JIT_FLAGS, sorted(defs.items())), commands, sig=False)
 
 
 def build_plugin(nx, ny, f64, kind, verbose=False, extra_defs=None):
@@ -370,40 +365,20 @@ def build_plugin(nx, ny, f64, kind, verbose=False, extra_defs=None):
     for d in os.environ.get("BEACON_JIT_DEFS", "").split():   # experiments: extra -D flags (scripts/tall_base.py)
         defs[d.partition("=")[0]] = d.partition("=")[2] or "1"
     defs.update(extra_defs or {})
-    name = "ns2d_%dx%d_%s_k%d_r%d_%s.so" % (nx, ny, "f64" if f64 else "f32", kind, m["R"], _signature(defs))
-    path = os.path.join(JIT_DIR, name)
-    if os.path.exists(path):
-        return path
-    cc = _build.hipcc()
-    if cc is None or os.environ.get("BEACON_NO_BUILD") == "1":
+    u = _unit(defs)
+    u.lib = os.path.join(JIT_DIR, "ns2d_%dx%d_%s_k%d_r%d_%s.so" % (nx, ny, "f64" if f64 else "f32", kind, m["R"], u.signature()[:12]))
+    if not u.stale():
+        return u.lib
+    if u.compiler() is None or _build.no_build():
         return None
-    tmp = "%s.tmp%d" % (path, os.getpid())
     try:
-        os.makedirs(JIT_DIR, exist_ok=True)
-        with open(path + ".lock", "w") as lock:
-            fcntl.flock(lock, fcntl.LOCK_EX)          # N ranks of one node asking for the same grid (one lock per plugin)
-            try:
-                if os.path.exists(path):
-                    return path
-                cmd = ([cc] + _build.FLAGS + _build.JIT_FLAGS +
-                       ["-D%s=%s" % kv for kv in sorted(defs.items())] + ["-I", _build.INC, "-shared", JIT_SRC, "-o", tmp])
-                if verbose:
-                    print(" ".join(cmd), flush=True)
-                subprocess.check_call(cmd)
-                os.replace(tmp, path)
-            finally:
-                fcntl.flock(lock, fcntl.LOCK_UN)
+        return u.build(verbose=verbose)               # (one lock per plugin: N ranks of one node asking for the same grid)
     except (OSError, subprocess.CalledProcessError) as e:
         # a read-only package directory, a full disk or a compiler error: the env keeps the generic kernel
         # (still on the GPU, only slower) instead of failing in its constructor
         warnings.warn("beacon_amd.jit: no register-resident kernel for %dx%d (%s); the generic kernel stays selected"
                       % (nx, ny, e), JitWarning)
-        try:
-            os.remove(tmp)
-        except OSError:
-            pass
         return None
-    return path
 
 
 class Plugin(object):

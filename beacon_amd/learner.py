@@ -6,7 +6,7 @@ actor.params in place (two launches: the update and the tick of the device-side 
 allocation, no atomics: every buffer is bit-reproducible, and both calls can be captured in a graph.  Learner.update is the
 convenience over a Rollout the actor is attached to.
 
-The library is a unit of its own, built and bound like the actor's (_unit.py); its table is SIGNATURES below.  Importing this
+The library is a unit of its own, built and bound like the actor's (build.py: one Unit each); its table is SIGNATURES below.  Importing this
 module touches neither a compiler nor the GPU."""
 import ctypes as C
 import os
@@ -16,7 +16,6 @@ import torch
 
 from . import actor as _actor
 from . import build as _build
-from ._unit import Unit as _Unit
 
 API_VERSION = 1                           # include/beacon_learner.h: BCN_LEARNER_API_VERSION
 # the float64 unit: one rounding per written operation, as actor_f64.hip
@@ -67,12 +66,11 @@ class BeaconLearnerError(RuntimeError):
 
 
 # ---- the library -------------------------------------------------------------------------
-# what the units include from outside their directory: the network both libraries run (csrc/actor/policy_net.h), the actor's kernel
-# header that brings it, and what that includes
-_UNIT = _Unit("learner", FILE_FLAGS, SIGNATURES, [os.path.join(_actor.SRC_DIR, "policy_net.h"), os.path.join(_actor.SRC_DIR, "actor_impl.h"),
-                                                  _actor.HEADER, os.path.join(_build.CSRC, "env1d.h"), os.path.join(_build.CSRC, "bcn_common.h"),
-                                                  os.path.join(_build.INC, "beacon_hip.h")])
-SRC_DIR, HEADER, LIB, OBJ = _UNIT.src_dir, _UNIT.header, _UNIT.lib, _UNIT.obj
+# (the units include the network both libraries run, csrc/actor/policy_net.h, and the actor's kernel header that brings it: the
+# dependency rule of build.py follows the #include lines there)
+SRC_DIR, HEADER = os.path.join(_build.CSRC, "learner"), os.path.join(_build.INC, "beacon_learner.h")
+LIB, OBJ = os.path.join(_build.PKG, "libbeacon_learner.so"), os.path.join(_build.OBJ, "learner")
+_UNIT = _build.hip_library(LIB, SRC_DIR, FILE_FLAGS, OBJ, SIGNATURES)
 sources, signature, stale, load = _UNIT.sources, _UNIT.signature, _UNIT.stale, _UNIT.load
 
 

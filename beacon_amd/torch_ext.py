@@ -6,10 +6,8 @@ step() when this library is present -- one dispatcher call per step instead of s
 stream query -- and falls back to the ctypes binding of the SAME C ABI when it is not (no g++ / no torch headers): either
 way the arithmetic happens in libbeacon_hip.so, and tests/test_gpu_parity.py steps every env through both bindings bit for bit.
 
-Built in-tree like the library itself (the shared object travels with the snapshot; its sidecar .sig holds a hash of the
-source, the C header, the flags and the torch version)."""
-import fcntl
-import hashlib
+Built in-tree like the library itself, by the same routine (build.py: a Unit of one g++ command); its sidecar .sig holds a hash of
+the source, the C header it includes, the flags and the torch version."""
 import os
 import shutil
 import subprocess
@@ -36,51 +34,30 @@ def _flags():
              "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + tlib])
 
 
-def signature():
+def _key():
     import torch
-    h = hashlib.sha256()
     cf, lf = _flags()
     # (path-independent: the tree is built in one place and used in another -- the flags' directories are left out)
-    h.update(repr(([f for f in cf if not os.path.isabs(f)], [f for f in lf if not os.path.isabs(f) and "rpath" not in f],
-                   torch.__version__)).encode())
-    for f in (SRC, os.path.join(_build.INC, "beacon_hip.h")):
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-    return h.hexdigest()
+    return ([f for f in cf if not os.path.isabs(f)], [f for f in lf if not os.path.isabs(f) and "rpath" not in f], torch.__version__)
 
 
-def stale():
-    if not os.path.exists(LIB) or not os.path.exists(LIB + ".sig"):
-        return True
-    with open(LIB + ".sig") as fh:
-        return fh.read().strip() != signature()
+def _commands(cxx, tmp, objdir):
+    cf, lf = _flags()
+    return [], [cxx] + cf + [SRC, "-o", tmp] + lf
+
+
+_UNIT = _build.Unit(LIB, lambda: [SRC], _key, _commands, compiler=lambda: os.environ.get("CXX") or shutil.which("g++"))
+signature, stale = _UNIT.signature, _UNIT.stale
 
 
 def build_ext(force=False, verbose=False):
     """Compile csrc/torch/beacon_torch.cpp with g++ against the torch headers; returns the path, or None without a compiler."""
     if not force and not stale():
         return LIB
-    cxx = os.environ.get("CXX") or shutil.which("g++")
-    if cxx is None or os.environ.get("BEACON_NO_BUILD") == "1":
+    if _UNIT.compiler() is None or _build.no_build():
         return None
     _build.build_lib()                       # links against libbeacon_hip.so
-    cf, lf = _flags()
-    with open(LIB + ".lock", "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        try:
-            if not force and not stale():
-                return LIB
-            tmp = "%s.tmp%d" % (LIB, os.getpid())
-            cmd = [cxx] + cf + [SRC, "-o", tmp] + lf
-            if verbose:
-                print(" ".join(cmd), flush=True)
-            subprocess.check_call(cmd)
-            os.replace(tmp, LIB)
-            with open(LIB + ".sig", "w") as fh:
-                fh.write(signature() + "\n")
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
-    return LIB
+    return _UNIT.build(force=force, verbose=verbose)
 
 
 def load():

@@ -132,11 +132,19 @@ def resources(root, asm_dir):
     return head + "\n".join(rows) + "\n"
 
 
+ASM = ("--cuda-device-only", "-S")
+
+
+def _compile_cmd(build, src, out, file_flags=None, defs=None):
+    """This tree's build.compile_cmd over the tables (FLAGS, FILE_FLAGS, include directory) of the checkout `build` is of, which
+    may be from before it had the function."""
+    from beacon_amd.build import compile_cmd
+    return compile_cmd(src, out, file_flags, defs, mode=ASM, tables=build)
+
+
 def unit_asm(build, unit, out_path, file_flags=None):
     """`file_flags`: the table of per-file flags when it is not build.FILE_FLAGS (the actor's, the learner's)"""
-    src = os.path.join(build.CSRC, unit)
-    subprocess.check_call([build.hipcc()] + build.FLAGS + (build.FILE_FLAGS if file_flags is None else file_flags).get(os.path.basename(unit), []) +
-                          ["-I", build.INC, "--cuda-device-only", "-S", src, "-o", out_path])
+    subprocess.check_call(_compile_cmd(build, os.path.join(build.CSRC, unit), out_path, file_flags))
     return normalise(open(out_path).read())
 
 
@@ -151,9 +159,7 @@ def plugin_defs(jit_choose, nx, ny, f64, kind, extra=None):
 
 
 def plugin_asm(build, defs, out_path):
-    src = os.path.join(build.CSRC, "jit", "ns2d_jit.hip")
-    subprocess.check_call([build.hipcc()] + build.FLAGS + build.JIT_FLAGS + ["-D%s=%s" % kv for kv in sorted(defs.items())] +
-                          ["-I", build.INC, "--cuda-device-only", "-S", src, "-o", out_path])
+    subprocess.check_call(_compile_cmd(build, os.path.join(build.CSRC, "jit", "ns2d_jit.hip"), out_path, build.JIT_FLAGS, defs))
     return normalise(open(out_path).read())
 
 

@@ -8,8 +8,8 @@ src = sys.argv[1]
 pat = sys.argv[2] if len(sys.argv) > 2 and not sys.argv[2].startswith("-") else ""
 extra = [a for a in sys.argv[2:] if a.startswith("-")]
 path = src if os.path.exists(src) else os.path.join(B.CSRC, src)
-cmd = [B.hipcc()] + B.FLAGS + B.FILE_FLAGS.get(os.path.basename(path), []) + extra + [
-    "-I", B.INC, "-I", B.CSRC, "--cuda-device-only", "--no-gpu-bundle-output", "-Rpass-analysis=kernel-resource-usage", "-c", path, "-o", "/tmp/resusage.o"]
+cmd = B.compile_cmd(path, "/tmp/resusage.o", extra=extra,
+                    mode=("-I", B.CSRC, "--cuda-device-only", "--no-gpu-bundle-output", "-Rpass-analysis=kernel-resource-usage", "-c"))
 r = subprocess.run(cmd, capture_output=True, text=True)
 if r.returncode:
     print(r.stderr[-4000:]); sys.exit(1)

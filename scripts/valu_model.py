@@ -14,8 +14,7 @@ KERNEL = "ns2d_fast_schedIfLi128ELi64ELi16ELi0ELb1ELi0EE"
 def main():
     out = sys.argv[1] if len(sys.argv) > 1 else None
     asm = "/tmp/valu_model_ns2d_fast.s"
-    subprocess.check_call([B.hipcc()] + B.FLAGS + B.FILE_FLAGS.get("ns2d_fast_runs.hip", []) +
-                          ["-I", B.INC, "--cuda-device-only", "-S", os.path.join(B.CSRC, "ns2d_fast_runs.hip"), "-o", asm])
+    subprocess.check_call(B.compile_cmd(os.path.join(B.CSRC, "ns2d_fast_runs.hip"), asm, mode=("--cuda-device-only", "-S")))
     s = open(asm).read()
     m = re.search(r'^(_Z\w*%s\w*):[^\n]*\n(.*?)\n\.Lfunc_end' % KERNEL, s, re.S | re.M)
     lines = [l.strip() for l in m.group(2).split("\n")]

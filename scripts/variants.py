@@ -15,8 +15,7 @@ HOT = ("ns2d_fast.hip", "ns2d_fast_f64.hip", "ns2d_fast2.hip")
 
 
 def compile_one(src, extra, out):
-    cmd = [B.hipcc()] + B.FLAGS + B.FILE_FLAGS.get(os.path.basename(src), []) + extra + ["-I", B.INC, "-c", src, "-o", out]
-    subprocess.check_call(cmd)
+    subprocess.check_call(B.compile_cmd(src, out, extra=extra))
 
 
 def build(specs):

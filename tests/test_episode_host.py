@@ -84,8 +84,7 @@ def test_bookkeeping_kernel_compiles_for_gfx950_without_scratch_or_atomics(tmp_p
     src = os.path.join(build.CSRC, "episode.hip")
     assert src in build.sources()
     asm = str(tmp_path / "episode.s")
-    subprocess.check_call([cc] + build.FLAGS + build.FILE_FLAGS.get("episode.hip", []) +
-                          ["-I", build.INC, "--cuda-device-only", "-S", src, "-o", asm])
+    subprocess.check_call(build.compile_cmd(src, asm, mode=("--cuda-device-only", "-S")))
     text = open(asm).read()
     kernels = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", text, flags=re.M)
     assert len(kernels) == 1 and "episode_track_k" in kernels[0], kernels

@@ -231,8 +231,8 @@ def test_removing_the_chain_pad_is_flagged_in_transport_chain_f32(tmp_path):
 
     def compile_and_scan(tag, extra):
         obj = str(tmp_path / (tag + ".co"))
-        subprocess.check_call([cc] + build.FLAGS + build.JIT_FLAGS + ["-D%s=%s" % kv for kv in sorted(defs.items())] + extra +
-                              ["-I", build.INC, "--offload-device-only", "--no-gpu-bundle-output", "-c", jit.JIT_SRC, "-o", obj])
+        subprocess.check_call(build.compile_cmd(jit.JIT_SRC, obj, build.JIT_FLAGS, defs, extra,
+                                                mode=("--offload-device-only", "--no-gpu-bundle-output", "-c")))
         return H.scan_file(obj, tool)
 
     with ThreadPoolExecutor(max_workers=2) as ex:

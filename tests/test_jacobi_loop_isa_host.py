@@ -32,8 +32,7 @@ def loops(tmp_path_factory):
     if cc is None:
         pytest.skip("no hipcc: nothing to compile with")
     asm = str(tmp_path_factory.mktemp("jacobi_loop") / "ns2d_fast.s")
-    subprocess.check_call([cc] + B.FLAGS + B.FILE_FLAGS.get("ns2d_fast_runs.hip", []) +
-                          ["-I", B.INC, "--cuda-device-only", "-S", os.path.join(B.CSRC, "ns2d_fast_runs.hip"), "-o", asm])
+    subprocess.check_call(B.compile_cmd(os.path.join(B.CSRC, "ns2d_fast_runs.hip"), asm, mode=("--cuda-device-only", "-S")))
     with open(asm) as fh:
         s = fh.read()
     m = re.search(r'^(_Z\w*%s\w*):[^\n]*\n(.*?)\n\.Lfunc_end' % KERNEL, s, re.S | re.M)

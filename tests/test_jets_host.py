@@ -108,8 +108,7 @@ def test_jets_kernel_compiles_for_gfx950_without_scratch_or_lds(tmp_path):
     src = os.path.join(build.CSRC, "shkadov_jets.hip")
     assert src in build.sources()
     asm = str(tmp_path / "shkadov_jets.s")
-    subprocess.check_call([cc] + build.FLAGS + build.FILE_FLAGS.get("shkadov_jets.hip", []) +
-                          ["-I", build.INC, "--cuda-device-only", "-S", src, "-o", asm])
+    subprocess.check_call(build.compile_cmd(src, asm, mode=("--cuda-device-only", "-S")))
     text = open(asm).read()
     kernels = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", text, flags=re.M)
     assert len(kernels) == 2 and all("shkadov_jets_k" in k for k in kernels), kernels

@@ -143,8 +143,7 @@ def test_normalize_kernels_compile_for_gfx950_without_scratch(tmp_path):
     src = os.path.join(build.CSRC, "normalize.hip")
     assert src in build.sources()
     asm = str(tmp_path / "normalize.s")
-    subprocess.check_call([cc] + build.FLAGS + build.FILE_FLAGS.get("normalize.hip", []) +
-                          ["-I", build.INC, "--cuda-device-only", "-S", src, "-o", asm])
+    subprocess.check_call(build.compile_cmd(src, asm, mode=("--cuda-device-only", "-S")))
     text = open(asm).read()
     kernels = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", text, flags=re.M)
     assert len(kernels) == 2 and sorted(re.search(r"normalize_(\w+?)_k", k).group(1) for k in kernels) == ["apply", "stats"], kernels

@@ -136,7 +136,7 @@ def test_no_1d_or_ode_kernel_gained_a_private_segment(unit, tmp_path):
     parent = json.load(open(os.path.join(GOLD, "params_parent_private_segments.json")))[unit]
     src = os.path.join(build.CSRC, unit)
     asm = str(tmp_path / (unit + ".s"))
-    subprocess.check_call([cc] + build.FLAGS + build.FILE_FLAGS.get(unit, []) + ["-I", build.INC, "--cuda-device-only", "-S", src, "-o", asm])
+    subprocess.check_call(build.compile_cmd(src, asm, mode=("--cuda-device-only", "-S")))
     text = open(asm).read()
     now = _kernel_meta(text)
     assert set(now) == set(parent), set(now) ^ set(parent)

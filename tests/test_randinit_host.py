@@ -115,7 +115,7 @@ def test_the_new_units_compile_for_gfx950_and_hold_only_warm_kernels(unit, tmp_p
     assert build.FILE_FLAGS.get("shkadov_warm_f64.hip") == build.FILE_FLAGS["env1d_f64.hip"] == ["-ffp-contract=off"]
     assert "shkadov_warm_f32.hip" not in build.FILE_FLAGS and "env1d_f32.hip" not in build.FILE_FLAGS
     asm = str(tmp_path / (unit + ".s"))
-    subprocess.check_call([cc] + build.FLAGS + build.FILE_FLAGS.get(unit, []) + ["-I", build.INC, "--cuda-device-only", "-S", src, "-o", asm])
+    subprocess.check_call(build.compile_cmd(src, asm, mode=("--cuda-device-only", "-S")))
     text = open(asm).read()
     kernels = _kernels(text)
     real = "f" if unit.endswith("f32.hip") else "d"

@@ -118,8 +118,7 @@ def test_copy_kernels_compile_for_gfx950_with_16_byte_accesses(tmp_path):
     src = os.path.join(build.CSRC, "snapshot.hip")
     assert src in build.sources()
     asm = str(tmp_path / "snapshot.s")
-    subprocess.check_call([cc] + build.FLAGS + build.FILE_FLAGS.get("snapshot.hip", []) +
-                          ["-I", build.INC, "--cuda-device-only", "-S", src, "-o", asm])
+    subprocess.check_call(build.compile_cmd(src, asm, mode=("--cuda-device-only", "-S")))
     text = open(asm).read()
     kernels = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", text, flags=re.M)
     assert len(kernels) == 2 and all("snapshot_copy_k" in k for k in kernels), kernels
