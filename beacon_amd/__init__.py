@@ -13,6 +13,9 @@ stream, log-probability and value in ONE launch (actor.act() -> actions; libbeac
 The PPO update of that actor on the device:  Learner(actor, lr=3e-4) -- the clipped-surrogate loss, its gradient with respect to every
 parameter and Adam on actor.params in place, five launches per minibatch (learner.update(ro, adv, ret); libbeacon_learner.so,
 include/beacon_learner.h)
+A whole update without the host:  learner.plan(ro, epochs=10, minibatches=4, seed=7) -> Plan -- the minibatch shuffle from the project's
+Philox stream, the advantage standardisation in float64, a KL early stop and a learning-rate schedule decided on the device;
+plan.run(adv, ret), or plan.capture(adv, ret) for ONE graph (libbeacon_epochs.so, include/beacon_epochs.h)
 Multi-agent shkadov under one shared policy:  Actor(env, per_jet=True) -- every (replica, jet) a row of that actor and that update
 
 Importing the package does not touch the GPU; constructing an env does, and raises if the HIP
@@ -20,6 +23,7 @@ library or a ROCm device is missing (there is no CPU fallback for the solver pat
 from .vec import Box, Discrete, EpisodeStats, JetStats, Normalizer, Rollout, RolloutOverflow, Snapshot, VecBurgers, VecEnv, VecLorenz, VecMixing, VecRayleigh, VecShkadov, VecSloshing, VecVortex  # noqa: F401
 from .actor import Actor  # noqa: F401
 from .learner import Learner  # noqa: F401
+from .epochs import Plan  # noqa: F401
 from .lorenz import lorenz  # noqa: F401
 from .vortex import vortex  # noqa: F401
 

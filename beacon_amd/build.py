@@ -1,5 +1,5 @@
 """The in-tree build of every library this package ships, stated once: libbeacon_hip.so (hand-written HIP for gfx950, hipcc),
-libbeacon_actor.so and libbeacon_learner.so (actor.py, learner.py), libbeacon_torch.so (torch_ext.py, g++) and the per-grid kernel
+libbeacon_actor.so, libbeacon_learner.so and libbeacon_epochs.so (actor.py, learner.py, epochs.py), libbeacon_torch.so (torch_ext.py, g++) and the per-grid kernel
 plugins (jit.py).  Each is a `Unit`: its sources, its flags, its commands.  The machinery is Unit's:
 
   what a library depends on   closure(): the quoted #include lines of its sources, followed transitively

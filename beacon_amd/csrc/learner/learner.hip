@@ -166,6 +166,7 @@ static int learner_step_t(const bcn_actor_cfg* c, void* params, const void* grad
   a.stats = reinterpret_cast<const double*>(static_cast<const char*>(work) + s[0].offset);
   a.n_elems = (int)learner_n_elems(c);
   a.lr = h->lr; a.beta1 = h->beta1; a.beta2 = h->beta2; a.eps = h->eps; a.max_grad_norm = h->max_grad_norm;
+  a.target_kl = h->target_kl; a.lr_end = h->lr_end; a.lr_steps = h->lr_steps;
   const int e = learner_launch_step<real>(a, step, stream);
   if (e) { g_learner_err.set("bcn_learner_step: launch -> %s", hipGetErrorString((hipError_t)e)); return BCN_LEARNER_ERR_HIP; }
   return BCN_LEARNER_OK;
@@ -219,6 +220,9 @@ BCN_LEARNER_API int bcn_learner_step(const bcn_actor_cfg* cfg, void* params_dev,
   LEARNER_NEED(opt_dev, "bcn_learner_step", "opt_dev")
   LEARNER_NEED(work_dev, "bcn_learner_step", "work_dev")
   LEARNER_NEED(adam, "bcn_learner_step", "adam")
+  if (!(adam->target_kl - adam->target_kl == 0.0)) { g_learner_err.set("bcn_learner_step: adam.target_kl = %g: must be finite (<= 0: no stop rule)", adam->target_kl); return BCN_LEARNER_ERR_ARG; }
+  if (!(adam->lr_end - adam->lr_end == 0.0)) { g_learner_err.set("bcn_learner_step: adam.lr_end = %g: must be finite", adam->lr_end); return BCN_LEARNER_ERR_ARG; }
+  if (!(adam->lr_steps - adam->lr_steps == 0.0)) { g_learner_err.set("bcn_learner_step: adam.lr_steps = %g: must be finite (<= 0: no schedule)", adam->lr_steps); return BCN_LEARNER_ERR_ARG; }
   if (!(adam->beta1 >= 0.0 && adam->beta1 < 1.0)) { g_learner_err.set("bcn_learner_step: adam.beta1 = %g: must lie in [0, 1)", adam->beta1); return BCN_LEARNER_ERR_ARG; }
   if (!(adam->beta2 >= 0.0 && adam->beta2 < 1.0)) { g_learner_err.set("bcn_learner_step: adam.beta2 = %g: must lie in [0, 1)", adam->beta2); return BCN_LEARNER_ERR_ARG; }
   return cfg->dtype ? learner_step_t<double>(cfg, params_dev, grad_dev, opt_dev, work_dev, adam, stream)

@@ -67,7 +67,14 @@ struct LearnerAdamArgs {
   const double* stats;
   int n_elems;
   double lr, beta1, beta2, eps, max_grad_norm;
+  double target_kl, lr_end, lr_steps;       // appended (bcn_learner_adam): all 0 is the update without a stop rule and without a schedule
 };
+
+// the KL stop rule of include/beacon_learner.h, the same for every Adam lane and for the tick: nothing writes these words during the
+// Adam launch.  A NaN approx_kl does not stop (the comparison is false).  Only called with target_kl > 0.
+__device__ __forceinline__ bool learner_kl_stop(const int32_t* step, const double* stats, double target_kl) {
+  return step[2] != 0 || stats[BCN_LEARNER_STAT_KL] > 1.5 * target_kl;
+}
 
 // dW[o][k0 + k] (+)= sum_r D[o][r] X[k][r] for o < OUT, k < ks, r ascending over the tile; with k0 = 0 also db[o] (+)= sum_r D[o][r].
 // D, X: LDS, row stride TBP, complete (the caller synchronised).  gW: the workgroup's slab at the matrix [OUT][K], gB at the bias.
@@ -396,6 +403,7 @@ template <typename real>
 __global__ __launch_bounds__(LEARNER_NT) void learner_adam_kernel(const LearnerAdamArgs<real> A) {
   const int p = blockIdx.x * LEARNER_NT + threadIdx.x;
   if (p >= A.n_elems) return;
+  if (A.target_kl > 0.0 && learner_kl_stop(A.step, A.stats, A.target_kl)) return;      // params, m and v stay as they are
   const double norm = A.stats[BCN_LEARNER_STAT_GRAD_NORM];
   double scale = 1.0;
   if (A.max_grad_norm > 0.0) {
@@ -403,7 +411,12 @@ __global__ __launch_bounds__(LEARNER_NT) void learner_adam_kernel(const LearnerA
     scale = scale < 1.0 ? scale : 1.0;
   }
   const double t = (double)(A.step[0] + 1);
-  const real step_size = (real)(A.lr / (1.0 - pow(A.beta1, t)));
+  double lr = A.lr;
+  if (A.lr_steps > 0.0) {                             // linear from lr to lr_end over lr_steps steps TAKEN, then lr_end
+    const double done = (double)A.step[0];
+    lr = A.lr + (A.lr_end - A.lr) * (done < A.lr_steps ? done : A.lr_steps) / A.lr_steps;
+  }
+  const real step_size = (real)(lr / (1.0 - pow(A.beta1, t)));
   const real bc2_sqrt = (real)sqrt(1.0 - pow(A.beta2, t));
   const real g = A.grad[p] * (real)scale;
   real m = A.m[p], v = A.v[p];
@@ -415,9 +428,18 @@ __global__ __launch_bounds__(LEARNER_NT) void learner_adam_kernel(const LearnerA
   A.params[p] = A.params[p] - step_size * (m / denom);
 }
 
+// the step is counted, or -- under the stop rule -- the flag is set and the skipped step counted; target_kl <= 0: step[1 .. 3] are
+// neither read nor written
 template <typename real>
-__global__ void learner_tick_kernel(int32_t* step) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) step[0] = step[0] + 1;
+__global__ void learner_tick_kernel(int32_t* step, const double* stats, double target_kl) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    if (target_kl > 0.0 && learner_kl_stop(step, stats, target_kl)) {
+      step[2] = 1;
+      step[3] = step[3] + 1;
+    } else {
+      step[0] = step[0] + 1;
+    }
+  }
 }
 
 // bytes of dynamic LDS of one workgroup of the backward launch
@@ -453,6 +475,6 @@ template <typename real> int learner_launch_step(const LearnerAdamArgs<real>& a,
     hipLaunchKernelGGL(learner_adam_kernel<real>, dim3((a.n_elems + LEARNER_NT - 1) / LEARNER_NT), dim3(LEARNER_NT), 0, s, a); \
     const hipError_t e = hipGetLastError();                                                                            \
     if (e != hipSuccess) return (int)e;                                                                                \
-    hipLaunchKernelGGL(learner_tick_kernel<real>, dim3(1), dim3(64), 0, s, step);                                      \
+    hipLaunchKernelGGL(learner_tick_kernel<real>, dim3(1), dim3(64), 0, s, step, a.stats, a.target_kl);                \
     return (int)hipGetLastError();                                                                                     \
   }

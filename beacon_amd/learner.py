@@ -42,7 +42,8 @@ class LearnerLoss(C.Structure):
 
 class LearnerAdam(C.Structure):
     """bcn_learner_adam"""
-    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("max_grad_norm", C.c_double)]
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("max_grad_norm", C.c_double),
+                ("target_kl", C.c_double), ("lr_end", C.c_double), ("lr_steps", C.c_double)]     # appended: the KL stop rule and the lr schedule, 0 means none
 
 
 _cfgp, _segp = C.POINTER(_actor.ActorCfg), C.POINTER(_actor.ActorSeg)
@@ -126,20 +127,29 @@ class Learner(object):
 
     Owns `grad` (one uint8 buffer in the layout of the actor's parameters; `grads` maps the segment names to typed views shaped as
     actor.weights), `opt` (the Adam moments `m`, `v` as flat views over the whole parameter buffer and `step_count`, int32 [4]:
-    [0] the steps taken, advanced on the device) and `work` (the slabs; `stats`: float64 [8] on the device -- loss, pg loss,
-    value loss, entropy, approx_kl, clip_frac, W, the gradient norm before clipping -- read by stats_dict(), the only host read).
-    The hyperparameters are plain attributes (lr, clip_range, vf_coef, ent_coef, max_grad_norm, betas, eps): they are ARGUMENTS of
-    the launches, so a captured graph keeps what it was recorded with.  max_grad_norm <= 0 or None: no clipping.
+    [0] the steps taken, advanced on the device, [1] the permutations a plan has drawn, [2] the KL stop flag, [3] the steps it
+    skipped) and `work` (the slabs; `stats`: float64 [8] on the device -- loss, pg loss, value loss, entropy, approx_kl, clip_frac,
+    W, the gradient norm before clipping -- read by stats_dict(), the only host read).
+    The hyperparameters are plain attributes (lr, clip_range, vf_coef, ent_coef, max_grad_norm, betas, eps, target_kl, lr_end,
+    lr_steps): they are ARGUMENTS of the launches, so a captured graph keeps what it was recorded with.  max_grad_norm <= 0 or
+    None: no clipping.
     A per-jet actor (Actor(env, per_jet=True)) is updated the same way: update() then takes adv / ret of
     ro.compute_gae(..., per_jet=True), every (step, replica, jet) is a row and the rollout's per-replica `valid` bytes weigh all
     jets of their replica (grad's rows_per_weight).
-    Not covered: ShardedVecEnv (no gradient all-reduce), learning-rate schedules, value clipping."""
+    Two hyperparameters are decided ON THE DEVICE and so keep working when a captured update is replayed (include/beacon_learner.h):
+    target_kl (None or 0: off) -- step() applies no minibatch whose approx_kl exceeds 1.5 target_kl and none behind it until the
+    next plan.run() clears the flag (step_count[2]; `skipped` reads step_count[3], the steps not taken); lr_steps > 0 -- the rate
+    goes linearly from lr to lr_end over lr_steps steps taken, read from step_count[0].
+    learner.plan(ro, epochs, minibatches) is the update as a chain of the library's own launches (beacon_amd/epochs.py).
+    Not covered: ShardedVecEnv (no gradient all-reduce), value clipping."""
 
-    def __init__(self, actor, lr=3e-4, clip_range=0.2, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5, betas=(0.9, 0.999), eps=1e-8):
+    def __init__(self, actor, lr=3e-4, clip_range=0.2, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5, betas=(0.9, 0.999), eps=1e-8,
+                 target_kl=None, lr_end=0.0, lr_steps=0):
         if not isinstance(actor, _actor.Actor):
             raise ValueError("Learner: actor must be a beacon_amd.Actor, got %r" % (type(actor).__name__,))
         self.actor = actor
-        self.set_hyper(lr=lr, clip_range=clip_range, vf_coef=vf_coef, ent_coef=ent_coef, max_grad_norm=max_grad_norm, betas=betas, eps=eps)
+        self.set_hyper(lr=lr, clip_range=clip_range, vf_coef=vf_coef, ent_coef=ent_coef, max_grad_norm=max_grad_norm, betas=betas, eps=eps,
+                       target_kl=target_kl, lr_end=lr_end, lr_steps=lr_steps)
         self.cfg, self.tdtype, self.device = actor.cfg, actor.tdtype, actor.device
         self.lib = load()
         self.grad_layout, nbytes = layout("grad", self.cfg)
@@ -171,6 +181,10 @@ class Learner(object):
                 new[k] = _number("eps", x, lo=0.0)
             elif k == "max_grad_norm":
                 new[k] = 0.0 if x is None else _number("max_grad_norm", x)
+            elif k == "target_kl":
+                new[k] = 0.0 if x is None else _number("target_kl", x, lo=0.0)
+            elif k in ("lr_end", "lr_steps"):
+                new[k] = _number(k, x, lo=0.0)
             elif k == "betas":
                 try:
                     b1, b2 = x
@@ -246,10 +260,12 @@ class Learner(object):
 
     def step(self):
         """One Adam step on actor.params IN PLACE from the gradient of the last grad(), clipped to max_grad_norm: TWO launches on the
-        current stream, no host synchronisation.  The step counter advances on the device."""
+        current stream, no host synchronisation.  The step counter advances on the device.  Under target_kl the step may be
+        skipped there, and with lr_steps its rate comes from the counter (the class docstring)."""
         stream = self._stream()
         p = _actor._ptr
-        h = LearnerAdam(lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, max_grad_norm=self.max_grad_norm)
+        h = LearnerAdam(lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, max_grad_norm=self.max_grad_norm,
+                        target_kl=self.target_kl, lr_end=self.lr_end, lr_steps=self.lr_steps)
         _check(self.lib.bcn_learner_step(C.byref(self.cfg), p(self.actor.params), p(self.grad_buf), p(self.opt), p(self.work), C.byref(h), stream))
         return self
 
@@ -310,18 +326,32 @@ class Learner(object):
                 self.step()
         return self
 
+    def plan(self, ro, epochs=10, minibatches=4, seed=None, normalize_adv=True):
+        """The update over `ro` as a chain of the library's own launches, allocated once: an epochs.Plan (plan.run(adv, ret),
+        plan.capture(adv, ret)).  update() stays what it is."""
+        from . import epochs as _epochs
+        return _epochs.Plan(self, ro, epochs=epochs, minibatches=minibatches, seed=seed, normalize_adv=normalize_adv)
+
+    @property
+    def skipped(self):
+        """The steps the KL stop rule has skipped so far (step_count[3]): a host read."""
+        return int(self.step_count[3])
+
     # -- checkpoints ------------------------------------------------------------------------
     def state_dict(self):
         """For checkpoints: the optimiser buffer on the CPU, what it was laid out for, and the hyperparameters."""
         return {"opt": self.opt.cpu(), "params_bytes": int(self.actor.params.numel()), "dtype": "f64" if self.tdtype == torch.float64 else "f32",
                 "lr": self.lr, "clip_range": self.clip_range, "vf_coef": self.vf_coef, "ent_coef": self.ent_coef,
-                "max_grad_norm": self.max_grad_norm, "betas": tuple(self.betas), "eps": self.eps}
+                "max_grad_norm": self.max_grad_norm, "betas": tuple(self.betas), "eps": self.eps,
+                "target_kl": self.target_kl, "lr_end": self.lr_end, "lr_steps": self.lr_steps}
 
     def load_state_dict(self, d):
         dt = "f64" if self.tdtype == torch.float64 else "f32"
         if d["params_bytes"] != self.actor.params.numel() or d["dtype"] != dt or d["opt"].numel() != self.opt.numel():
             raise ValueError("Learner.load_state_dict: the state is of another learner (%d parameter bytes, %s); this one has %d, %s"
                              % (d["params_bytes"], d["dtype"], self.actor.params.numel(), dt))
-        self.set_hyper(**{k: d[k] for k in ("lr", "clip_range", "vf_coef", "ent_coef", "max_grad_norm", "betas", "eps")})
+        # (a state written before there were a stop rule and a schedule has neither)
+        self.set_hyper(**{k: d[k] for k in ("lr", "clip_range", "vf_coef", "ent_coef", "max_grad_norm", "betas", "eps")},
+                       **{k: d.get(k, 0.0) for k in ("target_kl", "lr_end", "lr_steps")})
         self.opt.copy_(d["opt"])
         return self

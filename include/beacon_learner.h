@@ -77,6 +77,21 @@
  * The gradient buffer keeps the unclipped gradient.  The step counter lives in the optimiser buffer and advances ON THE DEVICE:
  * a captured step keeps counting at replay.  lr, the betas, eps and max_grad_norm are arguments of the launch: a captured graph
  * keeps the values it was recorded with.
+ *
+ * ---- The KL stop rule and the learning-rate schedule (fields appended to bcn_learner_adam) -----------------------------------
+ * Both are decided ON THE DEVICE, from words the launches before left, so they keep working when a captured update is replayed.
+ * The optimiser buffer's step segment, int32 [4], holds: [0] the Adam steps taken, [1] the permutations drawn (the epoch word of
+ * bcn_epochs_permute, include/beacon_epochs.h), [2] the stop flag, [3] the steps the stop rule skipped.
+ * target_kl > 0: with P = (step[2] != 0) || (stats[approx_kl] > 1.5 target_kl) -- evaluated by every Adam lane and by the tick from
+ *   the same words, which nothing writes during the Adam launch --
+ *     P true:   Adam touches neither params nor m nor v; the tick sets step[2] = 1 and step[3] += 1 and leaves step[0] alone
+ *     P false:  the step above; step[0] += 1
+ *   A NaN approx_kl does not stop (the comparison is false).  This is the target_kl rule of the common PPO implementations: the
+ *   minibatch whose approx_kl exceeds 1.5 times the target is not applied, and neither is any later one of the update -- their
+ *   bcn_learner_grad launches still run, there being no host decision, and move nothing.  bcn_epochs_begin clears the flag at the
+ *   head of the next update.  target_kl <= 0: step[2] and step[3] are neither read nor written.
+ * lr_steps > 0: the step uses lr_t = lr + (lr_end - lr) min(step[0], lr_steps) / lr_steps, in float64 from the device counter: a
+ *   skipped step does not advance it, and behind lr_steps steps the rate is lr_end.  lr_steps <= 0: lr.
  */
 #ifndef BEACON_LEARNER_H
 #define BEACON_LEARNER_H
@@ -126,6 +141,10 @@ typedef struct {
 typedef struct {
   double lr, beta1, beta2, eps;   /* betas in [0, 1) */
   double max_grad_norm;           /* <= 0: no clipping */
+  /* APPENDED (an adam that ends at max_grad_norm, zero-filled behind it, means what it meant): the stop rule and the schedule above.
+   * All three finite.  With all three 0 nothing new is read or written and the step is the one of version 1, bit for bit. */
+  double target_kl;               /* > 0: the KL stop rule; <= 0: none, step[2] and step[3] are neither read nor written */
+  double lr_end, lr_steps;        /* lr_steps > 0: the learning rate goes linearly from lr to lr_end over lr_steps steps taken */
 } bcn_learner_adam;
 
 /* The gradient buffer: the segments of bcn_actor_params_layout, name for name and offset for offset. */
@@ -134,7 +153,7 @@ BCN_LEARNER_API size_t bcn_learner_grad_bytes(const bcn_actor_cfg* cfg);
 
 /* The optimiser buffer, three segments (planes = 0):
  *   m, v   real [bcn_learner_grad_bytes / sizeof(real)]: the moments, element for element as the parameter buffer
- *   step   int32 [4]: [0] the Adam steps taken
+ *   step   int32 [4]: [0] the Adam steps taken, [1] the permutations drawn, [2] the KL stop flag, [3] the steps it skipped (above)
  * A zeroed buffer is a fresh optimiser. */
 BCN_LEARNER_API int bcn_learner_opt_layout(const bcn_actor_cfg* cfg, bcn_actor_seg* segs, int max_segs);
 BCN_LEARNER_API size_t bcn_learner_opt_bytes(const bcn_actor_cfg* cfg);
