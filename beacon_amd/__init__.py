@@ -16,6 +16,9 @@ include/beacon_learner.h)
 A whole update without the host:  learner.plan(ro, epochs=10, minibatches=4, seed=7) -> Plan -- the minibatch shuffle from the project's
 Philox stream, the advantage standardisation in float64, a KL early stop and a learning-rate schedule decided on the device;
 plan.run(adv, ret), or plan.capture(adv, ret) for ONE graph (libbeacon_epochs.so, include/beacon_epochs.h)
+Off-policy learning on the device:  TD3(env, hidden=(64, 64)) / TD3.ddpg(env) -- a deterministic policy, one or two critics, their targets
+and two Adam optimisers; agent.replay(capacity) -> Replay, a ring of transitions that Rollouts are appended to; agent.act(mode=...),
+mem.append(ro), agent.update(mem, n_updates, batch_size) or agent.plan(...).capture() for ONE graph (libbeacon_td3.so, include/beacon_td3.h)
 Multi-agent shkadov under one shared policy:  Actor(env, per_jet=True) -- every (replica, jet) a row of that actor and that update
 
 Importing the package does not touch the GPU; constructing an env does, and raises if the HIP
@@ -24,6 +27,7 @@ from .vec import Box, Discrete, EpisodeStats, JetStats, Normalizer, Rollout, Rol
 from .actor import Actor  # noqa: F401
 from .learner import Learner  # noqa: F401
 from .epochs import Plan  # noqa: F401
+from .td3 import TD3, Replay  # noqa: F401
 from .lorenz import lorenz  # noqa: F401
 from .vortex import vortex  # noqa: F401
 
