@@ -19,6 +19,9 @@ plan.run(adv, ret), or plan.capture(adv, ret) for ONE graph (libbeacon_epochs.so
 Off-policy learning on the device:  TD3(env, hidden=(64, 64)) / TD3.ddpg(env) -- a deterministic policy, one or two critics, their targets
 and two Adam optimisers; agent.replay(capacity) -> Replay, a ring of transitions that Rollouts are appended to; agent.act(mode=...),
 mem.append(ro), agent.update(mem, n_updates, batch_size) or agent.plan(...).capture() for ONE graph (libbeacon_td3.so, include/beacon_td3.h)
+Soft actor-critic over the same Replay:  SAC(env, hidden=(64, 64), alpha=1.0, auto_alpha=True) -- a tanh-squashed Gaussian policy with a
+state-dependent log-std, one or two critics, their targets and a learned temperature; agent.act(mode="sample" | "deterministic" |
+"uniform"), agent.update(mem, n_updates, batch_size) or agent.plan(...).capture() for ONE graph (libbeacon_sac.so, include/beacon_sac.h)
 Multi-agent shkadov under one shared policy:  Actor(env, per_jet=True) -- every (replica, jet) a row of that actor and that update
 
 Importing the package does not touch the GPU; constructing an env does, and raises if the HIP
@@ -28,6 +31,7 @@ from .actor import Actor  # noqa: F401
 from .learner import Learner  # noqa: F401
 from .epochs import Plan  # noqa: F401
 from .td3 import TD3, Replay  # noqa: F401
+from .sac import SAC  # noqa: F401
 from .lorenz import lorenz  # noqa: F401
 from .vortex import vortex  # noqa: F401
 

@@ -166,12 +166,15 @@ class Replay(object):
     Not covered: compaction (a row with live = 0 occupies a slot and weighs nothing), prioritised sampling, n-step returns."""
 
     def __init__(self, agent, capacity):
-        if not isinstance(agent, TD3):
+        from . import sac as _sac            # (here, not at the top: sac imports this module)
+        if not isinstance(agent, (TD3, _sac.SAC)):
             raise ValueError("Replay: agent must be a beacon_amd.TD3, got %r" % (type(agent).__name__,))
         if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or not 1 <= int(capacity) < 1 << 31:
             raise ValueError("Replay: capacity must be an integer in 1 .. 2^31 - 1, got %r" % (capacity,))
         self.agent, self.capacity = agent, int(capacity)
-        self.cfg, self.tdtype, self.device, self.lib = agent.cfg, agent.tdtype, agent.device, agent.lib
+        # a SAC agent's memory is this library's too: its replay_cfg is a bcn_td3_cfg of the same batch, dims, dtype and widths
+        self.cfg, self.lib = (agent.cfg, agent.lib) if isinstance(agent, TD3) else (agent.replay_cfg, load())
+        self.tdtype, self.device = agent.tdtype, agent.device
         self.layout, nbytes = layout("replay", self.cfg, self.capacity)
         self.buf = torch.zeros((nbytes,), dtype=torch.uint8, device=self.device)
         v = _views(self.buf, self.layout, self.tdtype)
