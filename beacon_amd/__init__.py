@@ -22,6 +22,10 @@ mem.append(ro), agent.update(mem, n_updates, batch_size) or agent.plan(...).capt
 Soft actor-critic over the same Replay:  SAC(env, hidden=(64, 64), alpha=1.0, auto_alpha=True) -- a tanh-squashed Gaussian policy with a
 state-dependent log-std, one or two critics, their targets and a learned temperature; agent.act(mode="sample" | "deterministic" |
 "uniform"), agent.update(mem, n_updates, batch_size) or agent.plan(...).capture() for ONE graph (libbeacon_sac.so, include/beacon_sac.h)
+Value-based learning for the discrete envs over the same Replay:  DQN(env, hidden=(64, 64), double=True, dueling=False, huber=1.0, eps=0.1)
+-- one Q network with an output per action and its target; agent.act(mode="greedy" | "epsilon" | "uniform") -> int32 [B] actions,
+mem.append(ro) from int32 rollout actions, agent.update(mem, n_updates, batch_size, target_every) or agent.plan(...).capture() for ONE
+graph (libbeacon_dqn.so, include/beacon_dqn.h)
 Multi-agent shkadov under one shared policy:  Actor(env, per_jet=True) -- every (replica, jet) a row of that actor and that update
 
 Importing the package does not touch the GPU; constructing an env does, and raises if the HIP
@@ -32,6 +36,7 @@ from .learner import Learner  # noqa: F401
 from .epochs import Plan  # noqa: F401
 from .td3 import TD3, Replay  # noqa: F401
 from .sac import SAC  # noqa: F401
+from .dqn import DQN  # noqa: F401
 from .lorenz import lorenz  # noqa: F401
 from .vortex import vortex  # noqa: F401
 

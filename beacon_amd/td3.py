@@ -166,13 +166,15 @@ class Replay(object):
     Not covered: compaction (a row with live = 0 occupies a slot and weighs nothing), prioritised sampling, n-step returns."""
 
     def __init__(self, agent, capacity):
-        from . import sac as _sac            # (here, not at the top: sac imports this module)
-        if not isinstance(agent, (TD3, _sac.SAC)):
+        from . import dqn as _dqn, sac as _sac            # (here, not at the top: both import this module)
+        if not isinstance(agent, (TD3, _sac.SAC, _dqn.DQN)):
             raise ValueError("Replay: agent must be a beacon_amd.TD3, got %r" % (type(agent).__name__,))
         if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or not 1 <= int(capacity) < 1 << 31:
             raise ValueError("Replay: capacity must be an integer in 1 .. 2^31 - 1, got %r" % (capacity,))
         self.agent, self.capacity = agent, int(capacity)
-        # a SAC agent's memory is this library's too: its replay_cfg is a bcn_td3_cfg of the same batch, dims, dtype and widths
+        # a SAC agent's memory is this library's too: its replay_cfg is a bcn_td3_cfg of the same batch, dims, dtype and widths; a DQN
+        # agent's likewise, with act_dim = 1 (the action index), and its append is libbeacon_dqn.so's: ro.act is int32 [T, B] there
+        self._int_act = isinstance(agent, _dqn.DQN)
         self.cfg, self.lib = (agent.cfg, agent.lib) if isinstance(agent, TD3) else (agent.replay_cfg, load())
         self.tdtype, self.device = agent.tdtype, agent.device
         self.layout, nbytes = layout("replay", self.cfg, self.capacity)
@@ -195,13 +197,21 @@ class Replay(object):
         if int(ro.batch) != a.batch or T * a.batch > self.capacity:
             raise ValueError("Replay.append: a rollout of T = %d steps of %d replicas; this memory takes T B <= %d of %d replicas"
                              % (T, int(ro.batch), self.capacity, a.batch))
+        if self._int_act and (ro.act.dtype != torch.int32 or ro.act.device != self.device or tuple(ro.act.shape) != (T, a.batch)):
+            raise ValueError("Replay.append: ro.act must be int32 [%d, %d] on %s for a DQN agent (the rollout of a discrete env), got %s %s"
+                             % (T, a.batch, self.device, str(ro.act.dtype).replace("torch.", ""), tuple(ro.act.shape)))
         for name, cols in (("obs", a.obs_dim), ("final_obs", a.obs_dim), ("act", a.act_dim), ("rwd", None)):
+            if self._int_act and name == "act":
+                continue
             t = getattr(ro, name)
             if t.dtype != self.tdtype or t.device != self.device or (cols is not None and t.shape[-1] != cols):
                 raise ValueError("Replay.append: ro.%s must be %s on %s%s" % (name, str(self.tdtype).replace("torch.", ""), self.device,
                                                                             "" if cols is None else " with rows of %d" % cols))
         stream = a._stream()
         self._keep = ro
+        if self._int_act:
+            a._append(self, ro, T)
+            return self
         _check(self.lib.bcn_replay_append(C.byref(self.cfg), self.capacity, _p(self.buf), T, _p(ro.obs), _p(ro.act), _p(ro.rwd), _p(ro.done),
                                           _p(ro.trunc), _p(ro.valid), _p(ro.final_obs), _p(ro.cursor), stream))
         return self
