@@ -26,6 +26,10 @@ Value-based learning for the discrete envs over the same Replay:  DQN(env, hidde
 -- one Q network with an output per action and its target; agent.act(mode="greedy" | "epsilon" | "uniform") -> int32 [B] actions,
 mem.append(ro) from int32 rollout actions, agent.update(mem, n_updates, batch_size, target_every) or agent.plan(...).capture() for ONE
 graph (libbeacon_dqn.so, include/beacon_dqn.h)
+Evolution strategies, one policy per member of a population:  ES(env, members=None, hidden=(64, 64), sigma=0.05, lr=0.01) -- antithetic
+Gaussian perturbations of one parameter vector, replica b under member b // R of the population in ONE act launch (an MLP whose
+weights differ per row group), first-episode returns as fitness, centred ranks and Adam; agent.begin(), agent.act(), agent.observe(),
+agent.update(), agent.act(shared=True) to evaluate theta; no backward pass, no replay memory (libbeacon_es.so, include/beacon_es.h)
 Multi-agent shkadov under one shared policy:  Actor(env, per_jet=True) -- every (replica, jet) a row of that actor and that update
 
 Importing the package does not touch the GPU; constructing an env does, and raises if the HIP
@@ -37,6 +41,7 @@ from .epochs import Plan  # noqa: F401
 from .td3 import TD3, Replay  # noqa: F401
 from .sac import SAC  # noqa: F401
 from .dqn import DQN  # noqa: F401
+from .es import ES  # noqa: F401
 from .lorenz import lorenz  # noqa: F401
 from .vortex import vortex  # noqa: F401
 
